@@ -12,17 +12,21 @@ Workloads (BASELINE.json configs):
 A step = one full pass of the hot path over the rank's bins, the raw records staged in HBM beforehand
 (umiclust_stage, untimed): vsearch's load-time work (umiclust_prepare: length filter and stable length sort, K1
 DUST / 4-bit codes / unique 8-mers of both strands), greedy blocks of K2 prefilter + K3 walk alignment + host
-resolution, K3T traceback for members, K4 consensus, and the result download.  Config 2 (N = 1) also runs the
-file leg (`e2e`, on by default, --no-e2e skips it): the same bin written as a FASTA with 1,500-nt `seq=` reads,
-then read FASTA -> cluster -> files written (umiclust_run_fasta, the reference's boundary:
-vsearch_umi_cluster.py:17-56) and the fused drop-in (umiclust_run_fasta_parse); each writer is followed by a
+resolution, K3T traceback for members, K4 consensus, and the result download.  A plain run sets up,
+warms up, times the steps and prints the result line; everything measured beside the headline figure runs only with
+--full: the CPU baseline (`cpu_baseline`, --no-cpu-baseline skips it) and, for config 2 (N = 1), the file leg (`e2e`,
+--no-e2e skips it): the same bin written as a FASTA with 1,500-nt `seq=` reads, then read FASTA -> cluster -> files
+written (umiclust_run_fasta, the reference's boundary: vsearch_umi_cluster.py:17-56) and the fused drop-in (umiclust_run_fasta_parse); each writer is followed by a
 replay of the same files (sizes, contiguous thread split, one streamed file; no formatting: tools/io_probe.c
 io_probe_replay) as a reference point, write_replay_ratio = replay seconds / writer seconds.  It is NOT a bound:
 the replay does not reissue the writer's exact system calls (open flags, directory order, chunking) and runs
 against a filesystem the writer has just filled and emptied, so the ratio can exceed 1 (round 4: 1.10).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--no-e2e]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full [--no-e2e]] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+--dump-outputs DIR writes what the last timed step computed (the arrays umiclust_fetch hands a caller: cluster,
+strand, centroid, consensus) as DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of larger outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 --gpus N without a launcher (no WORLD_SIZE in the environment) starts N ranks itself through
 torch.distributed.run before anything touches a GPU; under a launcher WORLD_SIZE must equal N.
 """
@@ -399,6 +403,40 @@ def breakdown(stats: list) -> dict:
     return {x: sum(s[x] for s in stats) for x in k}
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # of the 64 MB a dump may hold: room for the .npy headers
+
+
+def dump_outputs(d: str, results: list, prefix: str = "") -> None:
+    """The last step's results (one umiclust_fetch dict per bin, in bin order) as d/<prefix><name>.npy: per read the
+    cluster id, strand and centroid flag, per cluster the consensus length, and the consensus bytes end to end, bins
+    concatenated.  float32 where every value is exact in it, else float64.  If the arrays exceed the budget together,
+    each array over 1 MiB is cut to the same fraction of its elements, picked by a generator with a fixed seed (in
+    order), so two runs with the same arguments sample the same positions."""
+    import numpy as np
+    cat = lambda xs, t: np.concatenate([np.asarray(x, t) for x in xs]) if xs else np.zeros(0, t)  # noqa: E731
+    arrays = {
+        "n_clusters": np.asarray([r["n_clusters"] for r in results], np.int64),
+        "cluster": cat([r["cluster"] for r in results], np.int64),
+        "strand": cat([r["strand"] for r in results], np.int64),
+        "centroid": cat([r["centroid"] for r in results], np.int64),
+        "consensus_length": cat([[len(c) for c in r["consensus"]] for r in results], np.int64),
+        "consensus": cat([np.frombuffer("".join(r["consensus"]).encode(), np.uint8) for r in results], np.int64),
+    }
+    out = {k: a.astype(np.float32 if a.size == 0 or np.abs(a).max() < (1 << 24) else np.float64)
+           for k, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(20240601)
+        small = sum(a.nbytes for a in out.values() if a.nbytes <= (1 << 20))  # kept whole
+        frac = (DUMP_BUDGET_BYTES - small) / (total - small)
+        for k, a in out.items():
+            if a.nbytes > (1 << 20):
+                out[k] = a[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, f"{prefix}{k}.npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,8 +454,14 @@ def main() -> None:
                     help="reads of the sequential (--threads 1) CPU side figure's prefix")
     ap.add_argument("--cpu-sample-mt", type=int, default=200000,
                     help="reads of the CPU baseline's prefix in vsearch's --threads mode (the GPU line's policy)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the file leg (config 2, N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline figure: the CPU baseline and (config 2, N = 1) "
+                         "the file leg; off by default, so a plain run only sets up, warms up and times its steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (float32/float64, at "
+                         "most 64 MB in all: a fixed, seeded sample of anything larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the file leg (config 2, N = 1)")
     ap.add_argument("--lanes", type=int, default=8,
                     help="configs 3/4: bins clustered concurrently per GPU (one device context per lane; 8 measured "
                          "best on config 3 with blocks across length changes: profiles/r03/mixlen_ab.json)")
@@ -616,6 +660,9 @@ def main() -> None:
             dg["rounds"].append({str(int(sel[b])): binset.digest(x) for b, x in enumerate(r.results())})
         with open(f"{args.digest_out}.rank{rank}.json", "w") as fh:
             json.dump(dg, fh)
+    if args.dump_outputs:
+        res = [ctx.fetch()] if umis is not None else [x for r in runners for x in r.results()]
+        dump_outputs(args.dump_outputs, res, prefix=f"rank{rank}_" if world > 1 else "")
     if rank == 0:
         flat = [s for st in stats for s in st]
         roof, align = roofline(flat, args.config, args.traffic_json, tl_union)
@@ -680,7 +727,7 @@ def main() -> None:
             out["pack_reads"] = args.pack_reads
             out["lanes"] = args.lanes
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if umis is not None:
                 # the reference's operating mode (vsearch --threads on every core) is the baseline; the
                 # 1-thread sequential definition on a smaller prefix rides along
@@ -702,7 +749,7 @@ def main() -> None:
             else:
                 cpu = cpu_baseline_bins(runners[0].binset.bins, args.identity, lens)
         out["cpu_baseline"] = cpu
-        if not args.no_e2e and args.config == 2 and world == 1:
+        if args.full and not args.no_e2e and args.config == 2 and world == 1:
             out["e2e"] = e2e_leg(ctx, umis, args.identity, lens, threads=args.threads)
             # SURVEY §8d's UMIs/s (FASTA in -> files written) beside the HBM-resident value
             out["e2e_umis_per_s"] = out["e2e"]["umis_per_s"]

@@ -10,7 +10,7 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 B="bench.py --steps 1 --warmup 0 --no-cpu-baseline $*"
-timeout -k 10 300 python3 -u bench.py --steps 3 --warmup 1 "$@" > "$out/bench.json" 2> "$out/bench.err" &&
+timeout -k 10 300 python3 -u bench.py --steps 3 --warmup 1 --full "$@" > "$out/bench.json" 2> "$out/bench.err" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 $B \
     > "$out/trace.log" 2>&1 &&
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o run -- python3 $B \
