@@ -53,6 +53,7 @@
 #include "../../include/umiclust.h"
 #include "host_io.h"
 #include "resolve.h"
+#include "tunables.h"
 #include "umiclust_internal.h"
 
 using namespace uc;
@@ -340,24 +341,13 @@ struct umiclust_ctx {
   std::vector<uint8_t> cent_len;
   int32_t cnt_ge[kMaxLen + 1] = {};  // centroids of length >= L
   // two passes in flight (software pipeline over blocks) + round B on a side stream
-  Pass pass[kPeerTiles];          // passes in flight (the pipeline depth: UMICLUST_DEPTH, <= kPeerTiles)
+  Pass pass[kPeerTiles];          // passes in flight (`depth` of them, <= kPeerTiles)
   Tile blk_tile[kPeerTiles + 1], solo_tile;  // per-block peer tiles (ring of depth + 1), overflow re-runs
   Tile round_tile[2];             // O4 batched rounds: a pass's window from its first query's round start
   // passes in flight: 2; 3 (window of three blocks) hides more host time but its extra peers cost more than that
   // on configs 2/3/5 (profiles/r02/pipeline_depth_sweep.json)
   static constexpr int32_t depth = 2;
-  // split passes (depth 2, UMICLUST_SPLIT=0 turns them off): a block's counting runs against the index
-  // before the block two ahead is resolved, that block's hits flagged; only the merge and the alignment
-  // wait for its resolution, so the counting leaves the host <-> device critical cycle
-  int32_t split_env = -1;         // UMICLUST_SPLIT (-1: single-bin loads split, multi-bin sets do not)
-  bool pin = true;                 // UMICLUST_PIN=0: host resolve threads not kept in the caller's L3 domain (L3Pin;
-                                   // config 2 on two boxes: 3.41-3.90 M unpinned, 3.84-3.93 M pinned, profiles/r02/pin_ab.json);
-                                   // off by default when LOCAL_WORLD_SIZE > 1
-  bool pin_forced = false;         // UMICLUST_PIN=1: pinned even beside other contexts / ranks
-  int par_min = kParInorderMin;    // UMICLUST_PAR_MIN: open queries from which it runs on the pool
-  int32_t band_pairs = 140000;     // UMICLUST_BAND: alignment launches of at most this many pairs run banded
-                                   // (launch bound: a few one-lane waves per SIMD); 70,000 before the faster
-                                   // k_align_pk (profiles/r03/band_ab.json)
+  Tunables tun;                   // the UMICLUST_* switches, as umiclust_create read them (tunables.h)
   DevBuf<int32_t> d_seq2ord;      // [seqno - bin start] centroid ordinal or -1 (the merge's flagged hits)
   PinBuf<int32_t> h_seq2ord;
   hipEvent_t a_ev[4][3] = {};     // counting halves, ring by block: begin / end / spare
@@ -374,9 +364,6 @@ struct umiclust_ctx {
   void join_release() {
     if (in_release.joinable()) in_release.join();
   }
-  // host threads of resolve_pass (caller included); 0: 8 while this is the process's only context (config 2: host
-  // resolve 0.22 -> 0.14 s per step, profiles/r03/resolve_threads_ab.json), 4 beside other contexts (bin-set lanes)
-  int32_t resolve_threads = 0;
   DevBuf<uint16_t> arena;         // postings of every tile (one buffer, one descriptor per pass)
   uint64_t sealed_slot0 = 0;      // arena index of sealed tile 0's slot
   int32_t index_end = 0;          // centroid ordinals [0, index_end) are indexed
@@ -414,57 +401,34 @@ struct umiclust_ctx {
   };
   std::vector<BinOut> bout;
   umiclust_stats stats{};
-  int32_t block_size = 8192;
-  // UMICLUST_BLOCK unset: a bin of n queries uses blocks of about n / block_div (>= block_min): a small bin's
-  // window then holds fewer same-molecule peers (fewer speculative peer alignments and overflows)
-  int32_t block_div = 16;
-  static constexpr int32_t block_min = 2048;
-  // UMICLUST_MIXLEN=0: blocks end at every query-length change (one alignment launch per round); =1: a block spans
-  // up to kSegLens lengths (one launch per length and round): a small bin is then a few passes, not one per length
+  static constexpr int32_t block_min = 2048;  // the smallest default block (Tunables::block_div)
   // k_pack writes the outcomes and records straight into pinned host memory (true) or into device buffers copied by
   // DMA (false).  Set per clustering call: DMA with one context in the process (config 2: 4.33-4.36 vs 4.21-4.22 M
   // UMIs/s, the direct PCIe writes held k_pack at 133 us on the pass chain), direct with several (config 3, 8 lanes:
   // 7.56-7.60 vs 6.42-6.47 M: the lanes' copy dispatches contend for the hardware queues).
   bool rec_direct = false;
   static constexpr int32_t kDirectRecQ = 4096;  // blocks of at most this many queries write their records directly
-  int32_t mix_len = -1;  // -1: bins whose default block is below kMaxBlock (the bin has < 16 x kMaxBlock queries)
   // speculative walk below this best k-mer count (20 and 30 equal, 45 slower: profiles/r03/spec_ab)
   static constexpr int32_t spec_thr = 30;
   // relevant peers certain to become members are not aligned speculatively (config 2 4.02 -> 4.14 M, round 4)
   static constexpr bool peer_cert = true;
-  int32_t pf1_lds = 10240;  // UMICLUST_PF1: one-wave counting units up to this LDS per unit (0: never)
-  int32_t regrow_depth = kPeerCap / 4;  // UMICLUST_REGROW_DEPTH: a block whose deepest peer list reaches this is not clean
-  int32_t pt_side = 1;       // UMICLUST_PT_SIDE: whole passes build the next peer tiles on st_b beside the counting
-                             // (1: single-bin loads; 2: always; 0: on the main stream, as before round 6)
-  hipEvent_t pt_ev = nullptr;
-  bool pt_pending = false;   // pt_ev recorded since the main stream last waited for it
-  int32_t arrange = 1;       // UMICLUST_ARRANGE: bank-aware posting order in large tiles (1) / small tiles (2)
-  int32_t regrow = 8;        // UMICLUST_REGROW: clean shallow blocks before a halved block size doubles (0: never)
+  static constexpr int32_t regrow_depth = kPeerCap / 4;  // a block whose deepest peer list reaches this is not clean
+  hipEvent_t pt_ev = nullptr;  // whole passes of single-bin loads: the next peer tile is built on st_b
+  bool pt_pending = false;     // pt_ev recorded since the main stream last waited for it
   int32_t last_max_npeer = 0;
-  bool pf_probe = getenv("UMICLUST_PFPROBE") != nullptr;  // the counting kernel's phases without the count loop
   DevBuf<uint32_t> d_probe;
   // lazy peers below this new-centroid rate (per mille; higher rates lose: profiles/r02/lazy_peer_sweep.json)
-  int32_t lazy_permille = 5;  // UMICLUST_LAZY (0: never lazy)
-  int32_t rb_wprio = 0;       // round B's alignment waves at raised issue priority (UMICLUST_RB_WPRIO)
-  int32_t rb_direct = 4096;   // round B: at most this many pairs read / written in pinned memory (UMICLUST_RB_DIRECT)
+  static constexpr int32_t lazy_permille = 5;
+  static constexpr int32_t rb_direct = 4096;  // round B: at most this many pairs read / written in pinned memory
   int32_t o4_T = 0;               // policy O4 (umiclust_params.policy_threads): rounds of o4_T queries; 0 = sequential
   int32_t b_hint = 1 << 30;       // block size the last bin ended with (peer overflows halve it)
   int al_level = 0;                 // the alignment stream: 0 prioritised (al_priority), -1 plain (set_priority -1)
   int st_level = 0, prio_user = 0;  // the main stream's priority now / as umiclust_set_priority left it
   int64_t dbg[4] = {0, 0, 0, 0};  // UMICLUST_DEBUG: mispredicted peers, saved peers, blocked, -
-  // UMICLUST_DEBUG: per-block lines and sequential in-order resolution; UMICLUST_DEBUG=2: the per-bin summary only (the
-  // production code path, with its parallel in-order phase)
-  bool debug = getenv("UMICLUST_DEBUG") != nullptr && strcmp(getenv("UMICLUST_DEBUG"), "2") != 0;
   int64_t dbg_q[4] = {0, 0, 0, 0};
-  // UMICLUST_WALK_DUMP=<file>: per sorted seqno of the bin, the alignments each strand's walk counted and the
-  // path that resolved it (0 device, 1 classify thread, 2 in order, 3 round B) -- a parity-debugging aid
-  const char* walk_dump = getenv("UMICLUST_WALK_DUMP");
-  // UMICLUST_RESOLVE_DUMP=<prefix>[:i,j,...]: record resolve_block's inputs and outputs of the i-th, j-th, ... passes
-  // of the context (default 10, 40, 80) to <prefix>.<i>.bin (single-bin clustering only)
-  const char* resolve_dump = getenv("UMICLUST_RESOLVE_DUMP");
   int64_t n_resolved = 0;
-  bool dump_want(int64_t k) const {
-    const char* c = strchr(resolve_dump, ':');
+  bool dump_want(int64_t k) const {  // UMICLUST_RESOLVE_DUMP's pass list
+    const char* c = strchr(tun.resolve_dump, ':');
     if (!c) return k == 10 || k == 40 || k == 80;
     for (const char* p = c + 1; *p;) {
       char* e;
@@ -530,7 +494,7 @@ int affinity_cpus() {
 // phase's workers spin on each other's flags, so more threads than CPUs would only take slices from the worker
 // the others wait on
 int pool_threads(const umiclust_ctx* c) {
-  const int want = c->resolve_threads > 0 ? c->resolve_threads : (g_live_ctx.load() > 1 ? 4 : 8);
+  const int want = c->tun.resolve_threads > 0 ? c->tun.resolve_threads : (g_live_ctx.load() > 1 ? 4 : 8);
   return std::max(1, std::min(want, affinity_cpus()));
 }
 
@@ -539,7 +503,7 @@ struct L3Pin {
   bool on = false;
   umiclust_ctx* c = nullptr;
   explicit L3Pin(umiclust_ctx* ctx) : c(ctx) {
-    if (!c->pin || (g_live_ctx.load() > 1 && !c->pin_forced) || sched_getaffinity(0, sizeof saved, &saved) != 0)
+    if (!c->tun.pin || (g_live_ctx.load() > 1 && !c->tun.pin_forced) || sched_getaffinity(0, sizeof saved, &saved) != 0)
       return;
     // the pool is created with the caller's own mask before the caller is narrowed, so restoring `saved` on
     // both undoes the call's pinning completely
@@ -659,9 +623,9 @@ void build_tile(umiclust_ctx* c, Tile& t, const int32_t* map, int32_t first, int
   c->hip(launch_index_scan(t.hist.p, t.partial.p, t.off.p, t.cursor.p, post, st), "index scan");
   c->hip(launch_index_fill(c->d_kmers.p, c->d_nk.p, map, first, n, xoff, vbase, seg_mod, t.cursor.p, post, st),
          "index fill");
-  // bank-aware posting order (kernels.hip k_list_arrange): large tiles (bit 0: the base tile and sealed tiles, built
-  // once per fold / seal) and small ones (bit 1: delta, peer and round tiles, rebuilt every block)
-  if (n > 0 && (c->arrange & (n >= 2 * kDelta ? 1 : 2)))
+  // bank-aware posting order (kernels.hip k_list_arrange): large tiles (the base tile and sealed tiles, built
+  // once per fold / seal); the small ones (delta, peer and round tiles, rebuilt every block) keep the fill's order
+  if (n >= 2 * kDelta)
     c->hip(launch_index_arrange(t.off.p, post, st), "index arrange");
   t.n = n;
   t.built_n = n;
@@ -883,7 +847,7 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   // list table of the lean kernel: every k-mer of the block's length in every tile it reads
   a.nlist_cap = std::min(kMaxKmers * 12, std::max(1, block_maxlen(c, q0, nq) - 7) *
                                               ((a.nseg > 0 ? a.seg_tile[1] - a.seg_tile[0] : 0) + kPeerTiles));
-  a.pf1_lds = c->pf1_lds;
+  a.pf1_lds = c->tun.pf1_lds;
   a.ppeer_id = P.d_ppeer_id.p;
   a.ppeer_count = P.d_ppeer_count.p;
   a.pnpeer = P.d_pnpeer.p;
@@ -910,7 +874,7 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
     c->hip(launch_prefilter(a, st, 1), "prefilter (count)");
     c->hip(hipEventRecord(P.ev_c[1], st), "event");
     c->stats.counter_cells += (int64_t)nq * c->both * a.ncent;
-    if (c->pf_probe) launch_pf_probe(c, a, st);
+    if (c->tun.pf_probe) launch_pf_probe(c, a, st);
     c->hip(launch_prefilter(a, st, 2), "prefilter");
     P.c_timed = true;
   } else {
@@ -948,7 +912,7 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
     for (int32_t i = 0; i < nsg; i++)
       if (nql[i])
         c->hip(launch_align(ds, lmax - i, c->ambig, P.d_pq.p + sg.base[i], P.d_pt.p + sg.base[i], nql[i] * both * per_qs,
-                            cnt + i, P.d_outidx.p + sg.base[i], c->sc, P.d_res.p, st, c->band_pairs),
+                            cnt + i, P.d_outidx.p + sg.base[i], c->sc, P.d_res.p, st, c->tun.band_pairs),
                what);
   };
   c->hip(launch_walk(-1, q0, nqs, both, c->spec_thr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p, P.d_res.p,
@@ -1076,7 +1040,7 @@ void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile*
   a.units = P.d_units.p;
   a.nunits = P.d_anunits.p;
   a.nlist_cap = std::min(kMaxKmers * 12, std::max(1, block_maxlen(c, q0, nq) - 7) * (nv + kPeerTiles));
-  a.pf1_lds = c->pf1_lds;
+  a.pf1_lds = c->tun.pf1_lds;
   a.ppeer_id = P.d_ppeer_id.p;
   a.ppeer_count = P.d_ppeer_count.p;
   a.pnpeer = P.d_pnpeer.p;
@@ -1087,7 +1051,7 @@ void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile*
   c->hip(launch_prefilter(a, st, 1), "prefilter (count)");
   c->hip(hipEventRecord(c->a_ev[slot][1], st), "event");
   c->stats.counter_cells += (int64_t)nq * c->both * a.ncent;
-  if (c->pf_probe) launch_pf_probe(c, a, st);
+  if (c->tun.pf_probe) launch_pf_probe(c, a, st);
   c->last_a_slot = slot;
   P.a_live = true;
   P.a_q0 = q0;
@@ -1104,7 +1068,7 @@ void write_resolve_dump(const umiclust_ctx* c, const ResolveEnv& env, int32_t q0
                         const uint32_t* recs, uint32_t nrec, const std::vector<uint32_t>& bpq,
                         const std::vector<uint32_t>& bpt, const std::vector<uint32_t>& bres,
                         const std::vector<int32_t>& new_cents, const ResolveStats& rs) {
-  const std::string path = std::string(c->resolve_dump, strcspn(c->resolve_dump, ":")) + "." +
+  const std::string path = std::string(c->tun.resolve_dump, strcspn(c->tun.resolve_dump, ":")) + "." +
                            std::to_string(c->n_resolved - 1) + ".bin";
   FILE* f = fopen(path.c_str(), "wb");
   if (!f) return;
@@ -1241,8 +1205,8 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
   // (and only when every pool thread has a CPU of its own under the caller's current mask, L3Pin's included: its
   // workers spin-wait on each other)
   env.par_inorder = g_live_ctx.load() <= 1 && c->pool->size() <= affinity_cpus();
-  env.par_min = c->par_min;
-  env.debug = c->debug;
+  env.par_min = c->tun.par_min;
+  env.debug = c->tun.debug == 1;
   env.target = c->target.data();
   env.strand = c->strand.data();
   env.walk_dump = c->wd.empty() ? nullptr : c->wd.data();
@@ -1274,16 +1238,14 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
       pres = c->d_bres.p;
     }
     c->hip(hipEventRecord(c->evb[0], sb), "event");
-    Scoring scb = c->sc;
-    scb.wave_prio = c->rb_wprio;
     // the pairs are in query order: one launch per run of one query length
     int nl = 0;
     for (int32_t x0 = 0; x0 < nb; nl++) {
       const int32_t L = c->hlen[bpq[x0] >> 1];
       int32_t x1 = x0 + 1;
       while (x1 < nb && c->hlen[bpq[x1] >> 1] == L) x1++;
-      c->hip(launch_align(dev_seqs(c), L, c->ambig, pq + x0, pt + x0, x1 - x0, nullptr, nullptr, scb, pres + x0, sb,
-                          c->band_pairs),
+      c->hip(launch_align(dev_seqs(c), L, c->ambig, pq + x0, pt + x0, x1 - x0, nullptr, nullptr, c->sc, pres + x0, sb,
+                          c->tun.band_pairs),
              "align B");
       x0 = x1;
     }
@@ -1302,7 +1264,7 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
   };
   // UMICLUST_RESOLVE_DUMP: the pass's inputs, round-B pairs / results and outputs, for the host-only replay
   // (tools/resolve_tsan_main.cpp: the ThreadSanitizer harness of the CPU suite)
-  const bool dump = c->resolve_dump && !c->pack_on && c->dump_want(c->n_resolved);
+  const bool dump = c->tun.resolve_dump && !c->pack_on && c->dump_want(c->n_resolved);
   c->n_resolved++;
   std::vector<uint32_t> dpq, dpt, dres;
   std::vector<uint8_t> state_in;
@@ -1337,7 +1299,7 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
     write_resolve_dump(c, env, q0, nq, w0, state, state_in, hq, recs, *P.h_reccount.p, dpq, dpt, dres, new_cents, rs);
   t_host += th - rs.t_round_b_s;
   // UMICLUST_DEBUG: one line per resolved block (where the host's time goes, block by block)
-  if (c->debug)
+  if (c->tun.debug == 1)
     fprintf(stderr, "blk q0 %d nq %d new %zu wait %.3f classify %.3f inorder %.3f roundB %.3f (%lld pairs) merged %lld "
             "deferred %lld ms-since-wait %.3f\n", q0, nq, new_cents.size(), 1e3 * (tc0 - tsync0), 1e3 * rs.t_classify_s,
             1e3 * rs.t_inorder_s, 1e3 * rs.t_round_b_s, (long long)rs.pairs_round_b, (long long)rs.n_merged_walks,
@@ -1478,11 +1440,7 @@ hipError_t main_stream_priority(umiclust_ctx* c, int level) {
 }
 
 void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t npk = 1) {
-  static const int rec_env = [] {
-    const char* e = getenv("UMICLUST_REC_DIRECT");
-    return e ? atoi(e) : -1;
-  }();
-  c->rec_direct = rec_env >= 0 ? rec_env > 0 : g_live_ctx.load() > 1;
+  c->rec_direct = g_live_ctx.load() > 1;
   const double t0 = now_s();
   if (bin < 0 || npk < 1 || bin + npk >= (int32_t)c->bin_s.size())
     c->fail(UMICLUST_EINVAL, "bins [%d, %d) out of range", bin, bin + npk);
@@ -1526,12 +1484,12 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
   c->hip(hipMemsetAsync(c->d_seq2ord.p, 0xff, (size_t)n * 4, c->st), "memset");
   std::vector<uint8_t> state_buf((size_t)n, ST_UNDET);
   StateView state{state_buf.data(), s0};
-  if (c->walk_dump) c->wd.assign((size_t)n * 4, -1);
+  if (c->tun.walk_dump) c->wd.assign((size_t)n * 4, -1);
   double t_pf = 0, t_al = 0, t_host = 0;
   // blocks of at most B queries of one length (the aligner is compiled per query length); a block's
   // peer tile fills one kPeerRegion of the prefilter counters, so B <= kMaxBlock
-  int32_t B = std::max(1, std::min<int32_t>(c->block_size, kMaxBlock));
-  if (c->block_div > 0) B = std::min<int32_t>(B, std::max<int32_t>(c->block_min, ((s1 - s0) / c->block_div + 255) & ~255));
+  int32_t B = std::max(1, std::min<int32_t>(c->tun.block_size, kMaxBlock));
+  if (c->tun.block_div > 0) B = std::min<int32_t>(B, std::max<int32_t>(c->block_min, ((s1 - s0) / c->tun.block_div + 255) & ~255));
   c->pass_B = B;
   for (Pass& P : c->pass) ensure_pass_buffers(c, P, B);
   // postings arena: the base, delta, peer-ring and solo slots, then the sealed tile slots in creation
@@ -1558,7 +1516,7 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
   std::vector<std::pair<int32_t, int32_t>> blocks;
   // blocks across length changes: bins below the full block size (config 3: 4.15 vs 3.61 M UMIs/s; a 2M-read bin
   // gains nothing, its length runs are many blocks long: profiles/r03/mixlen_ab.json)
-  const bool mix = c->mix_len > 0 || (c->mix_len < 0 && (B < kMaxBlock || c->pack_on));
+  const bool mix = c->tun.mix_len > 0 || (c->tun.mix_len < 0 && (B < kMaxBlock || c->pack_on));
   // the blocks from query `from` on, at most `bmax` queries (of one length each unless mix)
   auto split_blocks = [&](int32_t from, int32_t bmax) {
     // packs: bmax (a deep cluster's halved size) holds until the end of `from`'s bin, the next bins start at B
@@ -1739,7 +1697,7 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
   // split passes shorten the host <-> device cycle of one bin at the price of a wider counting window;
   // multi-bin sets run several lanes on one GPU, which is throughput-bound: there the whole passes win
   // (configs 2 / 5: +12 % / +2 %, config 3: -6 %; profiles/r02/split_ab.json)
-  const bool split = !T4 && (c->split_env >= 0 ? c->split_env != 0 : !multi_bin);
+  const bool split = !T4 && (c->tun.split_env >= 0 ? c->tun.split_env != 0 : !multi_bin);
   c->ix_st = (split && D == 2) ? c->st_b : nullptr;
   c->last_r_ev = nullptr;
   if (split && D == 2) {
@@ -1822,7 +1780,7 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
       append_centroids(c, new_cents);
       const double ta1 = now_s();
       c->stats.n_blocks++;
-      lazy = c->lazy_permille > 0 && (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
+      lazy = (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
       c->stats.n_lazy_passes += (lazy && k + 2 < nb) ? 1 : 0;
       if (k + 2 < nb) second_half(k + 2, k + 1, true);
       if (k + 3 < nb) count_half(k + 3, k + 1, 0);
@@ -1840,9 +1798,8 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
       // the build runs beside the main stream's counting instead of between two counting launches; the pass that
       // next enqueues on the main stream waits for it (enqueue_pass, pt_ev).  Before, it sat on the main stream.
       Tile& t = tile_of(k + D);
-      hipStream_t bst = nullptr;
-      if (c->pt_side == 2 || (c->pt_side == 1 && !multi_bin)) {  // config 2 +1.6 %, multi-lane config 3 -2 %
-        bst = c->st_b;
+      hipStream_t bst = multi_bin ? nullptr : c->st_b;  // config 2 +1.6 %, multi-lane config 3 -2 %
+      if (bst) {
         c->hip(hipStreamWaitEvent(bst, P.ev[1], 0), "wait");
         if (!c->pt_ev) c->hip(hipEventCreateWithFlags(&c->pt_ev, hipEventDisableTiming), "event");
       }
@@ -1893,7 +1850,7 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
     if (T4) pending.insert(pending.end(), new_cents.begin(), new_cents.end());
     else append_centroids(c, new_cents);
     c->stats.n_blocks++;
-    lazy = c->lazy_permille > 0 && (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
+    lazy = (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
     c->stats.n_lazy_passes += (lazy && k + D < nb) ? 1 : 0;
     // Regrowth: after `regrow` consecutive blocks without an overflow whose deepest peer list stayed below a quarter of
     // the cap, the blocks not yet queued are cut at twice the size.  With overflowing blocks resolved up to their first
@@ -1902,7 +1859,7 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
     // do not grow (3.33 / 3.36 M; ungated regrowth after 4 clean blocks: 2.47 M) -- profiles/r05/regrow_ab/.
     if (c->last_max_npeer >= c->regrow_depth) {
       clean = 0;  // a deep window: no regrowth yet, and it does not count as a clean block
-    } else if (c->regrow > 0 && b_eff < B && ++clean >= c->regrow && k + D < nb) {
+    } else if (c->tun.regrow > 0 && b_eff < B && ++clean >= c->tun.regrow && k + D < nb) {
       b_eff = std::min<int32_t>(B, b_eff * 2);
       c->stats.n_regrows++;
       clean = 0;
@@ -2074,35 +2031,31 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
   }
   c->stats.t_total_s = now_s() - t0;
   c->clustered = true;
-  if (c->walk_dump && !c->wd.empty()) {
-    if (FILE* f = fopen(c->walk_dump, "wb")) {
+  if (c->tun.walk_dump && !c->wd.empty()) {
+    if (FILE* f = fopen(c->tun.walk_dump, "wb")) {
       fwrite(c->wd.data(), 2, c->wd.size(), f);
       fclose(f);
     }
     c->wd.clear();
   }
-  if (getenv("UMICLUST_DEBUG"))
+  if (c->tun.debug) {  // the per-bin summary
     fprintf(stderr, "bin %d: n %d mispredicted %lld saved(seen) %lld blocked %lld deferred %lld\n", bin, n,
             (long long)c->dbg[0], (long long)c->dbg[1], (long long)c->dbg[2], (long long)c->stats.n_deferred);
-  if (getenv("UMICLUST_DEBUG"))
     fprintf(stderr, "bin %d: queries no-record %lld earlier-block-only %lld in-block %lld; pass-1 host %.3f s\n", bin,
             (long long)c->dbg_q[0], (long long)c->dbg_q[1], (long long)c->dbg_q[2], c->dbg_q[3] * 1e-9);
-  if (getenv("UMICLUST_DEBUG"))
     fprintf(stderr, "bin %d: strands inline %lld many-relevant %lld record-read %lld peers-scanned %lld\n", bin,
             (long long)c->dbg_p[0], (long long)c->dbg_p[1], (long long)c->dbg_p[2], (long long)c->dbg_p[3]);
-  if (getenv("UMICLUST_DEBUG"))
     fprintf(stderr, "bin %d: resolve wait %.3f hq-copy %.3f rec-copy %.3f classify %.3f in-order %.3f total %.3f s "
             "(round B and the rest %.3f: round-B round trips %.3f, rest of resolve_block %.3f, outside it %.3f)\n", bin,
             c->dbg_t[0], c->dbg_t[1], c->dbg_t[2], c->dbg_t[3], c->dbg_t[4], c->dbg_t[6],
             c->dbg_t[6] - c->dbg_t[0] - c->dbg_t[1] - c->dbg_t[2] - c->dbg_t[3] - c->dbg_t[4], c->dbg_t[8],
             c->dbg_t[9] - c->dbg_t[3] - c->dbg_t[4] - c->dbg_t[8],
             c->dbg_t[6] - c->dbg_t[0] - c->dbg_t[1] - c->dbg_t[2] - c->dbg_t[9]);
-  if (getenv("UMICLUST_DEBUG"))
     fprintf(stderr, "bin %d: host: split-pass appends %.3f, enqueue (peer tiles, appends, launches) %.3f s; bin %.3f s\n",
             bin, c->dbg_t[7], c->dbg_t[5], now_s() - t0);
-  if (getenv("UMICLUST_DEBUG"))
     fprintf(stderr, "bin %d: round B: %.0f round trips, %.0f launches, %.0f pairs, %.4f s between its first and last "
             "launch's events\n", bin, c->dbg_rb[1], c->dbg_rb[2], c->dbg_rb[3], c->dbg_rb[0]);
+  }
   for (double& x : c->dbg_rb) x = 0;
   for (double& x : c->dbg_t) x = 0;
   c->dbg_q[0] = c->dbg_q[1] = c->dbg_q[2] = c->dbg_q[3] = 0;
@@ -2291,7 +2244,7 @@ void prepare_impl(umiclust_ctx* c, const umiclust_params* p) {
   }
   const double tp2 = now_s();
   c->hip(hipStreamSynchronize(c->st), "sync load");
-  if (getenv("UMICLUST_DEBUG"))
+  if (c->tun.debug)
     fprintf(stderr, "umiclust: prepare: host sort %.4f s, after the K1 launch %.4f s, sync %.4f s\n", tp1 - tp0,
             tp2 - tp1, now_s() - tp2);
   c->ambig = c->h_amb.p[0] != 0;
@@ -2404,7 +2357,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
   if (cons_th.t.joinable()) cons_th.t.join();
   if (cons_err) std::rethrow_exception(cons_err);
   const double t_write = now_s() - t1;
-  if (getenv("UMICLUST_DEBUG"))
+  if (c->tun.debug)
     fprintf(stderr, "umiclust: file path: read %.3f s, cluster %.3f s, masked download %.3f s (%lld changed), "
                     "cluster files done at %.3f s, consout (beside them) at %.3f s\n", t_read, t1 - t0 - t_read, t_mask,
             (long long)c->n_changed, t_files, t_cons);
@@ -2444,7 +2397,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
       c->fail(UMICLUST_EINVAL, "in-process parse needs --clusterout_sort and --clusterout_id numbering");
     const double tj = now_s();
     if (pre_th.t.joinable()) pre_th.t.join();
-    if (c->debug) fprintf(stderr, "umiclust: fused: waited %.3f s for the header fields\n", now_s() - tj);
+    if (c->tun.debug == 1) fprintf(stderr, "umiclust: fused: waited %.3f s for the header fields\n", now_s() - tj);
     io::parse_clusters(f, cv, pp, work_dir, pr, pre.empty() ? nullptr : pre.data(), &unmaps.v);
   }
   c->stats.t_read_s = t_read;
@@ -2454,11 +2407,11 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
     Fasta* in = fin.release();
     std::vector<std::pair<void*, size_t>> outs;
     outs.swap(unmaps.v);
-    c->in_release = std::thread([in, outs] {
+    c->in_release = std::thread([in, outs, debug = c->tun.debug] {
       const double tr = now_s();
       for (auto& m : outs) munmap(m.first, m.second);
       delete in;
-      if (getenv("UMICLUST_DEBUG")) fprintf(stderr, "umiclust: file path: input released in %.3f s\n", now_s() - tr);
+      if (debug) fprintf(stderr, "umiclust: file path: input released in %.3f s\n", now_s() - tr);
     });
   }
   c->stats.t_run_s = now_s() - t0;
@@ -2469,31 +2422,6 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
 }  // namespace
 
 // ====================================================================== C ABI
-// Retired or misspelled UMICLUST_* switches fail loudly (once per process, on stderr) instead of being ignored in
-// silence: every switch the library or its Python binding reads is listed here.
-extern char** environ;
-static void warn_unknown_env() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    static const char* const known[] = {
-        "ARRANGE", "BAND", "BAND_WPRIO", "BLOCK", "DEBUG", "IO_THREADS", "LAZY", "MIXLEN", "O4", "OVERLAP_TEST_COLLIDE", "PAR_MIN", "PF1", "PFPROBE",
-        "PFPROF", "PIN", "PT_SIDE", "REC_DIRECT", "RB_DIRECT", "RB_PRIO", "RB_WPRIO", "REGROW", "REGROW_DEPTH", "RESOLVE_DUMP", "RESOLVE_THREADS", "SPLIT", "WALK_DUMP",
-        // read by the Python side (umiclust/, bench.py)
-        "DEVICE", "CRIT_PRIO", "PACK_READS", "BENCH_THREADS", "E2E_DIR"};
-    for (char** e = environ; e && *e; e++) {
-      if (strncmp(*e, "UMICLUST_", 9) != 0) continue;
-      const char* name = *e + 9;
-      const char* eq = strchr(name, '=');
-      const size_t len = eq ? (size_t)(eq - name) : strlen(name);
-      bool ok = false;
-      for (const char* k : known) ok = ok || (strlen(k) == len && strncmp(k, name, len) == 0);
-      if (!ok)
-        fprintf(stderr, "umiclust: warning: unknown environment variable UMICLUST_%.*s ignored (retired or misspelled)\n",
-                (int)len, name);
-    }
-  });
-}
-
 extern "C" {
 
 int32_t umiclust_abi_version(void) { return UMICLUST_ABI_VERSION; }
@@ -2533,7 +2461,6 @@ int32_t umiclust_timeline(int32_t device_id, int32_t kind, int32_t reset, double
   return 0;
 }
 
-
 // The alignment stream is created with the device's greatest stream priority: a pass's walk/align/pack chain gates
 // the host's resolution of its block and through it the next passes.  A prioritised stream also gets a hardware
 // queue of its own class instead of sharing the normal-priority queues with the other lanes' streams (config 3, 4
@@ -2542,19 +2469,8 @@ int32_t umiclust_timeline(int32_t device_id, int32_t kind, int32_t reset, double
 static int al_priority() {
   int lo = 0, hi = 0;
   if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) return 0;
-  if (getenv("UMICLUST_DEBUG")) fprintf(stderr, "stream priorities: least %d greatest %d\n", lo, hi);
+  if (env_debug()) fprintf(stderr, "stream priorities: least %d greatest %d\n", lo, hi);
   return hi;
-}
-
-// the copy stream carries round B (the host waits for it): at the greatest priority with UMICLUST_RB_PRIO=1
-static hipError_t create_copy_stream(umiclust_ctx* c) {
-  const char* e = getenv("UMICLUST_RB_PRIO");
-  if (e && atoi(e) > 0) return hipStreamCreateWithPriority(&c->st_copy, hipStreamNonBlocking, al_priority());
-  return hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking);
-}
-
-static hipError_t create_al_stream(umiclust_ctx* c) {
-  return hipStreamCreateWithPriority(&c->st_al, hipStreamNonBlocking, al_priority());
 }
 
 umiclust_ctx* umiclust_create(int32_t device_id, int32_t* err) {
@@ -2571,7 +2487,8 @@ umiclust_ctx* umiclust_create(int32_t device_id, int32_t* err) {
   c->dev = device_id;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&c->st_b, hipStreamNonBlocking) != hipSuccess ||
-      create_copy_stream(c) != hipSuccess || create_al_stream(c) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->st_al, hipStreamNonBlocking, al_priority()) != hipSuccess ||
       hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
       hipEventCreate(&c->evb[0]) != hipSuccess || hipEventCreate(&c->evb[1]) != hipSuccess || [&] {
         for (Pass& P : c->pass)
@@ -2584,30 +2501,9 @@ umiclust_ctx* umiclust_create(int32_t device_id, int32_t* err) {
     return nullptr;
   }
   warn_unknown_env();
-  if (const char* e = getenv("UMICLUST_BAND")) c->band_pairs = std::max(0, atoi(e));
-  if (const char* e = getenv("UMICLUST_MIXLEN")) c->mix_len = atoi(e) != 0 ? 1 : 0;
-  if (const char* e = getenv("UMICLUST_PAR_MIN")) c->par_min = std::max(1, atoi(e));
-  if (const char* e = getenv("UMICLUST_PF1")) c->pf1_lds = std::max(0, atoi(e));
-  if (const char* e = getenv("UMICLUST_REGROW")) c->regrow = std::max(0, atoi(e));
-  if (const char* e = getenv("UMICLUST_ARRANGE")) c->arrange = atoi(e) & 3;
-  if (const char* e = getenv("UMICLUST_PT_SIDE")) c->pt_side = std::max(0, std::min(2, atoi(e)));
-  if (const char* e = getenv("UMICLUST_LAZY")) c->lazy_permille = std::max(0, std::min(1000, atoi(e)));
-  if (const char* e = getenv("UMICLUST_RB_DIRECT")) c->rb_direct = std::max(0, atoi(e));
-  if (const char* e = getenv("UMICLUST_RB_WPRIO")) c->rb_wprio = atoi(e) > 0 ? 1 : 0;
-  if (const char* e = getenv("UMICLUST_REGROW_DEPTH")) c->regrow_depth = std::max(1, std::min(kPeerCap + 1, atoi(e)));
-  if (const char* e = getenv("LOCAL_WORLD_SIZE")) c->pin = atoi(e) <= 1;
-  if (const char* e = getenv("UMICLUST_PIN")) {
-    c->pin = atoi(e) != 0;
-    c->pin_forced = atoi(e) == 1;
-  }
+  c->tun = read_tunables();
   io::set_live_contexts(++g_live_ctx);
-  if (const char* e = getenv("UMICLUST_SPLIT")) c->split_env = atoi(e) != 0 ? 1 : 0;
-  if (const char* e = getenv("UMICLUST_RESOLVE_THREADS")) c->resolve_threads = std::max(1, std::min(16, atoi(e)));
-  if (const char* b = getenv("UMICLUST_BLOCK")) {
-    c->block_size = std::max(1, std::min(kTile, atoi(b)));
-    c->block_div = 0;
-  }
-  if (getenv("UMICLUST_PFPROF")) {
+  if (c->tun.pf_prof) {
     if (c->pf_prof.ensure(24) != hipSuccess || hipMemset(c->pf_prof.p, 0, 24 * sizeof(unsigned long long)) != hipSuccess) {
       delete c;
       if (err) *err = UMICLUST_EDEVICE;
@@ -2921,7 +2817,7 @@ int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const ch
                "traceback");
       else
         c->hip(launch_align(ds, ql, amb != 0, d_pq.p + b0, d_pt.p + b0, (int32_t)(e - b0), nullptr, nullptr, sc,
-                            d_out.p + b0, c->st, c->band_pairs),
+                            d_out.p + b0, c->st, c->tun.band_pairs),
                "align");
       b0 = e;
     }
@@ -3004,7 +2900,7 @@ void overlap_table(umiclust_ctx* c, OvRun& R, const char* seqs, const int64_t* o
   // a 64-bit collision between two different sequences is detected exactly; the next seed is tried
   const uint64_t seeds[4] = {0x243f6a8885a308d3ull, 0x13198a2e03707344ull, 0xa4093822299f31d0ull,
                              0x082efa98ec4e6c89ull};
-  const bool test_collide = getenv("UMICLUST_OVERLAP_TEST_COLLIDE") != nullptr;  // first pass: 8-bit hashes
+  const bool test_collide = env_overlap_test_collide();  // first pass: 8-bit hashes
   for (int k = 0; k < 4; k++) {
     uint32_t coll = 0;
     const uint64_t hmask = (test_collide && k == 0) ? 0xffull : ~0ull;

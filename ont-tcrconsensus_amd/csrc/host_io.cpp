@@ -1,6 +1,7 @@
 // host_io.cpp -- the HIP-free host side of the drop-in boundary (see host_io.h).  Built by g++; the CPU
 // suite builds it again with ASan/UBSan and drives it from tools/host_asan_main.cpp.
 #include "host_io.h"
+#include "tunables.h"
 
 #include <fcntl.h>
 #include <sys/uio.h>
@@ -48,12 +49,8 @@ void set_live_contexts(int n) { g_io_ctx.store(std::max(1, n)); }
 // 16 threads per call with 8 lanes writing at once oversubscribed the box's 16-CPU quota: config 4's file
 // boundary at quarter scale, round 2 0.29 -> 0.63 M UMIs/s with 4 threads per lane (profiles/r05/io_threads_ab)
 int io_threads() {
-  static const int env = [] {
-    const char* e = getenv("UMICLUST_IO_THREADS");
-    return e ? std::max(1, std::min(atoi(e), 16)) : 0;
-  }();
-  if (env) return env;
-  return std::max(1, std::min(16, host_cpus() / g_io_ctx.load()));
+  static const int env = env_io_threads();
+  return env ? env : std::max(1, std::min(16, host_cpus() / g_io_ctx.load()));
 }
 
 Fasta::~Fasta() { release(); }
@@ -170,7 +167,7 @@ bool read_fasta(const char* path, Fasta& f) {
     if (!P.seq.empty()) memcpy(f.seq.data() + so[t], P.seq.data(), P.seq.size());
     for (size_t r = 1; r < P.seq_off.size(); r++) f.seq_off[rb[t] + r] = (int64_t)so[t] + P.seq_off[r];
   });
-  if (getenv("UMICLUST_DEBUG")) {
+  if (env_debug()) {
     const auto tr2 = std::chrono::steady_clock::now();
     fprintf(stderr, "umiclust: read_fasta: %d threads, parse %.3f s, merge %.3f s\n", T,
             std::chrono::duration<double>(tr1 - tr0).count(), std::chrono::duration<double>(tr2 - tr1).count());
@@ -767,7 +764,7 @@ void parse_clusters(const Fasta& f, const ClusterView& cv, const umiclust_parse_
     }
     return true;
   };
-  static const bool debug = getenv("UMICLUST_DEBUG") != nullptr;
+  static const bool debug = env_debug() != 0;
   auto clk = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tp0 = clk();
   const int T = K < 256 ? 1 : io_threads();
@@ -1184,7 +1181,7 @@ int32_t umiclust_params_from_argv(umiclust_params* p, int32_t argc, const char* 
   // always passes --threads n >= 25 (vsearch_umi_cluster.py:33-34,83-84; utils.py:56-63).  --threads 1 (or none) is
   // the sequential definition.  UMICLUST_O4=sequential forces the sequential definition whatever --threads says.
   p->policy_threads = p->threads > 1 ? 1 : 0;
-  if (const char* e = getenv("UMICLUST_O4")) {
+  if (const char* e = uc::env_o4()) {
     if (!strcmp(e, "sequential")) p->policy_threads = 0;
     else if (strcmp(e, "batched") != 0) return UMICLUST_EINVAL;
   }

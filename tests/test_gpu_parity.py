@@ -761,3 +761,40 @@ def test_file_path_releases_input_after_return(tmp_path):
             assert _read_dir(out) == _read_dir(ref)
         ctx.wait_host()
         ctx.wait_host()  # idempotent
+
+
+_RETIRED_ENV = {"RB_WPRIO": "1", "BAND_WPRIO": "1", "RB_PRIO": "1", "REC_DIRECT": "1", "PT_SIDE": "0", "LAZY": "0",
+                "REGROW_DEPTH": "1", "ARRANGE": "0", "RB_DIRECT": "0"}
+_SMOKE_CHILD = """
+import numpy as np
+import orc
+from umiclust import _lib, synth
+seqs = synth.make_umis(80, seed=4242, max_reads=1200, orient_mix=0.2).as_list()
+with _lib.Context(0) as ctx:
+    ctx.load(_lib.params(_lib.PRESET_ROUND1, 0.93, 58, 68), seqs)
+    ctx.cluster()
+    g = ctx.fetch()
+o = orc.cluster(orc.params(1, 0.93, 58, 68), seqs)
+assert g["n_clusters"] == o["n_clusters"] and np.array_equal(g["cluster"], o["cluster"])
+assert np.array_equal(g["strand"], o["strand"])
+assert g["consensus"] == o["consensus"]
+"""
+
+
+def test_retired_switches_warn_and_change_nothing():
+    """The nine switches retired after round 6, set to what were non-default values, are named once each by the
+    unknown-variable warning (printed once per process, hence the fresh child) and change nothing: the child clusters
+    the smoke input at block 256 (several passes, peers, a regrowth decision, round B) bit-identically to the oracle.
+    A kept switch (UMICLUST_BLOCK) is not warned about."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, UMICLUST_BLOCK="256",
+               PYTHONPATH=os.pathsep.join([os.path.join(root, "ont-tcrconsensus_amd"), os.path.join(root, "oracle")]))
+    env.update({"UMICLUST_" + k: v for k, v in _RETIRED_ENV.items()})
+    r = subprocess.run([sys.executable, "-c", _SMOKE_CHILD], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-4000:]
+    warned = [line for line in r.stderr.splitlines() if "unknown environment variable" in line]
+    for k in _RETIRED_ENV:
+        assert sum(f"UMICLUST_{k} " in line for line in warned) == 1, (k, warned)
+    assert not any("UMICLUST_BLOCK" in line for line in warned), warned
