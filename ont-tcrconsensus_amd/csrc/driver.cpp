@@ -52,6 +52,7 @@
 
 #include "../../include/umiclust.h"
 #include "host_io.h"
+#include "plan.h"
 #include "resolve.h"
 #include "tunables.h"
 #include "umiclust_internal.h"
@@ -120,7 +121,38 @@ struct PinBuf {
   }
 };
 
+// Policy constants of the host side, with what they were measured against (the block planner's are in plan.h)
 constexpr int32_t kDelta = 8192;  // centroids in the per-block delta tile before folding into base
+// passes in flight: 2; 3 (window of three blocks) hides more host time but its extra peers cost more than that
+// on configs 2/3/5 (profiles/r02/pipeline_depth_sweep.json)
+constexpr int32_t kDepth = 2;
+constexpr int32_t kBlockMin = 2048;  // the smallest default block (Tunables::block_div)
+// small blocks (deep clusters: config 5's ~2k-query blocks) write their outcomes and records straight into pinned host
+// memory: their copies are dispatch-bound (`profiles/r05/recdirect_small_ab/`: config 5 3.52 -> 3.64 M UMIs/s, config
+// 2's 8k-query blocks lose with it)
+constexpr int32_t kDirectRecQ = 4096;
+// speculative walk below this best k-mer count (20 and 30 equal, 45 slower: profiles/r03/spec_ab)
+constexpr int32_t kSpecThr = 30;
+// lazy peers below this new-centroid rate (per mille; higher rates lose: profiles/r02/lazy_peer_sweep.json)
+constexpr int32_t kLazyPermille = 5;
+constexpr int32_t kRbDirect = 4096;  // round B: at most this many pairs read / written in pinned memory
+
+// UMICLUST_DEBUG: what the per-bin summary reports, summed over the bin's passes
+struct DebugSums {
+  struct {  // resolve_pass phases and the pipeline's host side (s)
+    double wait = 0, hq_copy = 0, rec_copy = 0, classify = 0, inorder = 0, enqueue = 0, total = 0, appends = 0,
+           round_b = 0, resolve_block = 0;
+  } t;
+  struct {  // round B: device time between its first and last launch's events (s), round trips, launches, pairs
+    double dev_s = 0, trips = 0, launches = 0, pairs = 0;
+  } rb;
+  int64_t mispredicted = 0, saved = 0, blocked = 0;  // relevant peers predicted members that were not / were / undetermined
+  // queries without records / records with only earlier-block relevant peers / with an in-block relevant peer / host ns
+  // in pass 1
+  int64_t q_no_record = 0, q_earlier_only = 0, q_in_block = 0, q_host_ns = 0;
+  // strands on the inline path / with > kInlineRel relevant peers / reading their record / peers scanned there
+  int64_t s_inline = 0, s_many_relevant = 0, s_record_read = 0, s_peers_scanned = 0;
+};
 
 struct Tile {
   DevBuf<uint32_t> hist;      // [kBins], all zero between builds (the scan re-zeroes it)
@@ -341,12 +373,9 @@ struct umiclust_ctx {
   std::vector<uint8_t> cent_len;
   int32_t cnt_ge[kMaxLen + 1] = {};  // centroids of length >= L
   // two passes in flight (software pipeline over blocks) + round B on a side stream
-  Pass pass[kPeerTiles];          // passes in flight (`depth` of them, <= kPeerTiles)
+  Pass pass[kPeerTiles];          // passes in flight (kDepth of them, <= kPeerTiles)
   Tile blk_tile[kPeerTiles + 1], solo_tile;  // per-block peer tiles (ring of depth + 1), overflow re-runs
   Tile round_tile[2];             // O4 batched rounds: a pass's window from its first query's round start
-  // passes in flight: 2; 3 (window of three blocks) hides more host time but its extra peers cost more than that
-  // on configs 2/3/5 (profiles/r02/pipeline_depth_sweep.json)
-  static constexpr int32_t depth = 2;
   Tunables tun;                   // the UMICLUST_* switches, as umiclust_create read them (tunables.h)
   DevBuf<int32_t> d_seq2ord;      // [seqno - bin start] centroid ordinal or -1 (the merge's flagged hits)
   PinBuf<int32_t> h_seq2ord;
@@ -388,8 +417,7 @@ struct umiclust_ctx {
   PinBuf<uint8_t> h_cent_len;
   int32_t nclusters = 0;          // current bin
   // outputs of the current bin (output-cluster numbering)
-  std::vector<int32_t> rank_of;   // creation number -> output number
-  std::vector<int32_t> ostart, omemb;  // members per output cluster (centroid first)
+  ClusterNumbers num;             // creation -> output numbers, members per output cluster, clusters per bin (plan.h)
   std::vector<char> cons;
   std::vector<int64_t> cons_off;
   // per-bin results kept for umiclust_fetch_bin
@@ -401,31 +429,20 @@ struct umiclust_ctx {
   };
   std::vector<BinOut> bout;
   umiclust_stats stats{};
-  static constexpr int32_t block_min = 2048;  // the smallest default block (Tunables::block_div)
   // k_pack writes the outcomes and records straight into pinned host memory (true) or into device buffers copied by
   // DMA (false).  Set per clustering call: DMA with one context in the process (config 2: 4.33-4.36 vs 4.21-4.22 M
   // UMIs/s, the direct PCIe writes held k_pack at 133 us on the pass chain), direct with several (config 3, 8 lanes:
   // 7.56-7.60 vs 6.42-6.47 M: the lanes' copy dispatches contend for the hardware queues).
   bool rec_direct = false;
-  static constexpr int32_t kDirectRecQ = 4096;  // blocks of at most this many queries write their records directly
-  // speculative walk below this best k-mer count (20 and 30 equal, 45 slower: profiles/r03/spec_ab)
-  static constexpr int32_t spec_thr = 30;
-  // relevant peers certain to become members are not aligned speculatively (config 2 4.02 -> 4.14 M, round 4)
-  static constexpr bool peer_cert = true;
-  static constexpr int32_t regrow_depth = kPeerCap / 4;  // a block whose deepest peer list reaches this is not clean
   hipEvent_t pt_ev = nullptr;  // whole passes of single-bin loads: the next peer tile is built on st_b
   bool pt_pending = false;     // pt_ev recorded since the main stream last waited for it
   int32_t last_max_npeer = 0;
   DevBuf<uint32_t> d_probe;
-  // lazy peers below this new-centroid rate (per mille; higher rates lose: profiles/r02/lazy_peer_sweep.json)
-  static constexpr int32_t lazy_permille = 5;
-  static constexpr int32_t rb_direct = 4096;  // round B: at most this many pairs read / written in pinned memory
   int32_t o4_T = 0;               // policy O4 (umiclust_params.policy_threads): rounds of o4_T queries; 0 = sequential
   int32_t b_hint = 1 << 30;       // block size the last bin ended with (peer overflows halve it)
   int al_level = 0;                 // the alignment stream: 0 prioritised (al_priority), -1 plain (set_priority -1)
   int st_level = 0, prio_user = 0;  // the main stream's priority now / as umiclust_set_priority left it
-  int64_t dbg[4] = {0, 0, 0, 0};  // UMICLUST_DEBUG: mispredicted peers, saved peers, blocked, -
-  int64_t dbg_q[4] = {0, 0, 0, 0};
+  DebugSums dbg;
   int64_t n_resolved = 0;
   bool dump_want(int64_t k) const {  // UMICLUST_RESOLVE_DUMP's pass list
     const char* c = strchr(tun.resolve_dump, ':');
@@ -440,12 +457,6 @@ struct umiclust_ctx {
     return false;
   }
   std::vector<int16_t> wd;
-  double dbg_rb[4] = {};  // UMICLUST_DEBUG: round B device time (s), round trips, launches, pairs
-  double dbg_t[10] = {};  // UMICLUST_DEBUG: resolve_pass phases (s): event wait, outcome copy, record copy, classify,
-                          // in-order resolve, enqueue, total, appends, round B round trips, resolve_block
-  int64_t dbg_p[4] = {0, 0, 0, 0};  // UMICLUST_DEBUG: strands on the inline path / with > kInlineRel relevant
-                                    // peers / reading their record / peers scanned there  // UMICLUST_DEBUG: queries without records / records with only earlier-block
-                                    // relevant peers / with an in-block relevant peer / host ns in pass 1
   // traceback / consensus buffers, kept across calls (a bin set clusters hundreds of small bins)
   DevBuf<uint32_t> t_mpq, t_mpt, t_mout;
   PinBuf<uint32_t> h_mpq, h_mpt;     // the member pairs' pinned staging (traceback launch)
@@ -693,13 +704,6 @@ void ensure_pass_buffers(umiclust_ctx* c, Pass& P, int32_t B) {
   if (!P.ev_a) c->hip(hipEventCreate(&P.ev_a), "event");
 }
 
-// Enqueue the device pass of block [q0, q0+nq) against the index as it stands (centroids of the
-// blocks before the peer window), with no host synchronisation: the block's own peer tile (kept
-// for the next block's window), prefilter, the batch-of-8 walk over T_old (up to 4 align rounds),
-// the speculative alignment of every (query, earlier window query) pair passing the k-mer
-// threshold, and one download of the walk states, top lists, walked results and peer results.
-// The peer window is [prev->base, q0+nq) with prev = the previous block's tile, or the block
-// alone (prev == nullptr).
 // the longest / shortest query of a block (sorted within a bin, but a pack's lengths restart at every bin)
 int32_t block_maxlen(const umiclust_ctx* c, int32_t q0, int32_t nq) {
   int32_t m = 0;
@@ -712,12 +716,69 @@ int32_t block_minlen(const umiclust_ctx* c, int32_t q0, int32_t nq) {
   return m;
 }
 
-// the packs' bin bounds of the prefilter (PrefilterArgs::qbin) and the centroid length table
-void set_bins(umiclust_ctx* c, PrefilterArgs& a) {
+// ---- what enqueue_pass and enqueue_count share of a prefilter launch ----
+// Stream st waits for the side stream's index appends and peer-tile builds.
+void wait_index_and_tiles(umiclust_ctx* c, hipStream_t st) {
+  if (c->ix_st && c->ix_done) c->hip(hipStreamWaitEvent(st, c->ix_done, 0), "wait");  // index / peer tiles
+  if (c->pt_pending) {  // whole passes: the peer tiles built ahead on the side stream (ClusterRun::run_whole)
+    c->hip(hipStreamWaitEvent(st, c->pt_ev, 0), "wait");
+    c->pt_pending = false;
+  }
+}
+
+// The index's tile views (sealed tiles, then base and current delta: segment order) in the pinned array h, uploaded
+// to its device mirror d on st when they are too many for the kernel arguments.  Returns their number.
+int32_t stage_tile_views(umiclust_ctx* c, PinBuf<TileView>& h, DevBuf<TileView>& d, hipStream_t st) {
+  int32_t nv = 0;
+  const size_t need = c->tiles.size() + 2;
+  if (need > h.n) {
+    c->hip(hipStreamSynchronize(st), "sync");  // rare: the views array grows
+    c->hip(h.ensure(need * 2), "pin");
+    c->hip(d.ensure(need * 2), "alloc");
+  }
+  for (Tile* t : c->tiles)
+    if (t->n > 0) h.p[nv++] = view_of(*t);
+  if (c->base_tile.n > 0) h.p[nv++] = view_of(c->base_tile);
+  if (c->delta_tile[c->delta_cur].n > 0) h.p[nv++] = view_of(c->delta_tile[c->delta_cur]);
+  if (nv > kArgTiles)
+    c->hip(hipMemcpyAsync(d.p, h.p, (size_t)nv * sizeof(TileView), hipMemcpyHostToDevice, st), "tiles");
+  return nv;
+}
+
+// The arguments that do not depend on the peer window: the sequences, the index as it stands (nv staged views), the
+// block, the pass's per-part buffers, the packs' bin bounds (PrefilterArgs::qbin) and the centroid length table.
+PrefilterArgs prefilter_args(umiclust_ctx* c, const Pass& P, const TileView* views, const TileView* dviews, int32_t nv,
+                             int32_t q0, int32_t nq) {
+  PrefilterArgs a{};
+  for (int32_t i = 0; i < nv && nv <= kArgTiles; i++) a.tv[i] = views[i];
+  a.seqs = dev_seqs(c);
+  a.arena = c->arena.p;
+  a.tiles = dviews;
+  a.ntiles = nv;
+  a.ncent = c->index_end;
+  a.nseg = (c->index_end + kSegCentroids - 1) / kSegCentroids;
+  a.cent_seqno = c->d_cent.p;
+  for (int L = 0; L <= kMaxLen; L++) a.cnt_ge[L] = c->cnt_ge[L];
+  a.q0 = q0;
+  a.nq = nq;
+  a.both = c->both;
+  a.minwordmatches = c->p.minwordmatches;
+  a.seq2ord = c->d_seq2ord.p - c->bin_s[c->cur_bin];
+  a.pcand = P.d_pcand.p;
+  a.pncand = P.d_pncand.p;
+  a.units = P.d_units.p;
+  a.nunits = P.d_anunits.p;
+  a.ppeer_id = P.d_ppeer_id.p;
+  a.ppeer_count = P.d_ppeer_count.p;
+  a.pnpeer = P.d_pnpeer.p;
+  a.ppost = P.d_ppost.p;
+  a.pf1_lds = c->tun.pf1_lds;
+  a.prof = c->pf_prof.p;  // null unless UMICLUST_PFPROF is set
   a.qbin = c->pack_on ? c->d_qbin.p : nullptr;
   a.bin_seq0 = c->d_bin_seq0.p;
   a.bin_ord0 = c->d_bin_ord0.p;
   a.cent_len = c->d_cent_len.p;
+  return a;
 }
 
 // UMICLUST_PFPROBE=1 (measurement only): after every counting launch, the same launch without its count loop
@@ -744,17 +805,20 @@ void launch_pf_probe(umiclust_ctx* c, const PrefilterArgs& a, hipStream_t st) {
   c->hip(launch_prefilter(b, st, 3), "prefilter probe");
 }
 
+// Enqueue the device pass of block [q0, q0+nq) against the index as it stands (centroids of the
+// blocks before the peer window), with no host synchronisation: the block's own peer tile (kept
+// for the next block's window), prefilter, the batch-of-8 walk over T_old (up to 4 align rounds),
+// the speculative alignment of every (query, earlier window query) pair passing the k-mer
+// threshold, and one download of the walk states, top lists, walked results and peer results.
+// The peer window is [prev->base, q0+nq) with prev = the previous block's tile, or the block
+// alone (prev == nullptr).
 void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* const* prevs, int nprev, Tile& own,
                   int32_t region, bool lazy_peers = false, bool after_count = false) {
   const int32_t w0 = nprev > 0 ? prevs[0]->base : q0;
   const int both = c->both;
   const int32_t nqs = nq * both;
   hipStream_t st = c->st;
-  if (c->ix_st && c->ix_done) c->hip(hipStreamWaitEvent(st, c->ix_done, 0), "wait");  // index / peer tiles
-  if (c->pt_pending) {  // whole passes: the peer tiles built ahead on the side stream (cluster_all)
-    c->hip(hipStreamWaitEvent(st, c->pt_ev, 0), "wait");
-    c->pt_pending = false;
-  }
+  wait_index_and_tiles(c, st);
   P.q0 = q0;
   P.nq = nq;
   P.w0 = w0;
@@ -773,33 +837,13 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
     st = c->st_al;
     if (c->ix_done) c->hip(hipStreamWaitEvent(st, c->ix_done, 0), "wait");
   }
-  int32_t nv = 0;
-  const size_t need = c->tiles.size() + 2;
-  if (need > P.h_tiles.n) {
-    c->hip(hipStreamSynchronize(st), "sync");  // rare: the views array grows
-    c->hip(P.h_tiles.ensure(need * 2), "pin");
-    c->hip(P.d_tiles.ensure(need * 2), "alloc");
-  }
-  for (Tile* t : c->tiles)
-    if (t->n > 0) P.h_tiles.p[nv++] = view_of(*t);
-  if (c->base_tile.n > 0) P.h_tiles.p[nv++] = view_of(c->base_tile);
-  if (c->delta_tile[c->delta_cur].n > 0) P.h_tiles.p[nv++] = view_of(c->delta_tile[c->delta_cur]);
-  if (nv > kArgTiles)
-    c->hip(hipMemcpyAsync(P.d_tiles.p, P.h_tiles.p, (size_t)nv * sizeof(TileView), hipMemcpyHostToDevice, st),
-           "tiles");
+  const int32_t nv = stage_tile_views(c, P.h_tiles, P.d_tiles, st);
   // the counters are zero unless this buffer set's last pass launched no k_pack (which re-zeroes them at its end)
   if (!P.ctr_zeroed) c->hip(hipMemsetAsync(P.d_counters.p, 0, kCountersLen * 4, st), "memset");
   P.ctr_zeroed = false;
-  PrefilterArgs a{};
-  for (int32_t i = 0; i < nv && nv <= kArgTiles; i++) a.tv[i] = P.h_tiles.p[i];
-  a.seqs = dev_seqs(c);
-  a.arena = c->arena.p;
-  a.tiles = P.d_tiles.p;
-  a.ntiles = nv;
+  PrefilterArgs a = prefilter_args(c, P, P.h_tiles.p, P.d_tiles.p, nv, q0, nq);
   // centroid tiles are in segment order (sealed tiles, then base and delta); each pass addresses its
   // postings from the lowest arena slot it reads
-  a.ncent = c->index_end;
-  a.nseg = (c->index_end + kSegCentroids - 1) / kSegCentroids;
   if (a.nseg > kMaxSegs) c->fail(UMICLUST_ERANGE, "more than %d centroids in one bin", kMaxSegs * kSegCentroids);
   for (int s = 0, vi = 0; s <= a.nseg; s++) {
     while (vi < nv && P.h_tiles.p[vi].seg < s) vi++;
@@ -815,12 +859,6 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
       a.seg_base[s] = lo;
     }
   }
-  a.cent_seqno = c->d_cent.p;
-  for (int L = 0; L <= kMaxLen; L++) a.cnt_ge[L] = c->cnt_ge[L];
-  a.q0 = q0;
-  a.nq = nq;
-  a.both = both;
-  a.minwordmatches = c->p.minwordmatches;
   // peer slots oldest first, the own tile last; missing earlier blocks leave n = 0 slots in front
   for (int i = 0; i < kPeerTiles - 1; i++) {
     const int j = i - (kPeerTiles - 1 - nprev);
@@ -828,15 +866,10 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   }
   a.peer[kPeerTiles - 1] = view_of(own);
   a.peer_base = w0;
-  a.pcand = P.d_pcand.p;
-  a.pncand = P.d_pncand.p;
-  a.units = P.d_units.p;
-  a.nunits = P.d_anunits.p;
   a.flag_tile = -1;
   a.cand_base = w0;
   a.peer_shift = 0;
   a.peer_id_add = 0;
-  a.seq2ord = c->d_seq2ord.p - c->bin_s[c->cur_bin];
   if (second_half) {
     // the counting half ran with the window one block wider (oldest first): its peer ids are relative to
     // that window's start
@@ -847,11 +880,6 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   // list table of the lean kernel: every k-mer of the block's length in every tile it reads
   a.nlist_cap = std::min(kMaxKmers * 12, std::max(1, block_maxlen(c, q0, nq) - 7) *
                                               ((a.nseg > 0 ? a.seg_tile[1] - a.seg_tile[0] : 0) + kPeerTiles));
-  a.pf1_lds = c->tun.pf1_lds;
-  a.ppeer_id = P.d_ppeer_id.p;
-  a.ppeer_count = P.d_ppeer_count.p;
-  a.pnpeer = P.d_pnpeer.p;
-  a.ppost = P.d_ppost.p;
   a.top_seqno = P.d_top_seqno.p;
   a.top_count = P.d_top_count.p;
   a.ntop = P.d_ntop.p;
@@ -859,8 +887,6 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   a.peer_count = P.d_peer_count.p;
   a.npeer = P.d_npeer.p;
   a.postings_touched = P.d_counters.p;
-  a.prof = c->pf_prof.p;  // null unless UMICLUST_PFPROF is set
-  set_bins(c, a);
   if (second_half) c->hip(hipStreamWaitEvent(st, c->a_ev[P.a_slot][1], 0), "wait");
   c->hip(hipEventRecord(P.ev[0], st), "event");
   P.c_timed = false;
@@ -915,7 +941,7 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
                             cnt + i, P.d_outidx.p + sg.base[i], c->sc, P.d_res.p, st, c->tun.band_pairs),
                what);
   };
-  c->hip(launch_walk(-1, q0, nqs, both, c->spec_thr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p, P.d_res.p,
+  c->hip(launch_walk(-1, q0, nqs, both, kSpecThr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p, P.d_res.p,
                      c->d_acc.p, c->d_rank.p, P.d_ws.p, P.d_pq.p, P.d_pt.p, P.d_outidx.p, sg0, segc, cells_w, st),
          "walk");
   c->hip(hipEventRecord(P.ev[2], st), "event");
@@ -925,16 +951,16 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   const uint32_t peer_out0 = (uint32_t)nqs * kWalk;
   // small passes (deep clusters cut blocks small) spread every pair over a lane group
   align_round(sg0, kWalk, segc, "align 0");
-  c->hip(launch_walk(0, q0, nqs, both, c->spec_thr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p,
+  c->hip(launch_walk(0, q0, nqs, both, kSpecThr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p,
                      P.d_res.p, c->d_acc.p, c->d_rank.p, P.d_ws.p, P.d_pq.p, P.d_pt.p, P.d_outidx.p, sg1, segc + kSegLens,
                      cells_w, st),
          "walk 0");
   // the previous block's pass (its walk states are final and stay until that buffer set's next walk, which is
   // queued after this one on the align stream): peers there whose device walk accepted are certain members
+  // (relevant peers certain to become members are not aligned speculatively: config 2 4.02 -> 4.14 M, round 4)
   const Pass* prev = nullptr;
-  if (c->peer_cert)
-    for (const Pass& Q : c->pass)
-      if (&Q != &P && Q.nq > 0 && Q.q0 + Q.nq == q0) prev = &Q;
+  for (const Pass& Q : c->pass)
+    if (&Q != &P && Q.nq > 0 && Q.q0 + Q.nq == q0) prev = &Q;
   c->hip(launch_peer_pairs(q0, w0, nqs, both, c->d_lens.p, P.d_ws.p, P.d_peer_id.p, P.d_peer_count.p, P.d_npeer.p,
                            P.d_pq.p, P.d_pt.p, P.d_outidx.p, sg1, segc + kSegLens, cells_p, P.d_counters.p + 8,
                            peer_out0, P.d_paligned.p, lazy_peers ? 0 : 1,
@@ -942,16 +968,15 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
                            prev ? prev->nq : 0, st),
          "peer pairs");
   align_round(sg1, kWalk + kPeerCap, segc + kSegLens, "align 1");
-  c->hip(launch_walk(1, q0, nqs, both, c->spec_thr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p,
+  c->hip(launch_walk(1, q0, nqs, both, kSpecThr, P.d_top_seqno.p, P.d_top_count.p, P.d_ntop.p, c->d_lens.p,
                      P.d_res.p, c->d_acc.p, c->d_rank.p, P.d_ws.p, P.d_pq.p, P.d_pt.p, P.d_outidx.p, sg1,
                      segc + 2 * kSegLens, cells_w, st),
          "walk 1");
   c->hip(hipEventRecord(P.ev[3], st), "event");
   // what the host needs goes straight to pinned host memory; the pass that next reuses these
   // buffers is enqueued only after the host has waited for ev[4]
-  // small blocks (deep clusters: config 5's ~2k-query blocks) write directly too: their copies are dispatch-bound
-  // (`profiles/r05/recdirect_small_ab/`: config 5 3.52 -> 3.64 M UMIs/s, config 2's 8k-query blocks lose with it)
-  P.rec_direct = c->rec_direct || nq <= umiclust_ctx::kDirectRecQ;
+  // blocks of at most kDirectRecQ queries write directly too
+  P.rec_direct = c->rec_direct || nq <= kDirectRecQ;
   // rec_direct: k_pack writes the outcomes and records straight into the pinned host buffers (no DMA copies on the
   // chain the host waits for: a 3 MB record copy was 0.14 ms per config-2 block); otherwise device buffers + copies
   c->hip(launch_pack(nqs, w0, c->d_lens.p, P.d_ws.p, P.d_ntop.p, P.d_top_seqno.p, P.d_top_count.p, P.d_res.p,
@@ -984,69 +1009,27 @@ void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile*
   // on its own stream, gated by the main stream's work so far (index append, peer tiles, this buffer set's
   // last merge): the main stream's next append and second half do not queue behind it
   hipStream_t st = c->st;
-  if (c->ix_st && c->ix_done) c->hip(hipStreamWaitEvent(st, c->ix_done, 0), "wait");  // index / peer tiles
-  if (c->pt_pending) {  // whole passes: the peer tiles built ahead on the side stream (cluster_all)
-    c->hip(hipStreamWaitEvent(st, c->pt_ev, 0), "wait");
-    c->pt_pending = false;
-  }
+  wait_index_and_tiles(c, st);
   // this buffer set's last second half (full kernel + merge on the align stream) has read what
   // the counting half overwrites
   if (c->ix_st) c->hip(hipStreamWaitEvent(st, P.ev[1], 0), "wait");
   c->hip(hipEventSynchronize(P.ev_a), "sync");  // the last upload from h_tiles_a is done
-  int32_t nv = 0;
-  const size_t need = c->tiles.size() + 2;
-  if (need > P.h_tiles_a.n) {
-    c->hip(hipStreamSynchronize(st), "sync");  // rare: the views array grows
-    c->hip(P.h_tiles_a.ensure(need * 2), "pin");
-    c->hip(P.d_tiles_a.ensure(need * 2), "alloc");
-  }
-  for (Tile* t : c->tiles)
-    if (t->n > 0) P.h_tiles_a.p[nv++] = view_of(*t);
-  if (c->base_tile.n > 0) P.h_tiles_a.p[nv++] = view_of(c->base_tile);
-  if (c->delta_tile[c->delta_cur].n > 0) P.h_tiles_a.p[nv++] = view_of(c->delta_tile[c->delta_cur]);
-  if (nv > kArgTiles)
-    c->hip(hipMemcpyAsync(P.d_tiles_a.p, P.h_tiles_a.p, (size_t)nv * sizeof(TileView), hipMemcpyHostToDevice, st),
-           "tiles");
+  const int32_t nv = stage_tile_views(c, P.h_tiles_a, P.d_tiles_a, st);
   c->hip(hipEventRecord(P.ev_a, st), "event");
-  PrefilterArgs a{};
-  for (int32_t i = 0; i < nv && nv <= kArgTiles; i++) a.tv[i] = P.h_tiles_a.p[i];
-  a.seqs = dev_seqs(c);
-  a.arena = c->arena.p;
-  a.tiles = P.d_tiles_a.p;
-  a.ntiles = nv;
-  a.ncent = c->index_end;
-  a.nseg = nseg;
+  PrefilterArgs a = prefilter_args(c, P, P.h_tiles_a.p, P.d_tiles_a.p, nv, q0, nq);
   a.seg_tile[0] = 0;
   a.seg_tile[1] = nv;
   uint64_t lo = UINT64_MAX;
   for (int i = 0; i < nwin; i++) lo = std::min(lo, wins[i]->post_base);
   for (int v = 0; v < nv; v++) lo = std::min(lo, P.h_tiles_a.p[v].post_base);
   a.seg_base[0] = lo;
-  a.cent_seqno = c->d_cent.p;
-  for (int L = 0; L <= kMaxLen; L++) a.cnt_ge[L] = c->cnt_ge[L];
-  a.q0 = q0;
-  a.nq = nq;
-  a.both = c->both;
-  a.minwordmatches = c->p.minwordmatches;
   for (int i = 0; i < kPeerTiles; i++) {
     const int j = i - (kPeerTiles - nwin);
     a.peer[i] = j >= 0 ? view_of(*wins[j]) : TileView{};
   }
   a.flag_tile = flag >= 0 ? (kPeerTiles - nwin) + flag : -1;
   a.peer_base = a.cand_base = wins[0]->base;
-  a.seq2ord = c->d_seq2ord.p - c->bin_s[c->cur_bin];
-  a.pcand = P.d_pcand.p;
-  a.pncand = P.d_pncand.p;
-  a.units = P.d_units.p;
-  a.nunits = P.d_anunits.p;
   a.nlist_cap = std::min(kMaxKmers * 12, std::max(1, block_maxlen(c, q0, nq) - 7) * (nv + kPeerTiles));
-  a.pf1_lds = c->tun.pf1_lds;
-  a.ppeer_id = P.d_ppeer_id.p;
-  a.ppeer_count = P.d_ppeer_count.p;
-  a.pnpeer = P.d_pnpeer.p;
-  a.ppost = P.d_ppost.p;
-  a.prof = c->pf_prof.p;  // null unless UMICLUST_PFPROF is set
-  set_bins(c, a);
   c->hip(hipEventRecord(c->a_ev[slot][0], st), "event");
   c->hip(launch_prefilter(a, st, 1), "prefilter (count)");
   c->hip(hipEventRecord(c->a_ev[slot][1], st), "event");
@@ -1116,8 +1099,8 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
   const double tsync0 = now_s();
   c->hip(hipEventSynchronize(P.ev[4]), "sync");
   c->stats.t_sync_s += now_s() - tsync0;
-  c->dbg_t[0] += now_s() - tsync0;
-  struct DAcc { double* p; double t0; ~DAcc() { *p += now_s() - t0; } } dtot{&c->dbg_t[6], tsync0};
+  c->dbg.t.wait += now_s() - tsync0;
+  struct DAcc { double* p; double t0; ~DAcc() { *p += now_s() - t0; } } dtot{&c->dbg.t.total, tsync0};
   P.live = false;
   float ms = 0;
   c->hip(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]), "elapsed");
@@ -1166,7 +1149,7 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
     c->last_max_npeer = (int32_t)mx;
   }
   c->stats.t_sync_s += now_s() - tc0;
-  c->dbg_t[1] += now_s() - tc0;
+  c->dbg.t.hq_copy += now_s() - tc0;
   const HostQs* hq = P.hq_copy.data();
   if (!c->pool) c->pool.reset(new WorkPool(pool_threads(c)));
   // the records are copied into pageable memory first (one streaming read; scattered reads of the DMA'd
@@ -1188,7 +1171,7 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
     }
     recs = P.rec_copy.data();
     c->stats.t_sync_s += now_s() - tc1;
-    c->dbg_t[2] += now_s() - tc1;
+    c->dbg.t.rec_copy += now_s() - tc1;
   }
   ResolveEnv env;
   env.hlen = c->hlen.data();
@@ -1224,7 +1207,7 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
     // small rounds (the usual: tens of pairs) read their pairs from and write their scores to the pinned buffers
     // directly: one dispatch per query length and no copies on the host's critical path (two uploads and a download
     // were ~70 us of dispatch latency per block with deferred queries); large ones go through device buffers
-    const bool direct = nb <= c->rb_direct;
+    const bool direct = nb <= kRbDirect;
     const uint32_t *pq = c->h_bpq.p, *pt = c->h_bpt.p;
     uint32_t* pres = c->h_bres.p;
     if (!direct) {
@@ -1257,10 +1240,10 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
     float bms = 0;
     c->hip(hipEventElapsedTime(&bms, c->evb[0], c->evb[1]), "elapsed");
     t_al += bms * 1e-3;
-    c->dbg_rb[0] += bms * 1e-3;
-    c->dbg_rb[1] += 1;
-    c->dbg_rb[2] += nl;
-    c->dbg_rb[3] += nb;
+    c->dbg.rb.dev_s += bms * 1e-3;
+    c->dbg.rb.trips += 1;
+    c->dbg.rb.launches += nl;
+    c->dbg.rb.pairs += nb;
   };
   // UMICLUST_RESOLVE_DUMP: the pass's inputs, round-B pairs / results and outputs, for the host-only replay
   // (tools/resolve_tsan_main.cpp: the ThreadSanitizer harness of the CPU suite)
@@ -1305,10 +1288,10 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
             1e3 * rs.t_inorder_s, 1e3 * rs.t_round_b_s, (long long)rs.pairs_round_b, (long long)rs.n_merged_walks,
             (long long)rs.n_deferred, 1e3 * (now_s() - tsync0));
   c->stats.t_host_pass1_s += rs.t_classify_s + rs.t_inorder_s;
-  c->dbg_t[3] += rs.t_classify_s;
-  c->dbg_t[4] += rs.t_inorder_s;
-  c->dbg_t[8] += rs.t_round_b_s;
-  c->dbg_t[9] += th;
+  c->dbg.t.classify += rs.t_classify_s;
+  c->dbg.t.inorder += rs.t_inorder_s;
+  c->dbg.t.round_b += rs.t_round_b_s;
+  c->dbg.t.resolve_block += th;
   c->stats.n_alignments += rs.n_alignments;
   c->stats.cells += rs.cells;
   c->stats.n_merged_walks += rs.n_merged_walks;
@@ -1316,11 +1299,11 @@ bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<
   c->stats.n_deferred += rs.n_deferred;
   c->stats.pairs_round_b += rs.pairs_round_b;
   c->stats.cells_computed += rs.cells_round_b;
-  for (int i = 0; i < 4; i++) {
-    c->dbg[i] += rs.dbg[i];
-    c->dbg_p[i] += rs.dbg_p[i];
-    c->dbg_q[i] += rs.dbg_q[i];
-  }
+  DebugSums& d = c->dbg;  // (ResolveStats keeps arrays: resolve.cpp indexes them by the class it computes)
+  d.mispredicted += rs.dbg[0], d.saved += rs.dbg[1], d.blocked += rs.dbg[2];
+  d.q_no_record += rs.dbg_q[0], d.q_earlier_only += rs.dbg_q[1], d.q_in_block += rs.dbg_q[2], d.q_host_ns += rs.dbg_q[3];
+  d.s_inline += rs.dbg_p[0], d.s_many_relevant += rs.dbg_p[1], d.s_record_read += rs.dbg_p[2];
+  d.s_peers_scanned += rs.dbg_p[3];
   if (resolved) *resolved = nq;
   return !partial;
 }
@@ -1418,10 +1401,6 @@ void append_centroids(umiclust_ctx* c, const std::vector<int32_t>& new_cents) {
   }
 }
 
-// Cluster bin `bin` -- or, npk > 1, the pack of bins [bin, bin + npk) in one greedy order (each bin's queries in
-// its own sorted order, the bins one after another: bins never interact, so this is every bin's own vsearch run):
-// blocks then span bin boundaries and small bins share passes; the prefilter keeps only a query's own bin
-// (PrefilterArgs::qbin) and the results are split per bin.
 // The main (counting) stream re-created at the greatest priority (level 1) or as a plain stream (0), after its queued
 // work; no other handle of it is kept (ix_st is st_b or null, events recorded on it have completed).
 hipError_t main_stream_priority(umiclust_ctx* c, int level) {
@@ -1439,63 +1418,101 @@ hipError_t main_stream_priority(umiclust_ctx* c, int level) {
   return hipSuccess;
 }
 
-void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t npk = 1) {
-  c->rec_direct = g_live_ctx.load() > 1;
+// One cluster_all call: what its steps share (per call, not part of the context).  Seqnos stay absolute everywhere.
+struct ClusterRun {
+  umiclust_ctx* const c;
+  const int32_t bin, npk;  // the bins [bin, bin + npk)
+  const bool multi_bin;
   const double t0 = now_s();
-  if (bin < 0 || npk < 1 || bin + npk >= (int32_t)c->bin_s.size())
-    c->fail(UMICLUST_EINVAL, "bins [%d, %d) out of range", bin, bin + npk);
-  c->pack_on = npk > 1;
-  // one bin (or pack) = the sorted seqnos [s0, s1); seqnos stay absolute everywhere
-  const int32_t s0 = c->bin_s[bin], s1 = c->bin_s[bin + npk];
-  const int32_t n = s1 - s0;
-  c->cur_bin = bin;
-  std::fill(c->cno.begin() + s0, c->cno.begin() + s1, -1);
-  std::fill(c->strand.begin() + s0, c->strand.begin() + s1, 0);
-  std::fill(c->target.begin() + s0, c->target.begin() + s1, -1);
-  c->cent.clear();
-  c->cent.reserve((size_t)n + 1);
-  c->cent_len.clear();
-  std::fill(c->cnt_ge, c->cnt_ge + kMaxLen + 1, 0);
-  c->cent_len.reserve((size_t)n + 1);
-  c->nclusters = 0;
-  c->hip(hipStreamSynchronize(c->st), "sync");  // no queued work may still read the old tiles
-  for (Tile* t : c->tiles) delete t;
-  c->tiles.clear();
-  c->base_tile.n = c->delta_tile[0].n = c->delta_tile[1].n = 0;
-  c->last_a_slot = -1;
-  c->sealed_end = c->base_end = 0;
-  c->index_end = 0;
-  c->nix = 0;
-  c->stats = umiclust_stats{};
-  c->stats.n_input = c->bin_in[bin + npk] - c->bin_in[bin];
-  if (c->pack_on) {
-    for (int32_t b = bin; b < bin + npk; b++) c->h_bin_ord0.p[b] = INT32_MAX;  // no centroid of the bin indexed yet
-    c->hip(hipMemcpyAsync(c->d_bin_ord0.p + bin, c->h_bin_ord0.p + bin, (size_t)npk * 4, hipMemcpyHostToDevice, c->st),
-           "h2d bin ord0");
+  const int32_t s0, s1, n;  // one bin (or pack) = the sorted seqnos [s0, s1)
+  std::vector<uint8_t> state_buf;
+  StateView state;
+  BlockPlan plan;
+  std::vector<int32_t> pending;    // O4: resolved centroids the index does not hold yet (sync_index)
+  std::vector<int32_t> new_cents;  // the centroids of the block resolved last
+  // Lazy peers: once new centroids have become rare (the last resolved block created fewer than kLazyPermille per
+  // mille), in-window peers are not aligned speculatively; a query whose relevant peer turns out to be a centroid is
+  // deferred and round B aligns what it needs (deep clusters: config 5)
+  bool lazy = false;
+  double t_pf = 0, t_al = 0, t_host = 0, t_cons = 0;
+  int32_t tw_n = 0;            // member pairs handed to the traceback so far (tw_launch)
+  int32_t tw_maxl = kMaxLen;   // the bin's longest sequence
+  DevSeqs ds{};
+  const int32_t T4;  // policy O4: queries per round (0: sequential)
+  const int D;       // passes in flight
+
+  ClusterRun(umiclust_ctx* ctx, int32_t bin_, int32_t npk_, bool multi)
+      : c(ctx), bin(bin_), npk(npk_), multi_bin(multi), s0(ctx->bin_s[bin_]), s1(ctx->bin_s[bin_ + npk_]), n(s1 - s0),
+        T4(ctx->o4_T), D(T4 ? 2 : kDepth) {}
+
+  // ---- step 1: a clean slate for the bin
+  void reset_bin() {
+    c->pack_on = npk > 1;
+    c->cur_bin = bin;
+    std::fill(c->cno.begin() + s0, c->cno.begin() + s1, -1);
+    std::fill(c->strand.begin() + s0, c->strand.begin() + s1, 0);
+    std::fill(c->target.begin() + s0, c->target.begin() + s1, -1);
+    c->cent.clear();
+    c->cent.reserve((size_t)n + 1);
+    c->cent_len.clear();
+    std::fill(c->cnt_ge, c->cnt_ge + kMaxLen + 1, 0);
+    c->cent_len.reserve((size_t)n + 1);
+    c->nclusters = 0;
+    c->hip(hipStreamSynchronize(c->st), "sync");  // no queued work may still read the old tiles
+    for (Tile* t : c->tiles) delete t;
+    c->tiles.clear();
+    c->base_tile.n = c->delta_tile[0].n = c->delta_tile[1].n = 0;
+    c->last_a_slot = -1;
+    c->sealed_end = c->base_end = 0;
+    c->index_end = 0;
+    c->nix = 0;
+    c->stats = umiclust_stats{};
+    c->stats.n_input = c->bin_in[bin + npk] - c->bin_in[bin];
+    if (c->pack_on) {
+      for (int32_t b = bin; b < bin + npk; b++) c->h_bin_ord0.p[b] = INT32_MAX;  // no centroid of the bin indexed yet
+      c->hip(hipMemcpyAsync(c->d_bin_ord0.p + bin, c->h_bin_ord0.p + bin, (size_t)npk * 4, hipMemcpyHostToDevice, c->st),
+             "h2d bin ord0");
+    }
+    c->stats.n_kept = n;
+    c->hip(c->d_cent.ensure((size_t)n + 1), "alloc cent");
+    c->hip(c->d_cent_len.ensure((size_t)n + 1), "alloc cent");
+    c->hip(c->h_cent.ensure((size_t)n + 1), "pin cent");
+    c->hip(c->h_cent_len.ensure((size_t)n + 1), "pin cent");
+    c->hip(c->d_seq2ord.ensure((size_t)n + 1), "alloc seq2ord");
+    c->hip(c->h_seq2ord.ensure((size_t)n + 1), "pin seq2ord");
+    std::fill(c->h_seq2ord.p, c->h_seq2ord.p + n, -1);
+    c->hip(hipMemsetAsync(c->d_seq2ord.p, 0xff, (size_t)n * 4, c->st), "memset");
+    state_buf.assign((size_t)n, ST_UNDET);
+    state = StateView{state_buf.data(), s0};
+    if (c->tun.walk_dump) c->wd.assign((size_t)n * 4, -1);
   }
-  c->stats.n_kept = n;
-  c->hip(c->d_cent.ensure((size_t)n + 1), "alloc cent");
-  c->hip(c->d_cent_len.ensure((size_t)n + 1), "alloc cent");
-  c->hip(c->h_cent.ensure((size_t)n + 1), "pin cent");
-  c->hip(c->h_cent_len.ensure((size_t)n + 1), "pin cent");
-  c->hip(c->d_seq2ord.ensure((size_t)n + 1), "alloc seq2ord");
-  c->hip(c->h_seq2ord.ensure((size_t)n + 1), "pin seq2ord");
-  std::fill(c->h_seq2ord.p, c->h_seq2ord.p + n, -1);
-  c->hip(hipMemsetAsync(c->d_seq2ord.p, 0xff, (size_t)n * 4, c->st), "memset");
-  std::vector<uint8_t> state_buf((size_t)n, ST_UNDET);
-  StateView state{state_buf.data(), s0};
-  if (c->tun.walk_dump) c->wd.assign((size_t)n * 4, -1);
-  double t_pf = 0, t_al = 0, t_host = 0;
-  // blocks of at most B queries of one length (the aligner is compiled per query length); a block's
-  // peer tile fills one kPeerRegion of the prefilter counters, so B <= kMaxBlock
-  int32_t B = std::max(1, std::min<int32_t>(c->tun.block_size, kMaxBlock));
-  if (c->tun.block_div > 0) B = std::min<int32_t>(B, std::max<int32_t>(c->block_min, ((s1 - s0) / c->tun.block_div + 255) & ~255));
-  c->pass_B = B;
-  for (Pass& P : c->pass) ensure_pass_buffers(c, P, B);
+
+  // the block size and the pass buffers for it, then the bin's blocks
+  void plan_blocks() {
+    // blocks of at most B queries of one length (the aligner is compiled per query length); a block's
+    // peer tile fills one kPeerRegion of the prefilter counters, so B <= kMaxBlock
+    int32_t B = std::max(1, std::min<int32_t>(c->tun.block_size, kMaxBlock));
+    if (c->tun.block_div > 0) B = std::min<int32_t>(B, std::max<int32_t>(kBlockMin, ((s1 - s0) / c->tun.block_div + 255) & ~255));
+    c->pass_B = B;
+    for (Pass& P : c->pass) ensure_pass_buffers(c, P, B);
+    plan.hlen = c->hlen.data();
+    plan.s0 = s0;
+    plan.s1 = s1;
+    plan.B = B;
+    // blocks across length changes: bins below the full block size (config 3: 4.15 vs 3.61 M UMIs/s; a 2M-read bin
+    // gains nothing, its length runs are many blocks long: profiles/r03/mixlen_ab.json)
+    plan.mix = c->tun.mix_len > 0 || (c->tun.mix_len < 0 && (B < kMaxBlock || c->pack_on));
+    plan.o4_T = T4;
+    plan.hqbin = c->pack_on ? c->hqbin.data() : nullptr;
+    plan.bin_s = c->bin_s.data();
+    plan.regrow = c->tun.regrow;
+    plan.start(c->b_hint);
+  }
+
   // postings arena: the base, delta, peer-ring and solo slots, then the sealed tile slots in creation
   // order (n / kTile of them at most); a prefilter pass reads the slots of one counter segment (plus
   // the unsealed ones in its last pass), which keeps its 32-bit buffer offsets in range
-  {
+  void layout_arena() {
     uint64_t off = 0;
     auto slot = [&](Tile& t, int64_t nseq) {
       t.post_base = off;
@@ -1507,46 +1524,28 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
     slot(c->delta_tile[1], kDelta);
     for (Tile& t : c->blk_tile) slot(t, kMaxBlock);
     slot(c->solo_tile, kMaxBlock);
-    if (c->o4_T)
-      for (Tile& t : c->round_tile) slot(t, c->o4_T);
+    if (T4)
+      for (Tile& t : c->round_tile) slot(t, T4);
     c->sealed_slot0 = off;
     off += (uint64_t)(n / kTile) * tile_cap(kTile);
     c->hip(c->arena.ensure((size_t)off + 64), "alloc arena");
   }
-  std::vector<std::pair<int32_t, int32_t>> blocks;
-  // blocks across length changes: bins below the full block size (config 3: 4.15 vs 3.61 M UMIs/s; a 2M-read bin
-  // gains nothing, its length runs are many blocks long: profiles/r03/mixlen_ab.json)
-  const bool mix = c->tun.mix_len > 0 || (c->tun.mix_len < 0 && (B < kMaxBlock || c->pack_on));
-  // the blocks from query `from` on, at most `bmax` queries (of one length each unless mix)
-  auto split_blocks = [&](int32_t from, int32_t bmax) {
-    // packs: bmax (a deep cluster's halved size) holds until the end of `from`'s bin, the next bins start at B
-    const int32_t until = c->pack_on ? c->bin_s[c->hqbin[from] + 1] : s1;
-    for (int32_t q0 = from; q0 < s1;) {
-      int32_t same = 1;
-      const int32_t bcap = q0 < until ? bmax : B;
-      if (mix) {  // across length changes, at most kSegLens lengths (one pair segment each)
-        const int32_t lim = std::min<int32_t>(bcap, s1 - q0);
-        int32_t lo = c->hlen[q0], hi = lo;  // (a pack's lengths restart at every bin)
-        while (same < lim && std::max<int32_t>(hi, c->hlen[q0 + same]) - std::min<int32_t>(lo, c->hlen[q0 + same]) < kSegLens) {
-          lo = std::min<int32_t>(lo, c->hlen[q0 + same]);
-          hi = std::max<int32_t>(hi, c->hlen[q0 + same]);
-          same++;
-        }
-      } else {
-        while (q0 + same < s1 && same < bcap && c->hlen[q0 + same] == c->hlen[q0]) same++;
-      }
-      // O4: a block cut by the size cap ends at a round start (trimmed by < 1 round), so the next block's window needs
-      // no round tile: only blocks starting at a length change (or a bin start in a pack) still begin mid-round
-      // (same-box A/B: config 3 +2.2 %, config 5 +1.8 %, config 2 unchanged; profiles/r05/round_align_ab/)
-      if (c->o4_T && same == bcap && q0 + same < s1) {
-        const int32_t r = round_start(c, s0, q0 + same);
-        if (r > q0 + same / 2) same = r - q0;
-      }
-      blocks.push_back({q0, same});
-      q0 += same;
-    }
-  };
-  // Policy O4 batched rounds (c->o4_T queries each, counted from the first sorted query of q's bin): query q's search
+
+  void alloc_traceback() {
+    c->t_opsidx.assign(n, -1);  // member -> its traceback slot
+    c->hip(c->h_mpq.ensure((size_t)std::max(n, 1)), "pin");
+    c->hip(c->h_mpt.ensure((size_t)std::max(n, 1)), "pin");
+    c->hip(c->t_mpq.ensure(n), "alloc");
+    c->hip(c->t_mpt.ensure(n), "alloc");
+    c->hip(c->t_mout.ensure(n), "alloc");
+    c->hip(c->t_ops.ensure((size_t)std::max(n, 1) * kOpsStride), "alloc");
+    c->hip(c->t_nops.ensure(n), "alloc");
+    ds = dev_seqs(c);
+    tw_maxl = s1 > s0 ? *std::max_element(c->hlen.begin() + s0, c->hlen.begin() + s1) : kMaxLen;
+  }
+
+  // ---- the O4 round window
+  // Policy O4 batched rounds (T4 queries each, counted from the first sorted query of q's bin): query q's search
   // sees only the centroids before its round start rstart(q), and the centroids of its round before it are the
   // re-check's extras -- both must be in its pass's peer window, and the index must hold nothing from the round.
   // Every pass that may still run or re-run counts: a queued pass is re-run alone when its block overflows a peer
@@ -1557,20 +1556,18 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
   // pass's own first query): when block k overflowed after pass k+1 had been queued, block k's re-run met centroids
   // of its own first round in the index -- config 5 under --threads 25 aligned 15-50 more pairs than the oracle and
   // moved reads between clusters, tests/test_gpu_o4.py::test_o4_config_vs_oracle_golden.)
-  const int32_t T4 = c->o4_T;
-  auto rstart = [&](int32_t q) { return round_start(c, s0, q); };
-  std::vector<int32_t> pending;
-  auto sync_index = [&](int32_t X) {  // the index gets the pending centroids before seqno X
+  int32_t rstart(int32_t q) const { return round_start(c, s0, q); }
+  void sync_index(int32_t X) {  // the index gets the pending centroids before seqno X
     size_t m = 0;
     while (m < pending.size() && pending[m] < X) m++;
     if (!m) return;
     std::vector<int32_t> a(pending.begin(), pending.begin() + (ptrdiff_t)m);
     append_centroids(c, a);
     pending.erase(pending.begin(), pending.begin() + (ptrdiff_t)m);
-  };
+  }
   // the window of a pass starting at query q with the nprev tiles prevs (oldest first), adjusted for the rounds:
   // the round tile (counter region 2; the block tiles of the D = 2 ring use 0 and 1) goes in front
-  auto round_window = [&](int32_t q, const Tile** prevs, int& nprev, int slot) {
+  void round_window(int32_t q, const Tile** prevs, int& nprev, int slot) {
     const int32_t first = nprev ? prevs[0]->base : q;
     const int32_t W = rstart(first);
     if (W < first) {
@@ -1585,52 +1582,251 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
       nprev++;
     }
     sync_index(W);
-  };
-  // a bin starts at the block size the previous one ended with, doubled (deep bins tend to follow deep bins)
-  int32_t b_eff = c->pack_on ? B : std::min<int64_t>(B, std::max<int64_t>(256, (int64_t)c->b_hint * 2));
-  int32_t eff_bin = -1;  // packs: the bin b_eff was last halved in (a deep cluster of one bin does not shrink the next)
-  // Halving stops at 256 queries (a floor of kPeerCap / 4 = 32, at which no window can overflow, ran config 4's
-  // giant-molecule bin 200 in 8,578 blocks: 1.44 s alone against 0.6 s at 256; a peer-load feedback that re-cut the
-  // queued blocks from each block's largest peer list lost on config 5: profiles/r04/block_policy)
-  constexpr int32_t kMinBlock = 256;
-  auto halve = [&](int32_t q) -> bool {  // false: already at the smallest block
-    if (c->pack_on && c->hqbin[q] != eff_bin) {
-      eff_bin = c->hqbin[q];
-      b_eff = B;
+  }
+
+  // ---- what both pipelines share
+  // the resolved block's (or prefix's) new centroids join the index -- under O4 once the window start has passed them
+  void keep_new_cents() {
+    if (T4) pending.insert(pending.end(), new_cents.begin(), new_cents.end());
+    else append_centroids(c, new_cents);
+    c->stats.n_blocks++;
+  }
+  // block k is resolved: are the next passes lazy?  (`ahead`: the pass enqueued next is block k + ahead's)
+  void count_lazy(int32_t k, int32_t ahead) {
+    lazy = (int64_t)new_cents.size() * 1000 < (int64_t)plan.blocks[k].second * kLazyPermille;
+    c->stats.n_lazy_passes += (lazy && k + ahead < plan.nb()) ? 1 : 0;
+  }
+  // A block whose peer list overflowed: re-run it alone (window = itself, index complete up to it)
+  // in halving pieces, synchronously.
+  void run_alone(int32_t q0, int32_t nq) {
+    Pass& P = c->pass[0];
+    int32_t piece = nq;
+    for (int32_t q = q0; q < q0 + nq;) {
+      const int32_t m = std::min(piece, q0 + nq - q);
+      const Tile* prevs[kPeerTiles];
+      int nprev = 0;
+      if (T4) round_window(q, prevs, nprev, 0);
+      enqueue_pass(c, P, q, m, prevs, nprev, c->solo_tile, 0);
+      c->stats.n_reruns++;
+      int32_t done = 0;
+      const bool all = resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, &done);
+      if (done > 0) {  // the whole piece, or its prefix before the first overflowing query
+        keep_new_cents();
+        q += done;
+      }
+      if (!all && done == 0) {
+        if (m == 1) c->fail(UMICLUST_EDEVICE, "peer overflow with block of 1");
+        piece = std::max(1, m / 2);
+      }
     }
-    if (b_eff <= kMinBlock) return false;
-    b_eff = std::max(kMinBlock, b_eff / 2);
-    return true;
-  };
-  split_blocks(s0, b_eff);
-  int32_t nb = (int32_t)blocks.size();
-  int32_t clean = 0;  // blocks resolved since the last overflow (regrowth)
-  std::vector<int32_t> new_cents;
-  // Member tracebacks: tw_launch(lo, hi, stream) traces the members among seqnos [lo, hi) (their targets are final),
-  // queries of <= 64 nt in a launch of their own (a one-stripe direction store: more waves per CU), appending to the
-  // pair arrays at tw_n; opsidx maps a member to its traceback slot.  (Tracing the first blocks' members early on a
-  // least-priority stream while later blocks are clustered measured no faster: round 4 cumask_early_ab/.)
-  std::vector<int32_t>& opsidx = c->t_opsidx;
-  opsidx.assign(n, -1);
-  int32_t tw_n = 0;
-  c->hip(c->h_mpq.ensure((size_t)std::max(n, 1)), "pin");
-  c->hip(c->h_mpt.ensure((size_t)std::max(n, 1)), "pin");
-  c->hip(c->t_mpq.ensure(n), "alloc");
-  c->hip(c->t_mpt.ensure(n), "alloc");
-  c->hip(c->t_mout.ensure(n), "alloc");
-  c->hip(c->t_ops.ensure((size_t)std::max(n, 1) * kOpsStride), "alloc");
-  c->hip(c->t_nops.ensure(n), "alloc");
-  const DevSeqs ds = dev_seqs(c);
-  const int32_t tw_maxl = s1 > s0 ? *std::max_element(c->hlen.begin() + s0, c->hlen.begin() + s1) : kMaxLen;
-  // members of <= 64-nt queries in a launch of their own (one launch for all measured equal: round 4 twsplit_ab/)
-  constexpr int tw_split = 64;
-  auto tw_launch = [&](int32_t lo, int32_t hi, hipStream_t stq) {
+  }
+
+  // ---- step 2a: whole passes
+  // Software pipeline over blocks, D passes in flight: passes k+1 .. k+D-1 are queued before
+  // the host resolves block k.  Pass j runs against the index of the blocks before its peer window (blocks
+  // j-D+1 .. j), and the window covers every later query before block j's, so C_old u window = all queries
+  // before j: the merged walk is exact.  Invariant at the top of iteration k: passes k .. k+D-1 (those that
+  // exist) are queued, the index holds blocks < k.  Block k's peer tile lives in blk_tile[k % (D + 1)]
+  // (read by passes k .. k+D-1) and counts into peer region k % D of the prefilter counters.
+  Tile& tile_of(int32_t k) { return c->blk_tile[k % (D + 1)]; }
+  // enqueue block k's pass with the nprev blocks before it in its peer window
+  void enqueue(int32_t k, int nprev) {
+    const Tile* prevs[kPeerTiles];
+    for (int i = 0; i < nprev; i++) prevs[i] = &tile_of(k - nprev + i);
+    if (T4) round_window(plan.blocks[k].first, prevs, nprev, k);
+    enqueue_pass(c, c->pass[k % D], plan.blocks[k].first, plan.blocks[k].second, prevs, nprev, tile_of(k), k % D, lazy);
+  }
+  // block k + D's peer tile depends on its queries only: build it now, while the host resolves block k (its ring
+  // slot was last read by pass k's prefilter).  Since round 6 on the side stream (after pass k's prefilter), so
+  // the build runs beside the main stream's counting instead of between two counting launches; the pass that
+  // next enqueues on the main stream waits for it (wait_index_and_tiles, pt_ev).  Before, it sat on the main stream.
+  void prebuild_peer(int32_t k) {
+    const auto& blk = plan.blocks[k + D];
+    Tile& t = tile_of(k + D);
+    hipStream_t bst = multi_bin ? nullptr : c->st_b;  // config 2 +1.6 %, multi-lane config 3 -2 %
+    if (bst) {
+      c->hip(hipStreamWaitEvent(bst, c->pass[k % D].ev[1], 0), "wait");
+      if (!c->pt_ev) c->hip(hipEventCreateWithFlags(&c->pt_ev, hipEventDisableTiming), "event");
+    }
+    build_tile(c, t, c->d_iota.p, blk.first, blk.second, 0, ((k + D) % D) * kPeerRegion, 1 << 30, bst);
+    if (bst) {
+      c->hip(hipEventRecord(c->pt_ev, bst), "event");
+      c->pt_pending = true;
+    }
+    t.base = blk.first;
+    t.seg = (k + D) % D;
+    t.prebuilt = true;
+  }
+  void run_whole() {
+    for (int32_t i = 0; i < D && i < plan.nb(); i++) enqueue(i, i);
+    for (int32_t k = 0; k < plan.nb(); k++) {
+      Pass& P = c->pass[k % D];
+      const double te0 = now_s();
+      if (k + D < plan.nb()) prebuild_peer(k);
+      c->dbg.t.enqueue += now_s() - te0;
+      int32_t done = 0;
+      if (!resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, &done)) {
+        // drain the queued passes k+1 .. k+D-1 (their windows include block k) and restart the pipeline
+        for (int i = 1; i < D; i++) {
+          Pass& Q = c->pass[(k + i) % D];
+          if (Q.live) {
+            c->hip(hipEventSynchronize(Q.ev[4]), "sync");
+            Q.live = false;
+          }
+        }
+        // the block's prefix before its first overflowing query is resolved (its queries' peers are all earlier)
+        if (done > 0) keep_new_cents();
+        // an overflowing bin runs synchronous re-runs from here on: with other lanes sharing the GPU they queue behind
+        // every lane's work unless its main stream goes first (config 4: a 792k-read bin with a giant molecule took
+        // 7.2 s among 8 lanes, 0.6 s alone)
+        run_alone(plan.blocks[k].first + done, plan.blocks[k].second - done);
+        plan.overflowed(k);
+        for (int i = 1; i <= D; i++)
+          if (k + i < plan.nb()) enqueue(k + i, i - 1);
+        continue;
+      }
+      keep_new_cents();
+      count_lazy(k, D);
+      if (plan.resolved(k, D, c->last_max_npeer)) {  // regrowth: the blocks from k + D on were re-cut
+        c->stats.n_regrows++;
+        tile_of(k + D).prebuilt = false;
+      }
+      const double te1 = now_s();
+      if (k + D < plan.nb()) enqueue(k + D, D - 1);
+      c->dbg.t.enqueue += now_s() - te1;
+    }
+  }
+
+  // ---- step 2b: split passes
+  // Pass j = counting half A(j) (index of blocks <= j-3, window j-2 .. j with block j-2
+  // flagged) enqueued after block j-3 is resolved, and second half R(j) (the full kernel over A's
+  // overflowed units against index <= j-2 / window j-1 .. j, the merge keeping the flagged hits that are
+  // centroids, then walk / align / pack) after block j-2 is.  Block j's peer tile: blk_tile[j % 4],
+  // counter region j % 3 (three consecutive blocks share a counting window).
+  // Unlike run_whole, this loop never regrows the blocks (plan.resolved is not called, so the planner's clean count
+  // is never read here) and resolves without partial resolution: an overflowing block is re-run whole.
+  Tile& stile(int32_t j) { return c->blk_tile[j % (kPeerTiles + 1)]; }
+  void build_peer(int32_t j, bool side) {
+    const auto& blk = plan.blocks[j];
+    Tile& t = stile(j);
+    const int32_t region = j % kPeerTiles;
+    if (!(t.prebuilt && t.base == blk.first && t.n == blk.second && t.seg == region)) {
+      hipStream_t bs = c->st;
+      if (side && c->ix_st) {
+        bs = c->ix_st;
+        if (c->last_r_ev) c->hip(hipStreamWaitEvent(bs, c->last_r_ev, 0), "wait");
+      }
+      build_tile(c, t, c->d_iota.p, blk.first, blk.second, 0, region * kPeerRegion, 1 << 30, bs);
+      if (bs != c->st) {
+        if (!c->ix_done) c->hip(hipEventCreate(&c->ix_done), "event");
+        c->hip(hipEventRecord(c->ix_done, bs), "event");
+      }
+    }
+    t.base = blk.first;
+    t.seg = region;
+    t.len = c->hlen[blk.first];
+    t.prebuilt = true;
+  }
+  // R(j) with the window's blocks from `first` (first = j - 1 in the steady state)
+  void second_half(int32_t j, int32_t first, bool after_count) {
+    const Tile* prevs[kPeerTiles];
+    int np = 0;
+    for (int32_t i = first; i < j; i++) prevs[np++] = &stile(i);
+    enqueue_pass(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, prevs, np, stile(j), j % kPeerTiles, lazy,
+                 after_count);
+  }
+  void count_half(int32_t j, int32_t first, int flag) {
+    const Tile* wins[kPeerTiles];
+    int nw = 0;
+    for (int32_t i = first; i <= j; i++) wins[nw++] = &stile(i);
+    enqueue_count(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, wins, nw, flag, j % 4);
+  }
+  // the index holds the blocks before r and nothing is queued: classic passes r (window r) and r+1 (window
+  // r, r+1), then A(r+2) with block r flagged
+  void prime(int32_t r) {
+    const int32_t nb = plan.nb();
+    for (int32_t j = r; j < r + 3 && j < nb; j++) build_peer(j, false);
+    if (r < nb) second_half(r, r, false);
+    if (r + 1 < nb) second_half(r + 1, r, false);
+    if (r + 2 < nb) count_half(r + 2, r, 0);
+  }
+  void run_split() {
+    prime(0);
+    for (int32_t k = 0; k < plan.nb(); k++) {
+      Pass& P = c->pass[k % 2];
+      const double tb0 = now_s();
+      if (k + 3 < plan.nb()) build_peer(k + 3, true);  // queries only: built while the host resolves block k
+      c->dbg.t.enqueue += now_s() - tb0;
+      if (!resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, nullptr)) {
+        // drain everything queued (its windows include block k) and restart the pipeline after block k
+        c->hip(hipStreamSynchronize(c->st_al), "sync");
+        c->hip(hipStreamSynchronize(c->st_b), "sync");
+        c->hip(hipStreamSynchronize(c->st), "sync");
+        for (Pass& Q : c->pass) {
+          Q.live = false;
+          Q.a_live = false;
+          c->hip(hipMemsetAsync(Q.d_anunits.p, 0, 4, c->st), "memset");
+        }
+        run_alone(plan.blocks[k].first, plan.blocks[k].second);
+        plan.overflowed(k);
+        for (Tile& t : c->blk_tile) t.prebuilt = false;
+        prime(k + 1);
+        continue;
+      }
+      const double ta0 = now_s();
+      keep_new_cents();
+      const double ta1 = now_s();
+      count_lazy(k, 2);
+      if (k + 2 < plan.nb()) second_half(k + 2, k + 1, true);
+      if (k + 3 < plan.nb()) count_half(k + 3, k + 1, 0);
+      c->dbg.t.appends += ta1 - ta0;          // UMICLUST_DEBUG: index appends (host side)
+      c->dbg.t.enqueue += now_s() - ta1;      // and the next passes' enqueue
+    }
+  }
+
+  // ---- step 2: cluster the blocks
+  void run_pipeline() {
+    // split passes shorten the host <-> device cycle of one bin at the price of a wider counting window;
+    // multi-bin sets run several lanes on one GPU, which is throughput-bound: there the whole passes win
+    // (configs 2 / 5: +12 % / +2 %, config 3: -6 %; profiles/r02/split_ab.json)
+    const bool split = !T4 && (c->tun.split_env >= 0 ? c->tun.split_env != 0 : !multi_bin) && D == 2;
+    c->ix_st = split ? c->st_b : nullptr;
+    c->last_r_ev = nullptr;
+    if (split) run_split();
+    else run_whole();
+    c->b_hint = plan.b_eff;
+    // centroids still pending (O4): creation numbers only, no index is needed any more
+    c->cent.insert(c->cent.end(), pending.begin(), pending.end());
+  }
+
+  // ---- step 3: drain the streams; the main stream gets the caller's priority back
+  void drain() {
+    c->hip(hipStreamSynchronize(c->st_b), "sync");
+    c->ix_st = nullptr;
+    c->hip(hipStreamSynchronize(c->st_al), "sync");
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    c->hip(main_stream_priority(c, c->prio_user), "stream priority");
+    for (size_t i = 0; i < c->nix; i++) {
+      float ms = 0;
+      c->hip(hipEventElapsedTime(&ms, c->ix_events[i].first, c->ix_events[i].second), "elapsed");
+      c->stats.t_index_s += ms * 1e-3;
+    }
+  }
+
+  // ---- step 4: member tracebacks
+  // tw_launch(lo, hi, stream) traces the members among seqnos [lo, hi) (their targets are final), queries of <= 64 nt
+  // in a launch of their own (a one-stripe direction store: more waves per CU; one launch for all measured equal:
+  // round 4 twsplit_ab/), appending to the pair arrays at tw_n; t_opsidx maps a member to its traceback slot.
+  // (Tracing the first blocks' members early on a least-priority stream while later blocks are clustered measured no
+  // faster: round 4 cumask_early_ab/.)
+  void tw_launch(int32_t lo, int32_t hi, hipStream_t stq) {
+    constexpr int tw_split = 64;
     const int32_t x0 = tw_n;
     int32_t x = x0, nm1 = 0, maxq1 = 0, maxq2 = 0;
     for (int pass = 0; pass < 2; pass++) {
       for (int32_t s = lo; s < hi; s++)
         if (c->target[s] >= 0 && (((int)c->hlen[s] <= tw_split) == (pass == 0))) {
-          opsidx[s - s0] = x;
+          c->t_opsidx[s - s0] = x;
           c->h_mpq.p[x] = ((uint32_t)s << 1) | c->strand[s];
           c->h_mpt.p[x] = (uint32_t)c->target[s];
           (pass ? maxq2 : maxq1) = std::max(pass ? maxq2 : maxq1, (int32_t)c->hlen[s]);
@@ -1648,302 +1844,41 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
     c->hip(launch_traceback(ds, c->t_mpq.p + nm1, c->t_mpt.p + nm1, x - nm1, c->sc, c->t_ops.p + (size_t)nm1 * kOpsStride,
                             c->t_nops.p + nm1, c->t_mout.p + nm1, stq, tw_maxl, maxq2),
            "traceback");
-  };
-  // A block whose peer list overflowed: re-run it alone (window = itself, index complete up to it)
-  // in halving pieces, synchronously.
-  auto run_alone = [&](int32_t q0, int32_t nq) {
-    Pass& P = c->pass[0];
-    int32_t piece = nq;
-    for (int32_t q = q0; q < q0 + nq;) {
-      const int32_t m = std::min(piece, q0 + nq - q);
-      const Tile* prevs[kPeerTiles];
-      int nprev = 0;
-      if (T4) round_window(q, prevs, nprev, 0);
-      enqueue_pass(c, P, q, m, prevs, nprev, c->solo_tile, 0);
-      c->stats.n_reruns++;
-      int32_t done = 0;
-      const bool all = resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, &done);
-      if (done > 0) {  // the whole piece, or its prefix before the first overflowing query
-        if (T4) pending.insert(pending.end(), new_cents.begin(), new_cents.end());
-        else append_centroids(c, new_cents);
-        c->stats.n_blocks++;
-        q += done;
-      }
-      if (!all && done == 0) {
-        if (m == 1) c->fail(UMICLUST_EDEVICE, "peer overflow with block of 1");
-        piece = std::max(1, m / 2);
-      }
-    }
-  };
-  // Software pipeline over blocks, D = c->depth passes in flight: passes k+1 .. k+D-1 are queued before
-  // the host resolves block k.  Pass j runs against the index of the blocks before its peer window (blocks
-  // j-D+1 .. j), and the window covers every later query before block j's, so C_old u window = all queries
-  // before j: the merged walk is exact.  Invariant at the top of iteration k: passes k .. k+D-1 (those that
-  // exist) are queued, the index holds blocks < k.  Block k's peer tile lives in blk_tile[k % (D + 1)]
-  // (read by passes k .. k+D-1) and counts into peer region k % D of the prefilter counters.
-  const int D = T4 ? 2 : c->depth;
-  auto tile_of = [&](int32_t k) -> Tile& { return c->blk_tile[k % (D + 1)]; };
-  // Lazy peers: once new centroids have become rare (the last resolved block created fewer than
-  // lazy_permille per mille), in-window peers are not aligned speculatively; a query whose relevant peer
-  // turns out to be a centroid is deferred and round B aligns what it needs (deep clusters: config 5)
-  bool lazy = false;
-  // enqueue block k's pass with the nprev blocks before it in its peer window
-  auto enqueue = [&](int32_t k, int nprev) {
-    const Tile* prevs[kPeerTiles];
-    for (int i = 0; i < nprev; i++) prevs[i] = &tile_of(k - nprev + i);
-    if (T4) round_window(blocks[k].first, prevs, nprev, k);
-    enqueue_pass(c, c->pass[k % D], blocks[k].first, blocks[k].second, prevs, nprev, tile_of(k), k % D, lazy);
-  };
-  // split passes shorten the host <-> device cycle of one bin at the price of a wider counting window;
-  // multi-bin sets run several lanes on one GPU, which is throughput-bound: there the whole passes win
-  // (configs 2 / 5: +12 % / +2 %, config 3: -6 %; profiles/r02/split_ab.json)
-  const bool split = !T4 && (c->tun.split_env >= 0 ? c->tun.split_env != 0 : !multi_bin);
-  c->ix_st = (split && D == 2) ? c->st_b : nullptr;
-  c->last_r_ev = nullptr;
-  if (split && D == 2) {
-    // Split passes.  Pass j = counting half A(j) (index of blocks <= j-3, window j-2 .. j with block j-2
-    // flagged) enqueued after block j-3 is resolved, and second half R(j) (the full kernel over A's
-    // overflowed units against index <= j-2 / window j-1 .. j, the merge keeping the flagged hits that are
-    // centroids, then walk / align / pack) after block j-2 is.  Block j's peer tile: blk_tile[j % 4],
-    // counter region j % 3 (three consecutive blocks share a counting window).
-    auto stile = [&](int32_t j) -> Tile& { return c->blk_tile[j % (kPeerTiles + 1)]; };
-    auto build_peer = [&](int32_t j, bool side) {
-      Tile& t = stile(j);
-      const int32_t region = j % kPeerTiles;
-      if (!(t.prebuilt && t.base == blocks[j].first && t.n == blocks[j].second && t.seg == region)) {
-        hipStream_t bs = c->st;
-        if (side && c->ix_st) {
-          bs = c->ix_st;
-          if (c->last_r_ev) c->hip(hipStreamWaitEvent(bs, c->last_r_ev, 0), "wait");
-        }
-        build_tile(c, t, c->d_iota.p, blocks[j].first, blocks[j].second, 0, region * kPeerRegion, 1 << 30, bs);
-        if (bs != c->st) {
-          if (!c->ix_done) c->hip(hipEventCreate(&c->ix_done), "event");
-          c->hip(hipEventRecord(c->ix_done, bs), "event");
-        }
-      }
-      t.base = blocks[j].first;
-      t.seg = region;
-      t.len = c->hlen[blocks[j].first];
-      t.prebuilt = true;
-    };
-    // R(j) with the window's blocks from `first` (first = j - 1 in the steady state)
-    auto second_half = [&](int32_t j, int32_t first, bool after_count) {
-      const Tile* prevs[kPeerTiles];
-      int np = 0;
-      for (int32_t i = first; i < j; i++) prevs[np++] = &stile(i);
-      enqueue_pass(c, c->pass[j % 2], blocks[j].first, blocks[j].second, prevs, np, stile(j), j % kPeerTiles, lazy,
-                   after_count);
-    };
-    auto count_half = [&](int32_t j, int32_t first, int flag) {
-      const Tile* wins[kPeerTiles];
-      int nw = 0;
-      for (int32_t i = first; i <= j; i++) wins[nw++] = &stile(i);
-      enqueue_count(c, c->pass[j % 2], blocks[j].first, blocks[j].second, wins, nw, flag, j % 4);
-    };
-    // the index holds the blocks before r and nothing is queued: classic passes r (window r) and r+1 (window
-    // r, r+1), then A(r+2) with block r flagged
-    auto prime = [&](int32_t r) {
-      for (int32_t j = r; j < r + 3 && j < nb; j++) build_peer(j, false);
-      if (r < nb) second_half(r, r, false);
-      if (r + 1 < nb) second_half(r + 1, r, false);
-      if (r + 2 < nb) count_half(r + 2, r, 0);
-    };
-    prime(0);
-    for (int32_t k = 0; k < nb; k++) {
-      Pass& P = c->pass[k % 2];
-      const double tb0 = now_s();
-      if (k + 3 < nb) build_peer(k + 3, true);  // queries only: built while the host resolves block k
-      c->dbg_t[5] += now_s() - tb0;
-      if (!resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, nullptr)) {
-        // drain everything queued (its windows include block k) and restart the pipeline after block k
-        c->hip(hipStreamSynchronize(c->st_al), "sync");
-        c->hip(hipStreamSynchronize(c->st_b), "sync");
-        c->hip(hipStreamSynchronize(c->st), "sync");
-        for (Pass& Q : c->pass) {
-          Q.live = false;
-          Q.a_live = false;
-          c->hip(hipMemsetAsync(Q.d_anunits.p, 0, 4, c->st), "memset");
-        }
-      run_alone(blocks[k].first, blocks[k].second);
-        if (k + 1 < nb && halve(blocks[k].first)) {
-          const int32_t from = blocks[k].first + blocks[k].second;
-          blocks.resize((size_t)k + 1);
-          split_blocks(from, b_eff);
-          nb = (int32_t)blocks.size();
-        }
-        for (Tile& t : c->blk_tile) t.prebuilt = false;
-        prime(k + 1);
-        continue;
-      }
-      const double ta0 = now_s();
-      append_centroids(c, new_cents);
-      const double ta1 = now_s();
-      c->stats.n_blocks++;
-      lazy = (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
-      c->stats.n_lazy_passes += (lazy && k + 2 < nb) ? 1 : 0;
-      if (k + 2 < nb) second_half(k + 2, k + 1, true);
-      if (k + 3 < nb) count_half(k + 3, k + 1, 0);
-      c->dbg_t[7] += ta1 - ta0;           // UMICLUST_DEBUG: index appends (host side)
-      c->dbg_t[5] += now_s() - ta1;       // and the next passes' enqueue
-    }
-  } else {
-  for (int32_t i = 0; i < D && i < nb; i++) enqueue(i, i);
-  for (int32_t k = 0; k < nb; k++) {
-    Pass& P = c->pass[k % D];
-    const double te0 = now_s();
-    if (k + D < nb) {
-      // block k+D's peer tile depends on its queries only: build it now, while the host resolves block k (its ring
-      // slot was last read by pass k's prefilter).  Since round 6 on the side stream (after pass k's prefilter), so
-      // the build runs beside the main stream's counting instead of between two counting launches; the pass that
-      // next enqueues on the main stream waits for it (enqueue_pass, pt_ev).  Before, it sat on the main stream.
-      Tile& t = tile_of(k + D);
-      hipStream_t bst = multi_bin ? nullptr : c->st_b;  // config 2 +1.6 %, multi-lane config 3 -2 %
-      if (bst) {
-        c->hip(hipStreamWaitEvent(bst, P.ev[1], 0), "wait");
-        if (!c->pt_ev) c->hip(hipEventCreateWithFlags(&c->pt_ev, hipEventDisableTiming), "event");
-      }
-      build_tile(c, t, c->d_iota.p, blocks[k + D].first, blocks[k + D].second, 0, ((k + D) % D) * kPeerRegion,
-                 1 << 30, bst);
-      if (bst) {
-        c->hip(hipEventRecord(c->pt_ev, bst), "event");
-        c->pt_pending = true;
-      }
-      t.base = blocks[k + D].first;
-      t.seg = (k + D) % D;
-      t.prebuilt = true;
-    }
-    c->dbg_t[5] += now_s() - te0;
-    int32_t done = 0;
-    if (!resolve_pass(c, P, state, new_cents, t_pf, t_al, t_host, &done)) {
-      // drain the queued passes k+1 .. k+D-1 (their windows include block k) and restart the pipeline
-      for (int i = 1; i < D; i++) {
-        Pass& Q = c->pass[(k + i) % D];
-        if (Q.live) {
-          c->hip(hipEventSynchronize(Q.ev[4]), "sync");
-          Q.live = false;
-        }
-      }
-      // the block's prefix before its first overflowing query is resolved (its queries' peers are all earlier)
-      if (done > 0) {
-        if (T4) pending.insert(pending.end(), new_cents.begin(), new_cents.end());
-        else append_centroids(c, new_cents);
-        c->stats.n_blocks++;
-      }
-      // an overflowing bin runs synchronous re-runs from here on: with other lanes sharing the GPU they queue behind
-      // every lane's work unless its main stream goes first (config 4: a 792k-read bin with a giant molecule took
-      // 7.2 s among 8 lanes, 0.6 s alone)
-      run_alone(blocks[k].first + done, blocks[k].second - done);
-      clean = 0;
-      // deep clusters flood the peer window: later blocks are cut smaller (a smaller window holds fewer
-      // same-molecule peers), so the overflow re-runs do not repeat block after block
-      if (k + 1 < nb && halve(blocks[k].first)) {
-        const int32_t from = blocks[k].first + blocks[k].second;
-        blocks.resize((size_t)k + 1);
-        split_blocks(from, b_eff);
-        nb = (int32_t)blocks.size();
-      }
-      for (int i = 1; i <= D; i++)
-        if (k + i < nb) enqueue(k + i, i - 1);
-      continue;
-    }
-    if (T4) pending.insert(pending.end(), new_cents.begin(), new_cents.end());
-    else append_centroids(c, new_cents);
-    c->stats.n_blocks++;
-    lazy = (int64_t)new_cents.size() * 1000 < (int64_t)blocks[k].second * c->lazy_permille;
-    c->stats.n_lazy_passes += (lazy && k + D < nb) ? 1 : 0;
-    // Regrowth: after `regrow` consecutive blocks without an overflow whose deepest peer list stayed below a quarter of
-    // the cap, the blocks not yet queued are cut at twice the size.  With overflowing blocks resolved up to their first
-    // overflowing query (resolve_pass), a giant molecule's stretch no longer pins a bin at 256-query blocks: config 4's
-    // bin 200 7.0 -> 1.6 s among 8 lanes, config 4 6.51 -> 7.59 M UMIs/s; config 5's windows stay deep, so its blocks
-    // do not grow (3.33 / 3.36 M; ungated regrowth after 4 clean blocks: 2.47 M) -- profiles/r05/regrow_ab/.
-    if (c->last_max_npeer >= c->regrow_depth) {
-      clean = 0;  // a deep window: no regrowth yet, and it does not count as a clean block
-    } else if (c->tun.regrow > 0 && b_eff < B && ++clean >= c->tun.regrow && k + D < nb) {
-      b_eff = std::min<int32_t>(B, b_eff * 2);
-      c->stats.n_regrows++;
-      clean = 0;
-      const int32_t from = blocks[k + D].first;
-      blocks.resize((size_t)k + D);
-      split_blocks(from, b_eff);
-      nb = (int32_t)blocks.size();
-      tile_of(k + D).prebuilt = false;
-    }
-    const double te1 = now_s();
-    if (k + D < nb) enqueue(k + D, D - 1);
-    c->dbg_t[5] += now_s() - te1;
   }
-  }
-  c->b_hint = b_eff;
-  // centroids still pending (O4): creation numbers only, no index is needed any more
-  c->cent.insert(c->cent.end(), pending.begin(), pending.end());
-  c->hip(hipStreamSynchronize(c->st_b), "sync");
-  c->ix_st = nullptr;
-  c->hip(hipStreamSynchronize(c->st_al), "sync");
-  c->hip(hipStreamSynchronize(c->st), "sync");
-  c->hip(main_stream_priority(c, c->prio_user), "stream priority");
-  for (size_t i = 0; i < c->nix; i++) {
-    float ms = 0;
-    c->hip(hipEventElapsedTime(&ms, c->ix_events[i].first, c->ix_events[i].second), "elapsed");
-    c->stats.t_index_s += ms * 1e-3;
-  }
-  // --- member tracebacks first: their pairs (sorted seqno order) need only the targets, so the launch goes out
+  // The tracebacks go first: their pairs (sorted seqno order) need only the targets, so the launch goes out
   // before the host numbers the clusters, which then overlaps the traceback (round 4: the numbering and the
-  // pageable pair uploads were ~16 ms of idle GPU before the traceback of a 2M-read bin).  The members before
-  tw_launch(s0, s1, c->st);
-  const int32_t nm = tw_n;
-  if (!c->tev[0]) {
-    c->hip(hipEventCreate(&c->tev[0]), "event");
-    c->hip(hipEventCreate(&c->tev[1]), "event");
+  // pageable pair uploads were ~16 ms of idle GPU before the traceback of a 2M-read bin).
+  void trace_members() {
+    tw_launch(s0, s1, c->st);
+    if (!c->tev[0]) {
+      c->hip(hipEventCreate(&c->tev[0]), "event");
+      c->hip(hipEventCreate(&c->tev[1]), "event");
+    }
+    c->hip(hipEventRecord(c->tev[0], c->st), "event");
   }
-  c->hip(hipEventRecord(c->tev[0], c->st), "event");
-  (void)nm;
-  // creation numbers: centroids in creation (= sorted seqno) order, members inherit their centroid's
-  c->nclusters = (int32_t)c->cent.size();
-  for (int32_t k = 0; k < c->nclusters; k++) c->cno[c->cent[k]] = k;
-  for (int32_t s = s0; s < s1; s++)
-    if (c->target[s] >= 0) c->cno[s] = c->cno[c->target[s]];
-  // --- output numbering: --clusterout_sort orders clusters by size desc, creation order
-  const int32_t K = c->nclusters;
-  std::vector<int32_t> size(K, 0);
-  for (int32_t s = s0; s < s1; s++) size[c->cno[s]]++;
-  std::vector<int32_t> order(K);
-  for (int32_t k = 0; k < K; k++) order[k] = k;
-  // (a pack's clusters stay grouped by bin -- creation order already is -- and are sorted within their bin)
-  auto cbin = [&](int32_t k) { return c->pack_on ? c->hqbin[c->cent[k]] : 0; };
-  if (c->p.clusterout_sort)
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-      const int32_t ba = cbin(a), bb = cbin(b);
-      return ba != bb ? ba < bb : size[a] > size[b];
-    });
-  c->rank_of.assign(K, 0);
-  for (int32_t k = 0; k < K; k++) c->rank_of[order[k]] = k;
-  c->ostart.assign((size_t)K + 1, 0);
-  for (int32_t s = s0; s < s1; s++) {
-    c->ocl[s] = c->rank_of[c->cno[s]];
-    c->ostart[c->ocl[s] + 1]++;
+
+  // ---- step 5: creation and output numbers (plan.h)
+  void number() {
+    c->nclusters = (int32_t)c->cent.size();
+    number_clusters(s0, s1, c->cent, c->target.data(), c->p.clusterout_sort != 0, c->pack_on ? c->hqbin.data() : nullptr,
+                    bin, npk, c->cno.data(), c->ocl.data(), c->num);
   }
-  for (int32_t k = 0; k < K; k++) c->ostart[k + 1] += c->ostart[k];
-  c->omemb.assign(n, 0);
-  {
-    std::vector<int32_t> fill(c->ostart.begin(), c->ostart.end() - 1);
-    for (int32_t s = s0; s < s1; s++) c->omemb[fill[c->ocl[s]]++] = s;
-  }
-  // --- consensus (behind the traceback on the same stream)
-  double t_cons = 0;
-  {
+
+  // ---- step 6: consensus (behind the traceback on the same stream) and its download
+  void consensus() {
+    const int32_t K = c->nclusters;
     // consensus inputs in output-cluster order (pinned: the uploads are queued, not staged)
     c->hip(c->h_mseq.ensure((size_t)std::max(n, 1)), "pin");
     c->hip(c->h_mops.ensure((size_t)std::max(n, 1)), "pin");
     c->hip(c->h_mstr.ensure((size_t)std::max(n, 1)), "pin");
     c->hip(c->h_cstart.ensure((size_t)K + 1), "pin");
     for (int32_t x = 0; x < n; x++) {
-      const int32_t s = c->omemb[x];
+      const int32_t s = c->num.omemb[x];
       c->h_mseq.p[x] = s;
-      c->h_mops.p[x] = opsidx[s - s0];
+      c->h_mops.p[x] = c->t_opsidx[s - s0];
       c->h_mstr.p[x] = c->strand[s];
     }
-    std::copy(c->ostart.begin(), c->ostart.end(), c->h_cstart.p);
+    std::copy(c->num.ostart.begin(), c->num.ostart.end(), c->h_cstart.p);
     c->hip(c->t_cstart.ensure((size_t)K + 1), "alloc");
     c->hip(c->t_mseq.ensure(n), "alloc");
     c->hip(c->t_mops.ensure(n), "alloc");
@@ -1984,34 +1919,22 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
     for (int32_t k = 0; k < K; k++)
       memcpy(c->cons.data() + c->cons_off[k], craw + (size_t)k * kConsCap, clen[k]);
   }
-  if (!c->pack_on) {
-    auto& bo = c->bout[bin];
-    bo.done = true;
-    bo.K = K;
-    bo.cons = c->cons;
-    bo.cons_off = c->cons_off;
-  } else {
-    // per bin: its output clusters are the consecutive output numbers [k0, k1); numbers within the bin
-    int32_t k0 = 0;
+
+  // ---- step 7: every bin keeps its own clusters' consensus sequences (umiclust_fetch_bin)
+  void store_outputs() {
     for (int32_t b = bin; b < bin + npk; b++) {
-      int32_t k1 = k0;
-      while (k1 < K && cbin(order[k1]) == b) k1++;
+      const int32_t k0 = c->num.bin_k[b - bin], k1 = c->num.bin_k[b - bin + 1];
       auto& bo = c->bout[b];
       bo.done = true;
       bo.K = k1 - k0;
       bo.cons_off.assign((size_t)bo.K + 1, 0);
       for (int32_t k = 0; k <= bo.K; k++) bo.cons_off[k] = c->cons_off[k0 + k] - c->cons_off[k0];
       bo.cons.assign(c->cons.begin() + c->cons_off[k0], c->cons.begin() + c->cons_off[k1]);
-      for (int32_t s = c->bin_s[b]; s < c->bin_s[b + 1]; s++) c->ocl[s] -= k0;
-      k0 = k1;
     }
   }
-  c->stats.n_clusters = K;
-  c->stats.t_prefilter_s = t_pf;
-  c->stats.t_align_s = t_al;
-  c->stats.t_consensus_s = t_cons;
-  c->stats.t_host_s = t_host;
-  if (c->pf_prof.p) {
+
+  // ---- step 8: the call's statistics and the measurement-only reports
+  void report_pf_prof() {
     unsigned long long h[24];
     c->hip(hipMemcpy(h, c->pf_prof.p, sizeof(h), hipMemcpyDeviceToHost), "d2h");
     const double nwg = h[8] ? (double)h[8] : 1.0;
@@ -2029,38 +1952,67 @@ void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t n
               h[18] / nc, h[19] / nc / 100.0, (double)h[18] / ((double)h[19] / 100e6) / 1e9);
     c->hip(hipMemset(c->pf_prof.p, 0, 24 * sizeof(unsigned long long)), "memset");
   }
-  c->stats.t_total_s = now_s() - t0;
-  c->clustered = true;
-  if (c->tun.walk_dump && !c->wd.empty()) {
-    if (FILE* f = fopen(c->tun.walk_dump, "wb")) {
-      fwrite(c->wd.data(), 2, c->wd.size(), f);
-      fclose(f);
-    }
-    c->wd.clear();
-  }
-  if (c->tun.debug) {  // the per-bin summary
+  void report_debug() const {  // UMICLUST_DEBUG: the per-bin summary
+    const DebugSums& d = c->dbg;
     fprintf(stderr, "bin %d: n %d mispredicted %lld saved(seen) %lld blocked %lld deferred %lld\n", bin, n,
-            (long long)c->dbg[0], (long long)c->dbg[1], (long long)c->dbg[2], (long long)c->stats.n_deferred);
+            (long long)d.mispredicted, (long long)d.saved, (long long)d.blocked, (long long)c->stats.n_deferred);
     fprintf(stderr, "bin %d: queries no-record %lld earlier-block-only %lld in-block %lld; pass-1 host %.3f s\n", bin,
-            (long long)c->dbg_q[0], (long long)c->dbg_q[1], (long long)c->dbg_q[2], c->dbg_q[3] * 1e-9);
+            (long long)d.q_no_record, (long long)d.q_earlier_only, (long long)d.q_in_block, d.q_host_ns * 1e-9);
     fprintf(stderr, "bin %d: strands inline %lld many-relevant %lld record-read %lld peers-scanned %lld\n", bin,
-            (long long)c->dbg_p[0], (long long)c->dbg_p[1], (long long)c->dbg_p[2], (long long)c->dbg_p[3]);
+            (long long)d.s_inline, (long long)d.s_many_relevant, (long long)d.s_record_read,
+            (long long)d.s_peers_scanned);
     fprintf(stderr, "bin %d: resolve wait %.3f hq-copy %.3f rec-copy %.3f classify %.3f in-order %.3f total %.3f s "
             "(round B and the rest %.3f: round-B round trips %.3f, rest of resolve_block %.3f, outside it %.3f)\n", bin,
-            c->dbg_t[0], c->dbg_t[1], c->dbg_t[2], c->dbg_t[3], c->dbg_t[4], c->dbg_t[6],
-            c->dbg_t[6] - c->dbg_t[0] - c->dbg_t[1] - c->dbg_t[2] - c->dbg_t[3] - c->dbg_t[4], c->dbg_t[8],
-            c->dbg_t[9] - c->dbg_t[3] - c->dbg_t[4] - c->dbg_t[8],
-            c->dbg_t[6] - c->dbg_t[0] - c->dbg_t[1] - c->dbg_t[2] - c->dbg_t[9]);
+            d.t.wait, d.t.hq_copy, d.t.rec_copy, d.t.classify, d.t.inorder, d.t.total,
+            d.t.total - d.t.wait - d.t.hq_copy - d.t.rec_copy - d.t.classify - d.t.inorder, d.t.round_b,
+            d.t.resolve_block - d.t.classify - d.t.inorder - d.t.round_b,
+            d.t.total - d.t.wait - d.t.hq_copy - d.t.rec_copy - d.t.resolve_block);
     fprintf(stderr, "bin %d: host: split-pass appends %.3f, enqueue (peer tiles, appends, launches) %.3f s; bin %.3f s\n",
-            bin, c->dbg_t[7], c->dbg_t[5], now_s() - t0);
+            bin, d.t.appends, d.t.enqueue, now_s() - t0);
     fprintf(stderr, "bin %d: round B: %.0f round trips, %.0f launches, %.0f pairs, %.4f s between its first and last "
-            "launch's events\n", bin, c->dbg_rb[1], c->dbg_rb[2], c->dbg_rb[3], c->dbg_rb[0]);
+            "launch's events\n", bin, d.rb.trips, d.rb.launches, d.rb.pairs, d.rb.dev_s);
   }
-  for (double& x : c->dbg_rb) x = 0;
-  for (double& x : c->dbg_t) x = 0;
-  c->dbg_q[0] = c->dbg_q[1] = c->dbg_q[2] = c->dbg_q[3] = 0;
-  c->dbg_p[0] = c->dbg_p[1] = c->dbg_p[2] = c->dbg_p[3] = 0;
-  c->dbg[0] = c->dbg[1] = c->dbg[2] = 0;
+  void report() {
+    c->stats.n_clusters = c->nclusters;
+    c->stats.t_prefilter_s = t_pf;
+    c->stats.t_align_s = t_al;
+    c->stats.t_consensus_s = t_cons;
+    c->stats.t_host_s = t_host;
+    if (c->pf_prof.p) report_pf_prof();
+    c->stats.t_total_s = now_s() - t0;
+    c->clustered = true;
+    if (c->tun.walk_dump && !c->wd.empty()) {
+      if (FILE* f = fopen(c->tun.walk_dump, "wb")) {
+        fwrite(c->wd.data(), 2, c->wd.size(), f);
+        fclose(f);
+      }
+      c->wd.clear();
+    }
+    if (c->tun.debug) report_debug();
+    c->dbg = DebugSums{};
+  }
+};
+
+// Cluster bin `bin` -- or, npk > 1, the pack of bins [bin, bin + npk) in one greedy order (each bin's queries in
+// its own sorted order, the bins one after another: bins never interact, so this is every bin's own vsearch run):
+// blocks then span bin boundaries and small bins share passes; the prefilter keeps only a query's own bin
+// (PrefilterArgs::qbin) and the results are split per bin.
+void cluster_all(umiclust_ctx* c, int32_t bin, bool multi_bin = false, int32_t npk = 1) {
+  c->rec_direct = g_live_ctx.load() > 1;
+  if (bin < 0 || npk < 1 || bin + npk >= (int32_t)c->bin_s.size())
+    c->fail(UMICLUST_EINVAL, "bins [%d, %d) out of range", bin, bin + npk);
+  ClusterRun r(c, bin, npk, multi_bin);
+  r.reset_bin();
+  r.plan_blocks();
+  r.layout_arena();
+  r.alloc_traceback();
+  r.run_pipeline();
+  r.drain();
+  r.trace_members();
+  r.number();
+  r.consensus();
+  r.store_outputs();
+  r.report();
 }
 
 // ---------------------------------------------------------------- load
@@ -2302,7 +2254,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
   const double t1 = now_s();
   const int32_t K = c->nclusters;
   const int width = p->fasta_width;
-  const io::ClusterView cv{K, c->ostart.data(), c->omemb.data(), c->perm.data()};
+  const io::ClusterView cv{K, c->num.ostart.data(), c->num.omemb.data(), c->perm.data()};
   // both writers build and write disjoint cluster ranges on io_threads() threads; the consout (one file: bound by its
   // page allocation or inode lock, 0.12 s of a config-2 bin on the GPU box) is written beside the cluster<N> files
   double t_cons = 0.0;
@@ -2367,7 +2319,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
     int32_t smin = 0, smax = 0;
     for (int32_t x = 0; x < c->n; x++) nt += c->hlen[x];
     for (int32_t k = 0; k < K; k++) {
-      const int32_t sz = c->ostart[k + 1] - c->ostart[k];
+      const int32_t sz = c->num.ostart[k + 1] - c->num.ostart[k];
       singles += sz == 1;
       smin = k ? std::min(smin, sz) : sz;
       smax = std::max(smax, sz);

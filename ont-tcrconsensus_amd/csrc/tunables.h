@@ -22,7 +22,7 @@ struct Tunables {
   // UMICLUST_RESOLVE_THREADS: host threads of resolve_pass (caller included); 0: 8 while this is the process's only
   // context (config 2: host resolve 0.22 -> 0.14 s per step, profiles/r03/resolve_threads_ab.json), 4 beside others
   int32_t resolve_threads = 0;
-  // UMICLUST_BLOCK; unset: a bin of n queries uses blocks of about n / block_div (>= block_min): a small bin's
+  // UMICLUST_BLOCK; unset: a bin of n queries uses blocks of about n / block_div (>= kBlockMin): a small bin's
   // window then holds fewer same-molecule peers (fewer speculative peer alignments and overflows)
   int32_t block_size = 8192, block_div = 16;
   // UMICLUST_MIXLEN=0: blocks end at every query-length change (one alignment launch per round); =1: a block spans

@@ -31,6 +31,7 @@ constexpr int kParts = 8;
 constexpr int kPartShift = 3;
 constexpr int kBins = kParts << 16;
 constexpr int kMaxBlock = 8192;                     // queries per greedy block
+constexpr int kSegLens = 32;                        // query lengths one greedy block may span
 constexpr int kPeerRegion = kMaxBlock / kParts;     // counter slots per part of a peer tile
 constexpr int kPeerTiles = 3;                       // blocks in a prefilter's peer window, at most
 constexpr int kDummy = kPeerTiles * kPeerRegion;

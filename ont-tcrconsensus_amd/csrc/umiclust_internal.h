@@ -67,7 +67,6 @@ constexpr int kPartCand = 64;  // candidates a (query-strand, part) passes to th
 // pass counters: [0..15] stats and pair counts, the postings partial sums, the overflowed-unit count
 constexpr int kUnitsSlot = 16 + kPostSpread * 32;
 // per-length pair counters of the three walk rounds (SegTab), kSegLens each
-constexpr int kSegLens = 32;  // query lengths one greedy block may span
 constexpr int kSegSlot = kUnitsSlot + 32;
 constexpr int kCountersLen = kSegSlot + 3 * kSegLens;
 constexpr int kPfWinBase = 128;   // k_pf_count: windows whose base list and start mask are tabulated (the rest: search)
