@@ -295,7 +295,62 @@ int64_t umiclust_region_split(umiclust_ctx *ctx, const char *bam_file, int32_t n
                               int64_t *counts, int64_t *reads_per_cluster, int32_t ncluster_cap,
                               uint8_t *region_detected, char *missing_name, int32_t missing_cap);
 
+/* ---- quality filtering (row f5) ---- */
+/* Replaces the `vsearch --fastq_filter` subprocess of vsearch_fastq_filtering
+ * (/root/reference/ont_tcr_consensus/preprocessing.py:104-159, argv :129-148; run once per library between
+ * dorado_trim and minimap2_ont_align, tcr_consensus.py:156-169).  vsearch runs it on one thread (:104); here the
+ * host threads index the mapped FASTQ in chunks and gather the quality bytes, the device sums each record's
+ * expected error in fixed point (ee_fx = sum of llrint(10^(-q/10) * 2^40), order-independent), and the host decides,
+ * recomputing in double exactly as vsearch states it whatever falls within a guard band of a threshold.  Policies
+ * O7a-O7f (record form, quality range, expected error, decision order, options, log) are in DESIGN.md §9a.
+ * The reference's own seqkit calls (:126-127, :156-157) are not part of this. */
+typedef struct umiclust_fastq_filter_params {
+  int32_t fastq_ascii;      /* --fastq_ascii: 33 (default) or 64 */
+  int32_t fastq_qmin;       /* --fastq_qmin (0) */
+  int32_t fastq_qmax;       /* --fastq_qmax (41; the reference passes 93, :136-137) */
+  int32_t fastq_minlen;     /* --fastq_minlen (1; the reference passes minimal_length, :140-141) */
+  int32_t fastq_maxlen;     /* --fastq_maxlen; -1 = no limit */
+  int32_t pad;
+  double fastq_maxee;       /* --fastq_maxee; < 0 = not given */
+  double fastq_maxee_rate;  /* --fastq_maxee_rate; < 0 = not given (the reference passes max_ee_rate_base, :138-139) */
+} umiclust_fastq_filter_params;
+
+typedef struct umiclust_fastq_filter_result {
+  int64_t n_input, n_kept, n_discarded, bases_in, bases_kept;
+  int64_t n_short, n_long, n_maxee, n_maxee_rate; /* discarded records by their first failing criterion (O7d order) */
+  int64_t n_host_rechecked; /* records inside the guard band, decided by the host's sequential double sum */
+  int64_t n_chunks;
+  double ee_in, ee_kept;    /* sums, in input order, of the records' ee_fx * 2^-40 */
+  double t_read_s;          /* indexing + gathering, summed over the chunks (overlaps the rest) */
+  double t_h2d_s;           /* host-to-device copies (HIP events), summed */
+  double t_kernel_s;        /* the kernel (HIP events), summed */
+  double t_write_s;         /* decision + writers, summed */
+  double t_total_s;         /* wall time of the call */
+} umiclust_fastq_filter_result;
+
+/* Parse the argv of preprocessing.py:129-148 (argv[0] may be "vsearch"); every option in the `--opt` and the `-opt`
+ * spelling.  Fills p and the paths (each buffer of pathcap bytes, may be NULL).  Needs no context and no device.
+ * Options outside O7e, a missing --fastq_filter or no output file -> UMICLUST_EINVAL. */
+int32_t umiclust_fastq_filter_params_from_argv(umiclust_fastq_filter_params *p, int32_t argc,
+                                               const char *const *argv, char *in_fastq, char *fastqout,
+                                               char *fastqout_discarded, char *log_path, int32_t pathcap);
+/* Filter in_fastq: kept records to fastqout, the others to fastqout_discarded, each as `@label\nSEQ\n+\nQUAL\n` in
+ * input order; a text log with vsearch's summary line.  Any output path may be NULL.  Returns the number of kept
+ * records.  A quality byte outside [fastq_qmin, fastq_qmax] is UMICLUST_EFORMAT naming the first such record; the
+ * records before it are written.  Malformed FASTQ is UMICLUST_EFORMAT, gzip input UMICLUST_EINVAL. */
+int64_t umiclust_fastq_filter(umiclust_ctx *ctx, const umiclust_fastq_filter_params *p, const char *in_fastq,
+                              const char *fastqout, const char *fastqout_discarded, const char *log_path,
+                              umiclust_fastq_filter_result *result);
+/* same, from the exact argv the reference builds */
+int64_t umiclust_fastq_filter_argv(umiclust_ctx *ctx, int32_t argc, const char *const *argv,
+                                   umiclust_fastq_filter_result *result);
+
 /* ---- kernel-level entry points (parity tests) ---- */
+/* The quality kernel alone: record i = quals[offsets[i] .. offsets[i+1]); ee_fx[i] = sum over its bytes b with
+ * 0 <= b - fastq_ascii <= 93 of llrint(10^(-(b - fastq_ascii)/10) * 2^40) (other bytes add 0), qlo[i] / qhi[i] = its
+ * smallest / largest raw byte (255 / 0 for an empty record).  Records of more than 2^22 bytes: UMICLUST_ERANGE. */
+int32_t umiclust_fastq_ee(umiclust_ctx *ctx, const uint8_t *quals, const int64_t *offsets, int64_t n,
+                          int32_t fastq_ascii, int64_t *ee_fx, uint8_t *qlo, uint8_t *qhi);
 /* Align npairs (query, target) pairs with the production alignment kernel.  Sequences are
  * ASCII; q/t record k at [q_off[k], q_off[k+1]).  Outputs per pair: score, matches,
  * internal alignment length (columns minus the terminal gap runs, vsearch align_trim) and,

@@ -51,6 +51,7 @@
 #include <zlib.h>
 
 #include "../../include/umiclust.h"
+#include "fastq_filter.h"
 #include "host_io.h"
 #include "plan.h"
 #include "resolve.h"
@@ -316,6 +317,16 @@ struct umiclust_ctx {
   DevBuf<uint8_t> ex_dlen;
   DevBuf<int32_t> ex_dout;
   DevBuf<ExtractPatterns> ex_dpat;
+  // quality filtering (f5): two pinned staging slots (one being gathered while the other is on the device), one set
+  // of device buffers, kept across calls
+  struct FqSlot {
+    PinBuf<uint8_t> q, lo, hi;
+    PinBuf<int64_t> offs, ee;
+  } fq_slot[2];
+  DevBuf<uint8_t> fq_dq, fq_dlo, fq_dhi;
+  DevBuf<int64_t> fq_doffs, fq_dee;
+  DevBuf<uint64_t> fq_dtab;
+  hipEvent_t fq_ev[3] = {};  // copy begin, kernel begin, kernel end
 
   // input (host copies kept only for the file path outputs).  A load holds one or more independent
   // region bins (umiclust_load_bins): bin b is input records [bin_in[b], bin_in[b+1]) and sorted
@@ -2502,6 +2513,8 @@ void umiclust_destroy(umiclust_ctx* c) {
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   for (hipEvent_t e : c->evb)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->fq_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : c->ix_events) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
@@ -3069,6 +3082,138 @@ int64_t umiclust_extract_umis_file(umiclust_ctx* c, const char* fastx_file, cons
     const int64_t tot = io::write_detected_umis(out_fasta, f, res.data(), ngood, adapter_length_3_end);
     if (ngood < n) c->fail(UMICLUST_EFORMAT, "Read strand not annotated!");
     return tot;
+  });
+}
+
+// ---------------------------------------------------------------- quality filtering (row f5)
+namespace {
+
+// The device behind fq::run_filter: a chunk's gathered qualities and offsets go up in two copies, k_fastq_ee runs,
+// the per-record sums and byte ranges come back.  reserve() runs on the parsing thread, run() on the caller's.
+struct FqDevice : fq::Backend {
+  umiclust_ctx* c;
+  explicit FqDevice(umiclust_ctx* ctx) : c(ctx) {}
+  bool reserve(int slot, size_t qual_bytes, size_t nrec, fq::Slot& s, std::string& err) override {
+    umiclust_ctx::FqSlot& h = c->fq_slot[slot];
+    auto grow = [](auto& b, size_t count) {  // with slack: chunks differ by a few records
+      return (b.p && count <= b.n) || b.ensure(count + count / 8 + 64) == hipSuccess;
+    };
+    if (hipSetDevice(c->dev) != hipSuccess || !grow(h.q, qual_bytes + 2 * fq::kPad) || !grow(h.offs, nrec + 1) ||
+        !grow(h.ee, nrec + 1) || !grow(h.lo, nrec + 1) || !grow(h.hi, nrec + 1)) {
+      (void)hipGetLastError();
+      err = "cannot allocate the pinned staging buffers";
+      return false;
+    }
+    s = fq::Slot{h.q.p, h.offs.p, h.ee.p, h.lo.p, h.hi.p};
+    return true;
+  }
+  bool run(int slot, size_t qual_bytes, int64_t nrec, const uint64_t* table, double* t_h2d_s, double* t_kernel_s,
+           std::string& err) override {
+    umiclust_ctx::FqSlot& h = c->fq_slot[slot];
+    const size_t n = (size_t)nrec;
+    auto grow = [](auto& b, size_t count) {
+      return (b.p && count <= b.n) || b.ensure(count + count / 8 + 64) == hipSuccess;
+    };
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t x) { return e == hipSuccess && (e = x) == hipSuccess; };
+    for (hipEvent_t& ev : c->fq_ev)
+      if (!ev) ok(hipEventCreate(&ev));
+    if (e == hipSuccess && !(grow(c->fq_dq, qual_bytes + 2 * fq::kPad) && grow(c->fq_doffs, n + 1) &&
+                             grow(c->fq_dee, n + 1) && grow(c->fq_dlo, n + 1) && grow(c->fq_dhi, n + 1) &&
+                             grow(c->fq_dtab, 256)))
+      e = hipErrorOutOfMemory;
+    hipStream_t st = c->st;
+    ok(hipMemcpyAsync(c->fq_dtab.p, table, 256 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    ok(hipEventRecord(c->fq_ev[0], st));
+    ok(hipMemcpyAsync(c->fq_dq.p, h.q.p, qual_bytes + 2 * fq::kPad, hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(c->fq_doffs.p, h.offs.p, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    ok(hipEventRecord(c->fq_ev[1], st));
+    if (e == hipSuccess)
+      ok(launch_fastq_ee(c->fq_dq.p + fq::kPad, c->fq_doffs.p, nrec, c->fq_dtab.p, c->fq_dee.p, c->fq_dlo.p,
+                         c->fq_dhi.p, st));
+    ok(hipEventRecord(c->fq_ev[2], st));
+    ok(hipMemcpyAsync(h.ee.p, c->fq_dee.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    ok(hipMemcpyAsync(h.lo.p, c->fq_dlo.p, n, hipMemcpyDeviceToHost, st));
+    ok(hipMemcpyAsync(h.hi.p, c->fq_dhi.p, n, hipMemcpyDeviceToHost, st));
+    ok(hipStreamSynchronize(st));
+    float ms0 = 0.f, ms1 = 0.f;
+    ok(hipEventElapsedTime(&ms0, c->fq_ev[0], c->fq_ev[1]));
+    ok(hipEventElapsedTime(&ms1, c->fq_ev[1], c->fq_ev[2]));
+    if (e != hipSuccess) {
+      err = std::string("fastq_filter device step: ") + hipGetErrorString(e);
+      return false;
+    }
+    *t_h2d_s = ms0 * 1e-3;
+    *t_kernel_s = ms1 * 1e-3;
+    return true;
+  }
+};
+
+int64_t fastq_filter_impl(umiclust_ctx* c, const umiclust_fastq_filter_params* p, const char* in_fastq,
+                          const char* fastqout, const char* fastqout_discarded, const char* log_path,
+                          umiclust_fastq_filter_result* result) {
+  if (!p || !in_fastq) c->fail(UMICLUST_EINVAL, "null params or input path");
+  FqDevice dev(c);
+  fq::Paths paths;
+  paths.in = in_fastq;
+  paths.out = fastqout;
+  paths.discarded = fastqout_discarded;
+  paths.log = log_path;
+  std::string err;
+  const int64_t rc = fq::run_filter(*p, paths, io_threads(), c->tun.fq_chunk, dev, result, err);
+  if (rc < 0) c->fail((int)rc, "%s", err.c_str());
+  return rc;
+}
+
+}  // namespace
+
+int64_t umiclust_fastq_filter(umiclust_ctx* c, const umiclust_fastq_filter_params* p, const char* in_fastq,
+                              const char* fastqout, const char* fastqout_discarded, const char* log_path,
+                              umiclust_fastq_filter_result* result) {
+  UC_GUARD(c, { return fastq_filter_impl(c, p, in_fastq, fastqout, fastqout_discarded, log_path, result); });
+}
+
+int64_t umiclust_fastq_filter_argv(umiclust_ctx* c, int32_t argc, const char* const* argv,
+                                   umiclust_fastq_filter_result* result) {
+  UC_GUARD(c, {
+    umiclust_fastq_filter_params p;
+    std::vector<char> in(4096), out(4096), dis(4096), lg(4096);
+    const int32_t rc =
+        umiclust_fastq_filter_params_from_argv(&p, argc, argv, in.data(), out.data(), dis.data(), lg.data(), 4096);
+    if (rc != UMICLUST_OK) c->fail(rc, "cannot parse the vsearch --fastq_filter argv");
+    return fastq_filter_impl(c, &p, in.data(), out[0] ? out.data() : nullptr, dis[0] ? dis.data() : nullptr,
+                             lg[0] ? lg.data() : nullptr, result);
+  });
+}
+
+int32_t umiclust_fastq_ee(umiclust_ctx* c, const uint8_t* quals, const int64_t* offsets, int64_t n,
+                          int32_t fastq_ascii, int64_t* ee_fx, uint8_t* qlo, uint8_t* qhi) {
+  UC_GUARD(c, {
+    if (n < 0 || (n > 0 && (!quals || !offsets || !ee_fx || !qlo || !qhi)) || (fastq_ascii != 33 && fastq_ascii != 64))
+      c->fail(UMICLUST_EINVAL, "bad argument");
+    if (n == 0) return UMICLUST_OK;
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t len = offsets[i + 1] - offsets[i];
+      if (len < 0) c->fail(UMICLUST_EINVAL, "offsets decrease at record %lld", (long long)i);
+      if (len > fq::kDevMaxLen) c->fail(UMICLUST_ERANGE, "record %lld is longer than 2^22 bytes", (long long)i);
+    }
+    fq::Tables tab;
+    fq::build_tables(fastq_ascii, 0, 93, tab);
+    FqDevice dev(c);
+    fq::Slot s;
+    std::string err;
+    const size_t bytes = (size_t)(offsets[n] - offsets[0]);
+    if (!dev.reserve(0, bytes, (size_t)n, s, err)) c->fail(UMICLUST_ENOMEM, "%s", err.c_str());
+    memset(s.qual, 0, (size_t)fq::kPad);
+    memcpy(s.qual + fq::kPad, quals + offsets[0], bytes);
+    memset(s.qual + fq::kPad + bytes, 0, (size_t)fq::kPad);
+    for (int64_t i = 0; i <= n; i++) s.offs[i] = offsets[i] - offsets[0];
+    double t0, t1;
+    if (!dev.run(0, bytes, n, tab.fx, &t0, &t1, err)) c->fail(UMICLUST_EDEVICE, "%s", err.c_str());
+    memcpy(ee_fx, s.ee, (size_t)n * sizeof(int64_t));
+    memcpy(qlo, s.qlo, (size_t)n);
+    memcpy(qhi, s.qhi, (size_t)n);
+    return UMICLUST_OK;
   });
 }
 

@@ -30,6 +30,9 @@ struct Tunables {
   int32_t mix_len = -1;  // -1: bins whose default block is below kMaxBlock (the bin has < 16 x kMaxBlock queries)
   int32_t pf1_lds = 10240;         // UMICLUST_PF1: one-wave counting units up to this LDS per unit (0: never)
   int32_t regrow = 8;              // UMICLUST_REGROW: clean shallow blocks before a halved block size doubles (0: never)
+  // UMICLUST_FQ_CHUNK: quality bytes per chunk of the fastq_filter drop-in (its memory use: two pinned staging buffers
+  // of this size plus one on the device; the file is never held whole), within [1 KiB, 2 GiB]
+  int64_t fq_chunk = 64ll << 20;
   bool pf_prof = false, pf_probe = false;  // UMICLUST_PFPROF, UMICLUST_PFPROBE: the counting kernel's two instruments
   int debug = 0;  // UMICLUST_DEBUG: 1 per-block lines and sequential in-order resolution; 2 the per-bin summary only
   // UMICLUST_WALK_DUMP=<file>: per sorted seqno of the bin, the alignments each strand's walk counted and the

@@ -256,6 +256,13 @@ constexpr int kExMaxSlot = 252;  // S <= this: 128 slots fit the LDS staging of 
 hipError_t launch_extract_win(const char* win, const uint8_t* wlen, int64_t n, int32_t S, int32_t a5, int32_t k,
                               const ExtractPatterns* P, int32_t* out, hipStream_t st);
 
+// ---- per-record fixed-point expected error of FASTQ qualities (fastq_filter.hip; row f5) ----
+// qual = the concatenated quality bytes, 16-byte aligned, with 16 readable bytes before and after them; record i =
+// [offs[i], offs[i + 1]); table[256] indexed by the raw byte.  ee[i] = sum of table[b], qlo[i] / qhi[i] = min / max b
+// (255 / 0 for an empty record).
+hipError_t launch_fastq_ee(const uint8_t* qual, const int64_t* offs, int64_t n, const uint64_t* table, int64_t* ee,
+                           uint8_t* qlo, uint8_t* qhi, hipStream_t st);
+
 // ---- region binning of BAM records (regionsplit.hip) ----
 enum : int8_t { kBamUnmapped = 0, kBamSecondary = 1, kBamShort = 2, kBamLong = 3, kBamKept = 4, kBamNoRegion = 5,
                 kBamNoCluster = 6 };

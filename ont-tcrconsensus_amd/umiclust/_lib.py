@@ -105,6 +105,23 @@ class ParseResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class FastqFilterParams(C.Structure):
+    """umiclust_fastq_filter_params (vsearch --fastq_filter options; negative maxlen / maxee / maxee_rate: not given)"""
+    _fields_ = [("fastq_ascii", C.c_int32), ("fastq_qmin", C.c_int32), ("fastq_qmax", C.c_int32),
+                ("fastq_minlen", C.c_int32), ("fastq_maxlen", C.c_int32), ("pad", C.c_int32),
+                ("fastq_maxee", C.c_double), ("fastq_maxee_rate", C.c_double)]
+
+
+class FastqFilterResult(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_input", "n_kept", "n_discarded", "bases_in", "bases_kept", "n_short",
+                                         "n_long", "n_maxee", "n_maxee_rate", "n_host_rechecked", "n_chunks")] + \
+               [(k, C.c_double) for k in ("ee_in", "ee_kept", "t_read_s", "t_h2d_s", "t_kernel_s", "t_write_s",
+                                          "t_total_s")]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/umiclust.h declares
 EXPORTS = [
     "umiclust_abi_version", "umiclust_params_init", "umiclust_params_from_argv", "umiclust_create",
@@ -112,7 +129,8 @@ EXPORTS = [
     "umiclust_load", "umiclust_stage", "umiclust_prepare", "umiclust_set_priority", "umiclust_cluster", "umiclust_fetch", "umiclust_load_bins", "umiclust_cluster_bin", "umiclust_cluster_pack",
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
-    "umiclust_timeline", "umiclust_wait_host",
+    "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
+    "umiclust_fastq_filter_argv", "umiclust_fastq_ee",
 ]
 OVERLAP_MAX_REGIONS = 4096
 ABI_VERSION = 9  # include/umiclust.h UMICLUST_ABI_VERSION: the struct layouts below
@@ -202,6 +220,17 @@ def lib() -> C.CDLL:
                                 P(C.c_uint16), C.c_int32, P(C.c_int32)]
     L.umiclust_timeline.restype = C.c_int32
     L.umiclust_timeline.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(C.c_double), P(C.c_int64)]
+    L.umiclust_fastq_filter_params_from_argv.restype = C.c_int32
+    L.umiclust_fastq_filter_params_from_argv.argtypes = [P(FastqFilterParams), C.c_int32, P(C.c_char_p), C.c_char_p,
+                                                         C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32]
+    L.umiclust_fastq_filter.restype = C.c_int64
+    L.umiclust_fastq_filter.argtypes = [C.c_void_p, P(FastqFilterParams), C.c_char_p, C.c_char_p, C.c_char_p,
+                                        C.c_char_p, P(FastqFilterResult)]
+    L.umiclust_fastq_filter_argv.restype = C.c_int64
+    L.umiclust_fastq_filter_argv.argtypes = [C.c_void_p, C.c_int32, P(C.c_char_p), P(FastqFilterResult)]
+    L.umiclust_fastq_ee.restype = C.c_int32
+    L.umiclust_fastq_ee.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int64, C.c_int32, P(C.c_int64),
+                                    P(C.c_uint8), P(C.c_uint8)]
     _lib = L
     return L
 
@@ -237,6 +266,27 @@ def params_from_argv(argv: list[str]) -> tuple[Params, dict]:
     if rc != 0:
         raise UmiclustError(rc, f"cannot parse argv {argv!r}")
     keys = ["in_fasta", "clusters_prefix", "consout", "log"]
+    return p, {k: (b.value.decode() or None) for k, b in zip(keys, bufs)}
+
+
+def fastq_filter_params(fastq_ascii: int = 33, fastq_qmin: int = 0, fastq_qmax: int = 41, fastq_minlen: int = 1,
+                        fastq_maxlen: int = -1, fastq_maxee: float = -1.0,
+                        fastq_maxee_rate: float = -1.0) -> FastqFilterParams:
+    """vsearch's defaults; a negative fastq_maxlen / fastq_maxee / fastq_maxee_rate means the option is not given."""
+    return FastqFilterParams(fastq_ascii, fastq_qmin, fastq_qmax, fastq_minlen, fastq_maxlen, 0, fastq_maxee,
+                             fastq_maxee_rate)
+
+
+def fastq_filter_params_from_argv(argv: list[str]) -> tuple[FastqFilterParams, dict]:
+    """umiclust_fastq_filter_params_from_argv: the decoded options and the in / fastqout / fastqout_discarded / log
+    paths (None where not given).  Needs no device."""
+    p = FastqFilterParams()
+    bufs = [C.create_string_buffer(4096) for _ in range(4)]
+    arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
+    rc = lib().umiclust_fastq_filter_params_from_argv(C.byref(p), len(argv), arr, *bufs, 4096)
+    if rc != 0:
+        raise UmiclustError(rc, f"cannot parse argv {argv!r}")
+    keys = ["in_fastq", "fastqout", "fastqout_discarded", "log"]
     return p, {k: (b.value.decode() or None) for k, b in zip(keys, bufs)}
 
 
@@ -431,6 +481,38 @@ class Context:
     def extract_umis_file(self, fastx: str, out_fasta: str, a5: int, a3: int, k: int, fwd: str, rev: str) -> int:
         return int(self._check(lib().umiclust_extract_umis_file(self._h, fastx.encode(), out_fasta.encode(), a5, a3, k,
                                                                 fwd.encode(), rev.encode()), "extract_umis_file"))
+
+    def fastq_filter(self, p: FastqFilterParams, in_fastq: str, fastqout: str | None,
+                     fastqout_discarded: str | None = None, log: str | None = None) -> dict:
+        """umiclust_fastq_filter (vsearch --fastq_filter): the result counters and phase times."""
+        r = FastqFilterResult()
+        enc = lambda x: os.fspath(x).encode() if x else None  # noqa: E731
+        k = lib().umiclust_fastq_filter(self._h, C.byref(p), enc(in_fastq), enc(fastqout), enc(fastqout_discarded),
+                                        enc(log), C.byref(r))
+        self._check(k, "fastq_filter")
+        return r.as_dict()
+
+    def fastq_filter_argv(self, argv: list[str]) -> dict:
+        """The same from the argv the reference builds (preprocessing.py:129-148)."""
+        r = FastqFilterResult()
+        arr = (C.c_char_p * len(argv))(*[str(a).encode() for a in argv])
+        k = lib().umiclust_fastq_filter_argv(self._h, len(argv), arr, C.byref(r))
+        self._check(k, "fastq_filter_argv")
+        return r.as_dict()
+
+    def fastq_ee(self, quals, fastq_ascii: int = 33) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """umiclust_fastq_ee: per record of `quals` (bytes objects) the fixed-point expected error (int64, 2^-40
+        units) and the smallest / largest raw byte (255 / 0 for an empty record)."""
+        buf, off = _pack(quals)
+        n = len(off) - 1
+        ee = np.zeros(max(n, 1), np.int64)
+        lo = np.zeros(max(n, 1), np.uint8)
+        hi = np.zeros(max(n, 1), np.uint8)
+        P = C.POINTER
+        self._check(lib().umiclust_fastq_ee(self._h, buf.ctypes.data, _i64(off), n, fastq_ascii, _i64(ee),
+                                            lo.ctypes.data_as(P(C.c_uint8)), hi.ctypes.data_as(P(C.c_uint8))),
+                    "fastq_ee")
+        return ee[:n], lo[:n], hi[:n]
 
     def region_split(self, bam_file: str, names, lengths, clusters, minov: float, s5: int, s3: int, out_dir: str):
         """umiclust_region_split: (counts[4], reads_per_cluster, region_detected); KeyError(name) as the
