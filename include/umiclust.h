@@ -368,6 +368,24 @@ int32_t umiclust_prep(umiclust_ctx *ctx, const umiclust_params *p, const char *s
                       const int64_t *offsets, int64_t n, char *masked, uint16_t *kmers,
                       int32_t kstride, int32_t *nk);
 
+/* The k-mer prefilter alone (k_pf_count, k_pf_full, k_pf_merge), launched as a whole pass of the pipeline launches
+ * it, on the sequences of the current single-bin load (umiclust_load / umiclust_prepare; sequences given longest
+ * first keep their input index as sorted seqno).  cent[ncent]: increasing sorted seqnos, appended to a fresh index
+ * append_step at a time (which decides the tiles the kernels read: delta only, base + delta after folds, sealed
+ * tiles).  The block is the queries [q0, q0 + nq), its peer window [w0, q0 + nq) with w0 = q0 - nprev * nq (nprev
+ * = 0..2 earlier blocks of nq queries); every centroid seqno is < w0.  Per query-strand qs = (q - q0) * both +
+ * strand (both = 2 under strand_both, else 1), what k_pf_merge wrote:
+ *   top_seqno[qs * 41 ...], top_count[qs * 41 ...], ntop[qs]   the top hits, best first
+ *   peer_id[qs * 128 ...] (seqno - w0), peer_count[qs * 128 ...], npeer[qs]   the in-window peers (255 = overflow)
+ * and info[0..4]: (query-strand, part) units the lean kernel handed to the full kernel, centroid tiles the pass
+ * read, counter segments, 1 if the one-wave layout of k_pf_count was launched, both.  Any output may be NULL.
+ * Not covered (each keeps its end-to-end tests): split passes, packs, policy O4 rounds, more than one counter
+ * segment.  nq > 8192, centroids in the window, a block spanning more than 32 lengths, policy_threads or several
+ * bins: UMICLUST_EINVAL; no load: UMICLUST_ESTATE.  Leaves the context loaded and not clustered. */
+int32_t umiclust_prefilter(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int32_t q0, int32_t nq,
+                           int32_t nprev, int32_t append_step, uint32_t *top_seqno, uint8_t *top_count,
+                           uint8_t *ntop, uint16_t *peer_id, uint8_t *peer_count, uint8_t *npeer, int64_t *info);
+
 /* ---- measurement (bench.py; no reference counterpart) ---- */
 /* Process-wide device timeline of the counting launches (kind 0) and the alignment chains
  * (kind 1) of every context: busy_s = the union of their HIP-event brackets since the last

@@ -449,6 +449,7 @@ struct umiclust_ctx {
   bool pt_pending = false;     // pt_ev recorded since the main stream last waited for it
   int32_t last_max_npeer = 0;
   DevBuf<uint32_t> d_probe;
+  PinBuf<uint32_t> h_pf_nunits;   // umiclust_prefilter: the lean kernel's overflowed-unit count (PfCapture)
   int32_t o4_T = 0;               // policy O4 (umiclust_params.policy_threads): rounds of o4_T queries; 0 = sequential
   int32_t b_hint = 1 << 30;       // block size the last bin ended with (peer overflows halve it)
   int al_level = 0;                 // the alignment stream: 0 prioritised (al_priority), -1 plain (set_priority -1)
@@ -816,15 +817,21 @@ void launch_pf_probe(umiclust_ctx* c, const PrefilterArgs& a, hipStream_t st) {
   c->hip(launch_prefilter(b, st, 3), "prefilter probe");
 }
 
+// What a whole pass's prefilter ran, for umiclust_prefilter (the kernel-level parity entry)
+struct PfCapture {
+  uint32_t* h_nunits = nullptr;  // pinned: *nunits between the lean kernel and the full kernel over its units
+  int32_t ntiles = 0, nseg = 0, one_wave = 0;  // centroid tiles read, counter segments, k_pf_count<0, 1> launched
+};
+
 // Enqueue the device pass of block [q0, q0+nq) against the index as it stands (centroids of the
 // blocks before the peer window), with no host synchronisation: the block's own peer tile (kept
 // for the next block's window), prefilter, the batch-of-8 walk over T_old (up to 4 align rounds),
 // the speculative alignment of every (query, earlier window query) pair passing the k-mer
 // threshold, and one download of the walk states, top lists, walked results and peer results.
 // The peer window is [prev->base, q0+nq) with prev = the previous block's tile, or the block
-// alone (prev == nullptr).
+// alone (prev == nullptr).  `cap` is null in production (PfCapture).
 void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* const* prevs, int nprev, Tile& own,
-                  int32_t region, bool lazy_peers = false, bool after_count = false) {
+                  int32_t region, bool lazy_peers = false, bool after_count = false, PfCapture* cap = nullptr) {
   const int32_t w0 = nprev > 0 ? prevs[0]->base : q0;
   const int both = c->both;
   const int32_t nqs = nq * both;
@@ -912,6 +919,12 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
     c->hip(hipEventRecord(P.ev_c[1], st), "event");
     c->stats.counter_cells += (int64_t)nq * c->both * a.ncent;
     if (c->tun.pf_probe) launch_pf_probe(c, a, st);
+    if (cap) {
+      c->hip(hipMemcpyAsync(cap->h_nunits, P.d_anunits.p, 4, hipMemcpyDeviceToHost, st), "d2h units");
+      cap->ntiles = nv;
+      cap->nseg = a.nseg;
+      cap->one_wave = prefilter_one_wave(a) ? 1 : 0;
+    }
     c->hip(launch_prefilter(a, st, 2), "prefilter");
     P.c_timed = true;
   } else {
@@ -1739,12 +1752,12 @@ struct ClusterRun {
     t.prebuilt = true;
   }
   // R(j) with the window's blocks from `first` (first = j - 1 in the steady state)
-  void second_half(int32_t j, int32_t first, bool after_count) {
+  void second_half(int32_t j, int32_t first, bool after_count, PfCapture* cap = nullptr) {
     const Tile* prevs[kPeerTiles];
     int np = 0;
     for (int32_t i = first; i < j; i++) prevs[np++] = &stile(i);
     enqueue_pass(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, prevs, np, stile(j), j % kPeerTiles, lazy,
-                 after_count);
+                 after_count, cap);
   }
   void count_half(int32_t j, int32_t first, int flag) {
     const Tile* wins[kPeerTiles];
@@ -2690,6 +2703,79 @@ int64_t umiclust_cluster_pack(umiclust_ctx* c, int32_t first, int32_t nbins, umi
     cluster_all(c, first, true, nbins);
     if (stats) *stats = c->stats;
     return c->nclusters;
+  });
+}
+
+// The prefilter of one block against a caller-chosen index and peer window, through the pipeline's own steps: the
+// bin's clean slate, arena and pass buffers (ClusterRun), append_centroids in steps of append_step, the window's peer
+// tiles (ClusterRun::build_peer) and one whole pass (ClusterRun::second_half -> enqueue_pass) whose top and peer lists
+// are copied out.  The walk and alignments the pass also enqueues run and are dropped.
+int32_t umiclust_prefilter(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
+                           int32_t append_step, uint32_t* top_seqno, uint8_t* top_count, uint8_t* ntop,
+                           uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer, int64_t* info) {
+  UC_GUARD(c, {
+    if (!c->loaded) c->fail(UMICLUST_ESTATE, "umiclust_prefilter before umiclust_load");
+    if (c->bin_s.size() != 2) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: the load holds several bins");
+    if (c->o4_T) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: batched rounds (policy O4) are not covered");
+    if ((!cent && ncent > 0) || ncent < 0 || nq < 1 || nq > kMaxBlock || nprev < 0 || nprev > kPeerTiles - 1 ||
+        append_step < 1 || q0 < 0 || (int64_t)q0 + nq > c->n || (int64_t)q0 - (int64_t)nprev * nq < 0)
+      c->fail(UMICLUST_EINVAL, "umiclust_prefilter: block, window or append step out of range");
+    if (ncent > kSegCentroids) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: more than one counter segment");
+    const int32_t w0 = q0 - nprev * nq;
+    for (int32_t i = 0; i < ncent; i++)
+      if (cent[i] < (i ? cent[i - 1] + 1 : 0) || cent[i] >= w0)
+        c->fail(UMICLUST_EINVAL, "umiclust_prefilter: centroid seqnos must increase and precede the window");
+    if (block_maxlen(c, q0, nq) - block_minlen(c, q0, nq) + 1 > kSegLens)
+      c->fail(UMICLUST_EINVAL, "umiclust_prefilter: block spans more than %d query lengths", kSegLens);
+    c->rec_direct = g_live_ctx.load() > 1;
+    c->clustered = false;
+    for (auto& bo : c->bout) bo.done = false;
+    ClusterRun r(c, 0, 1, false);
+    r.reset_bin();
+    r.plan_blocks();
+    r.layout_arena();
+    if (nq > c->pass_B)
+      for (Pass& P : c->pass) ensure_pass_buffers(c, P, nq);
+    c->ix_st = nullptr;
+    c->last_r_ev = nullptr;
+    for (Pass& P : c->pass) P.live = P.a_live = false;
+    std::vector<int32_t> step;
+    for (int32_t i = 0; i < ncent; i += (int32_t)step.size()) {
+      step.assign(cent + i, cent + std::min<int64_t>(ncent, (int64_t)i + append_step));
+      append_centroids(c, step);
+    }
+    // the window's blocks, oldest first, the block under test last; as ClusterRun::prime enqueues a first pass
+    r.plan.blocks.clear();
+    for (int32_t j = 0; j <= nprev; j++) r.plan.blocks.push_back({w0 + j * nq, nq});
+    for (int32_t j = 0; j <= nprev; j++) r.build_peer(j, false);
+    c->hip(c->h_pf_nunits.ensure(1), "pin");
+    c->h_pf_nunits.p[0] = 0;
+    PfCapture cap;
+    cap.h_nunits = c->h_pf_nunits.p;
+    r.second_half(nprev, 0, false, &cap);
+    Pass& P = c->pass[nprev % 2];
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    c->hip(hipStreamSynchronize(c->st_al), "sync");
+    c->hip(hipStreamSynchronize(c->st_b), "sync");
+    P.live = false;
+    const size_t nqs = (size_t)nq * c->both;
+    auto out = [&](void* dst, const void* src, size_t bytes) {
+      if (dst) c->hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "d2h prefilter lists");
+    };
+    out(top_seqno, P.d_top_seqno.p, nqs * kTopHits * 4);
+    out(top_count, P.d_top_count.p, nqs * kTopHits);
+    out(ntop, P.d_ntop.p, nqs);
+    out(peer_id, P.d_peer_id.p, nqs * kPeerCap * 2);
+    out(peer_count, P.d_peer_count.p, nqs * kPeerCap);
+    out(npeer, P.d_npeer.p, nqs);
+    if (info) {
+      info[0] = c->h_pf_nunits.p[0];
+      info[1] = cap.ntiles;
+      info[2] = cap.nseg;
+      info[3] = cap.one_wave;
+      info[4] = c->both;
+    }
+    return UMICLUST_OK;
   });
 }
 

@@ -1556,6 +1556,18 @@ hipError_t launch_kmer_xor(uint16_t* kmers, const uint8_t* nk, int32_t n, const 
   return hipGetLastError();
 }
 
+// LDS bytes of a lean counting unit (counters of one segment's centroids, then the list table at *tab_off)
+static size_t pf_count_lds(const PrefilterArgs& a, uint32_t* tab_off) {
+  const int segn = a.ncent < kSegCentroids ? a.ncent : kSegCentroids;
+  const size_t sub = (size_t)(((segn + kParts - 1) >> kPartShift) + 15) & ~(size_t)15;
+  *tab_off = (uint32_t)(kCentBase + sub);
+  return *tab_off + pf_count_table_bytes(a.nlist_cap) + 16;  // (+16: the table copy's last vector)
+}
+bool prefilter_one_wave(const PrefilterArgs& a) {
+  uint32_t tab_off;
+  return (int64_t)pf_count_lds(a, &tab_off) <= (int64_t)a.pf1_lds;
+}
+
 hipError_t launch_prefilter(const PrefilterArgs& a, hipStream_t st, int mode) {
   const int nqs = a.nq * a.both;
   if (nqs <= 0) return hipSuccess;
@@ -1582,11 +1594,11 @@ hipError_t launch_prefilter(const PrefilterArgs& a, hipStream_t st, int mode) {
   if (mode == 1 || mode == 3 || (mode == 0 && a.nseg <= 1)) {
     // lean counting (one counter segment)
     if (a.nseg > 1 || a.nlist_cap < 1 || a.nlist_cap > kPfLists) return hipErrorInvalidValue;
-    const uint32_t tab_off = (uint32_t)(kCentBase + sub);
-    size_t lds = tab_off + pf_count_table_bytes(a.nlist_cap) + 16;  // (+16: the table copy's last vector)
+    uint32_t tab_off;
+    const size_t lds = pf_count_lds(a, &tab_off);
     if (mode == 3)  // the timing probe: every phase but the count loop, into scratch outputs (UMICLUST_PFPROBE)
       hipLaunchKernelGGL((k_pf_count<2, kPfWaves>), dim3(nqs * kParts), dim3(kPfThreads), lds, st, a, tab_off);
-    else if ((int64_t)lds <= (int64_t)a.pf1_lds)  // small index: one-wave units
+    else if (prefilter_one_wave(a))  // small index: one-wave units
       hipLaunchKernelGGL((k_pf_count<0, 1>), dim3(nqs * kParts), dim3(64), lds, st, a, tab_off);
     else
       hipLaunchKernelGGL((k_pf_count<0, kPfWaves>), dim3(nqs * kParts), dim3(kPfThreads), lds, st, a, tab_off);

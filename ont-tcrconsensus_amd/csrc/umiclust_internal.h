@@ -144,6 +144,8 @@ struct PrefilterArgs {
 // kernel alone for multi-segment bins, then the merge); mode 1: only the lean counting (a split pass's
 // first half); mode 2: the full kernel over the units mode 1 left + the merge (its second half)
 hipError_t launch_prefilter(const PrefilterArgs& a, hipStream_t st, int mode = 0);
+// whether launch_prefilter's lean counting runs one-wave units (k_pf_count<0, 1>) for these arguments
+bool prefilter_one_wave(const PrefilterArgs& a);
 
 // alignment of pairs whose queries all have length qlen; pq = (query seqno << 1) | strand, pt = target seqno (plus strand)
 // out[outidx ? outidx[k] : k] = matches | internal << 8 | (score & 0xffff) << 16.

@@ -130,7 +130,7 @@ EXPORTS = [
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
-    "umiclust_fastq_filter_argv", "umiclust_fastq_ee",
+    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter",
 ]
 OVERLAP_MAX_REGIONS = 4096
 ABI_VERSION = 9  # include/umiclust.h UMICLUST_ABI_VERSION: the struct layouts below
@@ -231,6 +231,10 @@ def lib() -> C.CDLL:
     L.umiclust_fastq_ee.restype = C.c_int32
     L.umiclust_fastq_ee.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int64, C.c_int32, P(C.c_int64),
                                     P(C.c_uint8), P(C.c_uint8)]
+    L.umiclust_prefilter.restype = C.c_int32
+    L.umiclust_prefilter.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
+                                     P(C.c_uint8), P(C.c_int64)]
     _lib = L
     return L
 
@@ -558,6 +562,28 @@ class Context:
             raw = ops.tobytes()
             out["ops"] = [raw[k * stride:k * stride + nops[k]].decode() for k in range(n)]
         return out
+
+    def prefilter(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30) -> dict:
+        """umiclust_prefilter on the current load: the top and peer lists of the block [q0, q0 + nq) against the
+        centroids `cent` (increasing sorted seqnos before the window), per query-strand (rows), and info[0..3]."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        nqs = max(nq, 1) * 2
+        top_seqno = np.zeros((nqs, 41), np.uint32)
+        top_count = np.zeros((nqs, 41), np.uint8)
+        ntop = np.zeros(nqs, np.uint8)
+        peer_id = np.zeros((nqs, 128), np.uint16)
+        peer_count = np.zeros((nqs, 128), np.uint8)
+        npeer = np.zeros(nqs, np.uint8)
+        info = np.zeros(8, np.int64)
+        P = C.POINTER
+        u8 = lambda a: a.ctypes.data_as(P(C.c_uint8))  # noqa: E731
+        rc = lib().umiclust_prefilter(self._h, ce.ctypes.data_as(P(C.c_int32)), len(ce), q0, nq, nprev, append_step,
+                                      top_seqno.ctypes.data_as(P(C.c_uint32)), u8(top_count), u8(ntop),
+                                      peer_id.ctypes.data_as(P(C.c_uint16)), u8(peer_count), u8(npeer), _i64(info))
+        self._check(rc, "prefilter")
+        n = nq * int(info[4])
+        return dict(top_seqno=top_seqno[:n], top_count=top_count[:n], ntop=ntop[:n], peer_id=peer_id[:n],
+                    peer_count=peer_count[:n], npeer=npeer[:n], info=info[:4], both=int(info[4]))
 
     def prep(self, p: Params, seqs) -> dict:
         b, o = _pack(seqs)

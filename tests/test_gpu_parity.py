@@ -353,6 +353,24 @@ def test_edge_inputs(gpu_ctx):
         _cmp_cluster(g, o)
 
 
+@pytest.mark.parametrize("family", ["shared_core", "low_complexity"])
+def test_cluster_tied_candidates_vs_oracle(gpu_ctx, family):
+    """The pipeline on the prefilter's stress families (tests/prefilter_ref.py): 1,300 sequences sharing a core, so
+    every query has about a thousand candidates with heavily tied k-mer counts, and the low-complexity set, whose
+    in-window members have few or no unmasked 8-mers (thr = nk < 12 and thr = 0)."""
+    import prefilter_ref
+    seqs = prefilter_ref.shared_core(1300, 211) if family == "shared_core" else prefilter_ref.low_mix()
+    if family == "low_complexity":
+        assert sum(1 for s in seqs if 58 <= len(s) <= 68 and not prefilter_ref.kmer_set(s)) >= 5
+    gpu_ctx.load(_lib.params(1, 0.93, 58, 68), seqs)
+    st = gpu_ctx.cluster()
+    g = gpu_ctx.fetch()
+    o = orc.cluster(orc.params(1, 0.93, 58, 68), seqs)
+    _cmp_cluster(g, o)
+    assert st["n_alignments"] == o["stats"]["alignments"]
+    assert st["cells"] == o["stats"]["cells"]
+
+
 def _read_dir(d):
     return {fn: open(os.path.join(d, fn), "rb").read() for fn in sorted(os.listdir(d)) if not fn.endswith(".log")}
 
