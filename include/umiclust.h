@@ -361,6 +361,35 @@ int32_t umiclust_align_pairs(umiclust_ctx *ctx, const umiclust_params *p, const 
                              int64_t npairs, int32_t *score, int32_t *matches,
                              int32_t *internal_len, char *cigar_ops, int32_t ops_stride,
                              int32_t *ops_len);
+/* The member tracebacks and the consensus kernel (k_trace_wave, k_consensus) on clusters the caller names.  Records
+ * are ASCII, record i at seqs[offsets[i] .. offsets[i+1]), 1..UMICLUST_MAX_LEN long, taken as they are (no length
+ * filter, no sort, no DUST).  Cluster c is the member entries [cstart[c], cstart[c+1]) (cstart[0] = 0): member[x] is
+ * a record index, the cluster's first entry its centroid; member_strand[x] = 1 reads the member as its reverse
+ * complement (a centroid's is ignored).  A record may be in no cluster, never in two.
+ *   ops_in == NULL (traced): every other member is aligned to its centroid exactly as a clustering call does it --
+ *     queries of at most 64 nt in one launch, longer ones in a second, each sized by its longest query and by the
+ *     call's longest record, members renumbered into traceback slots -- with p's scoring, then k_consensus reads
+ *     those slots.  score / matches / internal_len[x] (each may be NULL) are the traceback's results as
+ *     umiclust_align_pairs reports them; 0 for centroids.
+ *   ops_in != NULL (given): member entry x's ops ('M' both, 'D' a member residue against a gap in the centroid, 'I' a
+ *     centroid residue against a gap in the member; alignment order) are ops_in[x * ops_stride ...], ops_in_len[x] of
+ *     them (centroid entries are not read).  They are checked on the host -- only M, D, I; at most 2 *
+ *     UMICLUST_MAX_LEN; #M + #I = the centroid's length; #M + #D = the member's -- and uploaded into the slots; only
+ *     k_consensus runs.  score / matches / internal_len are set to 0.
+ * ops_out (may be NULL): the ops k_consensus read, downloaded from the slots, at ops_out[x * ops_stride ...] with
+ * their count in ops_out_len[x] (0 for centroids).  ops_stride >= 2 * UMICLUST_MAX_LEN.  cons / cons_cap / cons_off
+ * as umiclust_fetch: cons_off[nclusters + 1], cluster c's consensus at cons[cons_off[c] .. cons_off[c+1]).
+ * UMICLUST_EINVAL: an empty cluster, a record index out of range, a record listed twice, a short ops_stride,
+ * invalid given ops (nothing is launched).  UMICLUST_ERANGE: a record length outside 1..UMICLUST_MAX_LEN, or a
+ * cluster whose alignment has more than 2048 columns (the per-member outputs are written, no consensus).  Works
+ * beside the context's load: a loaded or clustered context stays as it was.
+ * Not covered (each keeps its end-to-end tests): how clustering picks targets and strands, packs, policy O4. */
+int32_t umiclust_consensus(umiclust_ctx *ctx, const umiclust_params *p, const char *seqs, const int64_t *offsets,
+                           int64_t n, const int32_t *cstart, int32_t nclusters, const int32_t *member,
+                           const uint8_t *member_strand, const char *ops_in, const int32_t *ops_in_len,
+                           int32_t ops_stride, char *ops_out, int32_t *ops_out_len, int32_t *score,
+                           int32_t *matches, int32_t *internal_len, char *cons, int64_t cons_cap,
+                           int64_t *cons_off);
 /* DUST-mask and extract unique 8-mers of n sequences on the device (K1). masked receives the
  * case-masked sequences (same layout as seqs); kmers[i*kstride ...] the sorted unique k-mer
  * codes of strand s (0 '+', 1 '-') at kmers[(2*i+s)*kstride], counts in nk[2*i+s]. */

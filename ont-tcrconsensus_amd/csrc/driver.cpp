@@ -1442,6 +1442,81 @@ hipError_t main_stream_priority(umiclust_ctx* c, int level) {
   return hipSuccess;
 }
 
+// ---- member tracebacks and consensus: the launches ClusterRun and umiclust_consensus share.  Both work in the
+// context's traceback / consensus buffers, on sequences the caller names by `ds`.
+// the buffers for at most n members
+void ensure_traceback_buffers(umiclust_ctx* c, int32_t n) {
+  c->hip(c->h_mpq.ensure((size_t)std::max(n, 1)), "pin");
+  c->hip(c->h_mpt.ensure((size_t)std::max(n, 1)), "pin");
+  c->hip(c->t_mpq.ensure(n), "alloc");
+  c->hip(c->t_mpt.ensure(n), "alloc");
+  c->hip(c->t_mout.ensure(n), "alloc");
+  c->hip(c->t_ops.ensure((size_t)std::max(n, 1) * kOpsStride), "alloc");
+  c->hip(c->t_nops.ensure(n), "alloc");
+}
+
+// The two launches of a TracePlan (plan.h) whose pairs are in h_mpq / h_mpt: ops, op counts and results go to the
+// members' slots of t_ops / t_nops / t_mout.  maxl: the longest sequence any pair can hold.
+void launch_tracebacks(umiclust_ctx* c, const DevSeqs& ds, const Scoring& sc, const TracePlan& tp, int32_t maxl,
+                       hipStream_t stq) {
+  const int32_t x0 = tp.x0, nm1 = tp.x0 + tp.n1, nall = tp.n1 + tp.n2;
+  if (nall == 0) return;
+  c->hip(hipMemcpyAsync(c->t_mpq.p + x0, c->h_mpq.p + x0, (size_t)nall * 4, hipMemcpyHostToDevice, stq), "h2d");
+  c->hip(hipMemcpyAsync(c->t_mpt.p + x0, c->h_mpt.p + x0, (size_t)nall * 4, hipMemcpyHostToDevice, stq), "h2d");
+  c->hip(launch_traceback(ds, c->t_mpq.p + x0, c->t_mpt.p + x0, tp.n1, sc, c->t_ops.p + (size_t)x0 * kOpsStride,
+                          c->t_nops.p + x0, c->t_mout.p + x0, stq, maxl, tp.maxq1),
+         "traceback");
+  c->hip(launch_traceback(ds, c->t_mpq.p + nm1, c->t_mpt.p + nm1, tp.n2, sc, c->t_ops.p + (size_t)nm1 * kOpsStride,
+                          c->t_nops.p + nm1, c->t_mout.p + nm1, stq, maxl, tp.maxq2),
+         "traceback");
+}
+
+// the pinned consensus inputs of n members in K clusters, for the caller to fill: h_cstart[K + 1], and per member in
+// cluster order (centroid first) h_mseq (seqno), h_mops (traceback slot, a centroid's is not read), h_mstr (strand)
+void ensure_consensus_inputs(umiclust_ctx* c, int32_t n, int32_t K) {
+  c->hip(c->h_mseq.ensure((size_t)std::max(n, 1)), "pin");
+  c->hip(c->h_mops.ensure((size_t)std::max(n, 1)), "pin");
+  c->hip(c->h_mstr.ensure((size_t)std::max(n, 1)), "pin");
+  c->hip(c->h_cstart.ensure((size_t)K + 1), "pin");
+}
+
+constexpr const char* kConsOverMsg = "consensus: %d clusters exceed the MSA column budget";
+
+// Uploads those inputs, runs k_consensus on the main stream behind whatever wrote t_ops / t_nops (ev, if given, is
+// recorded behind the kernel), downloads the lengths into h_clen and the sequences into h_craw (kConsCap bytes per
+// cluster) and waits.  Returns the clusters whose MSA is wider than kMsaCols (their length is 0): the caller fails with
+// kConsOverMsg.
+int32_t run_consensus(umiclust_ctx* c, const DevSeqs& ds, int32_t n, int32_t K, hipEvent_t ev) {
+  c->hip(c->t_cstart.ensure((size_t)K + 1), "alloc");
+  c->hip(c->t_mseq.ensure(n), "alloc");
+  c->hip(c->t_mops.ensure(n), "alloc");
+  c->hip(c->t_mstrand.ensure(n), "alloc");
+  c->hip(c->t_cons.ensure((size_t)std::max(K, 1) * kConsCap), "alloc");
+  c->hip(c->t_conslen.ensure((size_t)std::max(K, 1)), "alloc");
+  c->hip(c->t_over.ensure(1), "alloc");
+  c->hip(hipMemsetAsync(c->t_over.p, 0, 4, c->st), "memset");
+  c->hip(hipMemcpyAsync(c->t_cstart.p, c->h_cstart.p, ((size_t)K + 1) * 4, hipMemcpyHostToDevice, c->st), "h2d");
+  if (n > 0) {
+    c->hip(hipMemcpyAsync(c->t_mseq.p, c->h_mseq.p, (size_t)n * 4, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(hipMemcpyAsync(c->t_mops.p, c->h_mops.p, (size_t)n * 4, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(hipMemcpyAsync(c->t_mstrand.p, c->h_mstr.p, (size_t)n, hipMemcpyHostToDevice, c->st), "h2d");
+  }
+  c->hip(launch_consensus(ds, c->t_cstart.p, K, c->t_mseq.p, c->t_mops.p, c->t_mstrand.p, c->t_ops.p, c->t_nops.p,
+                          c->t_cons.p, c->t_conslen.p, c->t_over.p, c->st),
+         "consensus");
+  if (ev) c->hip(hipEventRecord(ev, c->st), "event");
+  c->hip(c->h_clen.ensure((size_t)std::max(K, 1)), "pin");
+  c->hip(c->h_craw.ensure((size_t)std::max(K, 1) * kConsCap), "pin");
+  c->hip(c->h_over.ensure(1), "pin");
+  if (K > 0) {
+    c->hip(hipMemcpyAsync(c->h_clen.p, c->t_conslen.p, (size_t)K * 2, hipMemcpyDeviceToHost, c->st), "d2h");
+    c->hip(hipMemcpyAsync(c->h_craw.p, c->t_cons.p, (size_t)K * kConsCap, hipMemcpyDeviceToHost, c->st), "d2h");
+  }
+  c->hip(hipMemcpyAsync(c->h_over.p, c->t_over.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  return *c->h_over.p;
+}
+
 // One cluster_all call: what its steps share (per call, not part of the context).  Seqnos stay absolute everywhere.
 struct ClusterRun {
   umiclust_ctx* const c;
@@ -1557,15 +1632,9 @@ struct ClusterRun {
 
   void alloc_traceback() {
     c->t_opsidx.assign(n, -1);  // member -> its traceback slot
-    c->hip(c->h_mpq.ensure((size_t)std::max(n, 1)), "pin");
-    c->hip(c->h_mpt.ensure((size_t)std::max(n, 1)), "pin");
-    c->hip(c->t_mpq.ensure(n), "alloc");
-    c->hip(c->t_mpt.ensure(n), "alloc");
-    c->hip(c->t_mout.ensure(n), "alloc");
-    c->hip(c->t_ops.ensure((size_t)std::max(n, 1) * kOpsStride), "alloc");
-    c->hip(c->t_nops.ensure(n), "alloc");
+    ensure_traceback_buffers(c, n);
     ds = dev_seqs(c);
-    tw_maxl = s1 > s0 ? *std::max_element(c->hlen.begin() + s0, c->hlen.begin() + s1) : kMaxLen;
+    tw_maxl = traceback_maxl(c->hlen.data(), s0, s1);
   }
 
   // ---- the O4 round window
@@ -1844,30 +1913,10 @@ struct ClusterRun {
   // (Tracing the first blocks' members early on a least-priority stream while later blocks are clustered measured no
   // faster: round 4 cumask_early_ab/.)
   void tw_launch(int32_t lo, int32_t hi, hipStream_t stq) {
-    constexpr int tw_split = 64;
-    const int32_t x0 = tw_n;
-    int32_t x = x0, nm1 = 0, maxq1 = 0, maxq2 = 0;
-    for (int pass = 0; pass < 2; pass++) {
-      for (int32_t s = lo; s < hi; s++)
-        if (c->target[s] >= 0 && (((int)c->hlen[s] <= tw_split) == (pass == 0))) {
-          c->t_opsidx[s - s0] = x;
-          c->h_mpq.p[x] = ((uint32_t)s << 1) | c->strand[s];
-          c->h_mpt.p[x] = (uint32_t)c->target[s];
-          (pass ? maxq2 : maxq1) = std::max(pass ? maxq2 : maxq1, (int32_t)c->hlen[s]);
-          x++;
-        }
-      if (pass == 0) nm1 = x;
-    }
-    tw_n = x;
-    if (x == x0) return;
-    c->hip(hipMemcpyAsync(c->t_mpq.p + x0, c->h_mpq.p + x0, (size_t)(x - x0) * 4, hipMemcpyHostToDevice, stq), "h2d");
-    c->hip(hipMemcpyAsync(c->t_mpt.p + x0, c->h_mpt.p + x0, (size_t)(x - x0) * 4, hipMemcpyHostToDevice, stq), "h2d");
-    c->hip(launch_traceback(ds, c->t_mpq.p + x0, c->t_mpt.p + x0, nm1 - x0, c->sc, c->t_ops.p + (size_t)x0 * kOpsStride,
-                            c->t_nops.p + x0, c->t_mout.p + x0, stq, tw_maxl, maxq1),
-           "traceback");
-    c->hip(launch_traceback(ds, c->t_mpq.p + nm1, c->t_mpt.p + nm1, x - nm1, c->sc, c->t_ops.p + (size_t)nm1 * kOpsStride,
-                            c->t_nops.p + nm1, c->t_mout.p + nm1, stq, tw_maxl, maxq2),
-           "traceback");
+    const TracePlan tp = plan_traceback(c->hlen.data(), c->target.data(), c->strand.data(), lo, hi, tw_n,
+                                        c->t_opsidx.data() + (lo - s0), c->h_mpq.p, c->h_mpt.p);
+    tw_n += tp.n1 + tp.n2;
+    launch_tracebacks(c, ds, c->sc, tp, tw_maxl, stq);
   }
   // The tracebacks go first: their pairs (sorted seqno order) need only the targets, so the launch goes out
   // before the host numbers the clusters, which then overlaps the traceback (round 4: the numbering and the
@@ -1892,10 +1941,7 @@ struct ClusterRun {
   void consensus() {
     const int32_t K = c->nclusters;
     // consensus inputs in output-cluster order (pinned: the uploads are queued, not staged)
-    c->hip(c->h_mseq.ensure((size_t)std::max(n, 1)), "pin");
-    c->hip(c->h_mops.ensure((size_t)std::max(n, 1)), "pin");
-    c->hip(c->h_mstr.ensure((size_t)std::max(n, 1)), "pin");
-    c->hip(c->h_cstart.ensure((size_t)K + 1), "pin");
+    ensure_consensus_inputs(c, n, K);
     for (int32_t x = 0; x < n; x++) {
       const int32_t s = c->num.omemb[x];
       c->h_mseq.p[x] = s;
@@ -1903,40 +1949,13 @@ struct ClusterRun {
       c->h_mstr.p[x] = c->strand[s];
     }
     std::copy(c->num.ostart.begin(), c->num.ostart.end(), c->h_cstart.p);
-    c->hip(c->t_cstart.ensure((size_t)K + 1), "alloc");
-    c->hip(c->t_mseq.ensure(n), "alloc");
-    c->hip(c->t_mops.ensure(n), "alloc");
-    c->hip(c->t_mstrand.ensure(n), "alloc");
-    c->hip(c->t_cons.ensure((size_t)std::max(K, 1) * kConsCap), "alloc");
-    c->hip(c->t_conslen.ensure((size_t)std::max(K, 1)), "alloc");
-    c->hip(c->t_over.ensure(1), "alloc");
-    c->hip(hipMemsetAsync(c->t_over.p, 0, 4, c->st), "memset");
-    c->hip(hipMemcpyAsync(c->t_cstart.p, c->h_cstart.p, ((size_t)K + 1) * 4, hipMemcpyHostToDevice, c->st), "h2d");
-    if (n > 0) {
-      c->hip(hipMemcpyAsync(c->t_mseq.p, c->h_mseq.p, (size_t)n * 4, hipMemcpyHostToDevice, c->st), "h2d");
-      c->hip(hipMemcpyAsync(c->t_mops.p, c->h_mops.p, (size_t)n * 4, hipMemcpyHostToDevice, c->st), "h2d");
-      c->hip(hipMemcpyAsync(c->t_mstrand.p, c->h_mstr.p, (size_t)n, hipMemcpyHostToDevice, c->st), "h2d");
-    }
-    c->hip(launch_consensus(ds, c->t_cstart.p, K, c->t_mseq.p, c->t_mops.p, c->t_mstrand.p, c->t_ops.p, c->t_nops.p,
-                            c->t_cons.p, c->t_conslen.p, c->t_over.p, c->st),
-           "consensus");
-    c->hip(hipEventRecord(c->tev[1], c->st), "event");
-    c->hip(c->h_clen.ensure((size_t)std::max(K, 1)), "pin");
-    c->hip(c->h_craw.ensure((size_t)std::max(K, 1) * kConsCap), "pin");
-    c->hip(c->h_over.ensure(1), "pin");
+    const int32_t over = run_consensus(c, ds, n, K, c->tev[1]);
     const uint16_t* clen = c->h_clen.p;
     const char* craw = c->h_craw.p;
-    if (K > 0) {
-      c->hip(hipMemcpyAsync(c->h_clen.p, c->t_conslen.p, (size_t)K * 2, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipMemcpyAsync(c->h_craw.p, c->t_cons.p, (size_t)K * kConsCap, hipMemcpyDeviceToHost, c->st), "d2h");
-    }
-    c->hip(hipMemcpyAsync(c->h_over.p, c->t_over.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    const int32_t over = *c->h_over.p;
     float ms = 0;
     c->hip(hipEventElapsedTime(&ms, c->tev[0], c->tev[1]), "elapsed");
     t_cons = ms * 1e-3;
-    if (over) c->fail(UMICLUST_ERANGE, "consensus: %d clusters exceed the MSA column budget", over);
+    if (over) c->fail(UMICLUST_ERANGE, kConsOverMsg, over);
     c->cons_off.assign((size_t)K + 1, 0);
     for (int32_t k = 0; k < K; k++) c->cons_off[k + 1] = c->cons_off[k] + clen[k];
     c->cons.resize((size_t)c->cons_off[K]);
@@ -2895,6 +2914,157 @@ int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const ch
       if (matches) matches[k] = (int32_t)(res[k] & 0xffu);
       if (internal_len) internal_len[k] = (int32_t)((res[k] >> 8) & 0xffu);
       if (score) score[k] = (int32_t)(int16_t)(res[k] >> 16);
+    }
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_consensus(umiclust_ctx* c, const umiclust_params* p, const char* seqs, const int64_t* offsets,
+                           int64_t n, const int32_t* cstart, int32_t nclusters, const int32_t* member,
+                           const uint8_t* member_strand, const char* ops_in, const int32_t* ops_in_len,
+                           int32_t ops_stride, char* ops_out, int32_t* ops_out_len, int32_t* score, int32_t* matches,
+                           int32_t* internal_len, char* cons, int64_t cons_cap, int64_t* cons_off) {
+  UC_GUARD(c, {
+    if (!p || n < 0 || nclusters < 0 || (n > 0 && (!seqs || !offsets)) ||
+        (nclusters > 0 && (!cstart || !member || !member_strand)) || (ops_in && !ops_in_len) ||
+        (ops_out && !ops_out_len))
+      c->fail(UMICLUST_EINVAL, "null argument");
+    if (n > (1 << 30)) c->fail(UMICLUST_ERANGE, "too many records");
+    if ((ops_in || ops_out) && ops_stride < kOpsStride) c->fail(UMICLUST_EINVAL, "ops_stride < %d", kOpsStride);
+    umiclust_params pp = *p;
+    pp.minseqlength = 1;
+    pp.maxseqlength = kMaxLen;
+    validate(c, pp);
+    const Scoring sc = to_scoring(pp);
+    const int32_t ns = (int32_t)n, K = nclusters;
+    // the records: lengths, and offsets from the first record's byte
+    std::vector<uint8_t> hlen((size_t)ns);
+    std::vector<int64_t> off((size_t)ns + 1, 0);
+    for (int32_t i = 0; i < ns; i++) {
+      const int64_t L = offsets[i + 1] - offsets[i];
+      if (L < 1 || L > kMaxLen) c->fail(UMICLUST_ERANGE, "record %d: length %lld outside 1..%d", i, (long long)L, kMaxLen);
+      hlen[i] = (uint8_t)L;
+      off[i + 1] = offsets[i + 1] - offsets[0];
+    }
+    // the clusters: every record in at most one, its centroid first
+    if (K > 0 && cstart[0] != 0) c->fail(UMICLUST_EINVAL, "cstart[0] must be 0");
+    for (int32_t k = 0; k < K; k++)
+      if (cstart[k + 1] <= cstart[k]) c->fail(UMICLUST_EINVAL, "cluster %d is empty", k);
+    const int32_t nm = K > 0 ? cstart[K] : 0;  // member entries
+    std::vector<int32_t> target((size_t)ns, -1);
+    std::vector<uint8_t> strand((size_t)ns, 0), seen((size_t)ns, 0);
+    for (int32_t k = 0; k < K; k++)
+      for (int32_t x = cstart[k]; x < cstart[k + 1]; x++) {
+        const int32_t r = member[x];
+        if (r < 0 || r >= ns) c->fail(UMICLUST_EINVAL, "cluster %d: record %d out of range", k, r);
+        if (seen[r]) c->fail(UMICLUST_EINVAL, "record %d is listed twice", r);
+        seen[r] = 1;
+        if (x > cstart[k]) {
+          target[r] = member[cstart[k]];
+          strand[r] = member_strand[x] ? 1 : 0;
+        }
+      }
+    // given ops: the consensus kernel indexes its LDS by their counts, so nothing invalid may reach the device
+    if (ops_in)
+      for (int32_t k = 0; k < K; k++)
+        for (int32_t x = cstart[k] + 1; x < cstart[k + 1]; x++) {
+          const int32_t len = ops_in_len[x];
+          if (len < 0 || len > kOpsStride) c->fail(UMICLUST_EINVAL, "member %d: %d ops (at most %d)", x, len, kOpsStride);
+          const char* o = ops_in + (size_t)x * ops_stride;
+          int32_t nM = 0, nD = 0, nI = 0;
+          for (int32_t y = 0; y < len; y++) {
+            if (o[y] == 'M') nM++;
+            else if (o[y] == 'D') nD++;
+            else if (o[y] == 'I') nI++;
+            else c->fail(UMICLUST_EINVAL, "member %d: op %d is not one of M D I", x, y);
+          }
+          if (nM + nI != hlen[member[cstart[k]]] || nM + nD != hlen[member[x]])
+            c->fail(UMICLUST_EINVAL, "member %d: ops cover %d centroid and %d member residues, not %d and %d", x, nM + nI,
+                    nM + nD, (int)hlen[member[cstart[k]]], (int)hlen[member[x]]);
+        }
+    // the sequences' codes, beside whatever load the context holds
+    DevBuf<char> d_a;
+    DevBuf<int64_t> d_o;
+    DevBuf<uint32_t> d_codes, d_amb;
+    DevBuf<uint8_t> d_lens, d_nk;
+    DevBuf<uint16_t> d_km;
+    c->hip(d_a.ensure((size_t)off[ns] + 1), "alloc");
+    c->hip(d_o.ensure(off.size()), "alloc");
+    c->hip(d_codes.ensure((size_t)ns * 2 * kCodeWords + 1), "alloc");
+    c->hip(d_lens.ensure((size_t)ns + 1), "alloc");
+    c->hip(d_km.ensure((size_t)ns * 2 * kKmerStride + 1), "alloc");
+    c->hip(d_nk.ensure((size_t)ns * 2 + 1), "alloc");
+    c->hip(d_amb.ensure(2), "alloc");
+    if (off[ns] > 0) c->hip(hipMemcpy(d_a.p, seqs + offsets[0], (size_t)off[ns], hipMemcpyHostToDevice), "h2d");
+    c->hip(hipMemcpy(d_o.p, off.data(), off.size() * 8, hipMemcpyHostToDevice), "h2d");
+    c->hip(hipMemsetAsync(d_amb.p, 0, 8, c->st), "memset");
+    c->hip(launch_prep(d_a.p, d_o.p, nullptr, ns, 0, d_codes.p, d_lens.p, d_km.p, d_nk.p, nullptr, d_amb.p, c->st),
+           "prep");
+    const DevSeqs ds{d_codes.p, d_lens.p, d_km.p, d_nk.p};
+    // slots and launches as ClusterRun::tw_launch plans them, records standing for the sorted seqnos
+    ensure_traceback_buffers(c, ns);
+    std::vector<int32_t> slot((size_t)ns, -1);
+    const TracePlan tp = plan_traceback(hlen.data(), target.data(), strand.data(), 0, ns, 0, slot.data(), c->h_mpq.p,
+                                        c->h_mpt.p);
+    const int32_t nslots = tp.n1 + tp.n2;
+    std::vector<uint8_t> hops;
+    std::vector<uint16_t> hnops((size_t)nslots);
+    if (ops_in) {
+      hops.assign((size_t)nslots * kOpsStride, 0);
+      for (int32_t k = 0; k < K; k++)
+        for (int32_t x = cstart[k] + 1; x < cstart[k + 1]; x++) {
+          const int32_t sl = slot[member[x]], len = ops_in_len[x];
+          hnops[sl] = (uint16_t)len;
+          memcpy(hops.data() + (size_t)sl * kOpsStride + kOpsStride - len, ops_in + (size_t)x * ops_stride, (size_t)len);
+        }
+      if (nslots > 0) {
+        c->hip(hipMemcpyAsync(c->t_ops.p, hops.data(), hops.size(), hipMemcpyHostToDevice, c->st), "h2d");
+        c->hip(hipMemcpyAsync(c->t_nops.p, hnops.data(), (size_t)nslots * 2, hipMemcpyHostToDevice, c->st), "h2d");
+      }
+    } else {
+      launch_tracebacks(c, ds, sc, tp, traceback_maxl(hlen.data(), 0, ns), c->st);
+    }
+    ensure_consensus_inputs(c, nm, K);
+    for (int32_t x = 0; x < nm; x++) {
+      c->h_mseq.p[x] = member[x];
+      c->h_mops.p[x] = slot[member[x]];
+      c->h_mstr.p[x] = strand[member[x]];
+    }
+    std::copy(cstart, cstart + (K > 0 ? K + 1 : 0), c->h_cstart.p);
+    if (K == 0) c->h_cstart.p[0] = 0;
+    const int32_t over = run_consensus(c, ds, nm, K, nullptr);
+    // what the consensus kernel read, and what the traceback reported, per member entry
+    std::vector<uint32_t> res((size_t)nslots);
+    if (nslots > 0) {
+      hops.resize((size_t)nslots * kOpsStride);
+      c->hip(hipMemcpy(hops.data(), c->t_ops.p, hops.size(), hipMemcpyDeviceToHost), "d2h");
+      c->hip(hipMemcpy(hnops.data(), c->t_nops.p, (size_t)nslots * 2, hipMemcpyDeviceToHost), "d2h");
+      if (!ops_in) c->hip(hipMemcpy(res.data(), c->t_mout.p, (size_t)nslots * 4, hipMemcpyDeviceToHost), "d2h");
+    }
+    for (int32_t x = 0; x < nm; x++) {
+      const int32_t sl = slot[member[x]];  // -1: a centroid
+      const int32_t len = sl < 0 ? 0 : hnops[sl];
+      const uint32_t r = sl < 0 ? 0u : res[sl];
+      if (ops_out) {
+        if (len > kOpsStride) c->fail(UMICLUST_EDEVICE, "member %d: the traceback reported %d ops", x, len);
+        ops_out_len[x] = len;
+        if (len > 0) memcpy(ops_out + (size_t)x * ops_stride, hops.data() + (size_t)sl * kOpsStride + kOpsStride - len, (size_t)len);
+      }
+      if (matches) matches[x] = (int32_t)(r & 0xffu);
+      if (internal_len) internal_len[x] = (int32_t)((r >> 8) & 0xffu);
+      if (score) score[x] = (int32_t)(int16_t)(r >> 16);
+    }
+    if (over) c->fail(UMICLUST_ERANGE, kConsOverMsg, over);
+    int64_t total = 0;
+    for (int32_t k = 0; k < K; k++) {
+      if (cons_off) cons_off[k] = total;
+      total += c->h_clen.p[k];
+    }
+    if (cons_off) cons_off[K] = total;
+    if (cons) {
+      if (total > cons_cap) c->fail(UMICLUST_EINVAL, "consensus buffer too small");
+      for (int64_t k = 0, at = 0; k < K; at += c->h_clen.p[k], k++)
+        memcpy(cons + at, c->h_craw.p + (size_t)k * kConsCap, c->h_clen.p[k]);
     }
     return UMICLUST_OK;
   });

@@ -120,4 +120,29 @@ void number_clusters(int32_t s0, int32_t s1, const std::vector<int32_t>& cent, c
     for (int32_t s = s0; s < s1; s++) ocl[s] -= out.bin_k[hqbin[s] - bin0];
 }
 
+TracePlan plan_traceback(const uint8_t* hlen, const int32_t* target, const uint8_t* strand, int32_t lo, int32_t hi,
+                         int32_t x0, int32_t* slot, uint32_t* pq, uint32_t* pt) {
+  TracePlan tp;
+  tp.x0 = x0;
+  int32_t x = x0;
+  for (int pass = 0; pass < 2; pass++) {
+    int32_t& maxq = pass ? tp.maxq2 : tp.maxq1;
+    for (int32_t s = lo; s < hi; s++)
+      if (target[s] >= 0 && (((int32_t)hlen[s] <= kTwSplit) == (pass == 0))) {
+        slot[s - lo] = x;
+        pq[x] = ((uint32_t)s << 1) | strand[s];
+        pt[x] = (uint32_t)target[s];
+        maxq = std::max(maxq, (int32_t)hlen[s]);
+        x++;
+      }
+    if (pass == 0) tp.n1 = x - x0;
+  }
+  tp.n2 = x - x0 - tp.n1;
+  return tp;
+}
+
+int32_t traceback_maxl(const uint8_t* hlen, int32_t s0, int32_t s1) {
+  return s1 > s0 ? *std::max_element(hlen + s0, hlen + s1) : kMaxLen;
+}
+
 }  // namespace uc

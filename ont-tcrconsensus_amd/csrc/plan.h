@@ -1,6 +1,7 @@
 // plan.h -- the integer policy of one clustering call, host-only C++ (no HIP): how a bin's sorted queries are cut
 // into greedy blocks and re-cut after peer overflows and clean stretches (BlockPlan), and how the finished clusters
-// are numbered for the output (number_clusters).  driver.cpp's cluster_all drives both; tools/plan_check_main.cpp
+// are numbered for the output (number_clusters), and which member traceback goes to which launch and slot
+// (plan_traceback).  driver.cpp's cluster_all drives them (umiclust_consensus the last); tools/plan_check_main.cpp
 // (tests/test_plan_cpu.py) exercises them under ASan + UBSan without a GPU.
 #pragma once
 #include <cstdint>
@@ -71,5 +72,23 @@ struct ClusterNumbers {
 void number_clusters(int32_t s0, int32_t s1, const std::vector<int32_t>& cent, const int32_t* target,
                      bool clusterout_sort, const int32_t* hqbin, int32_t bin0, int32_t nbins, int32_t* cno, int32_t* ocl,
                      ClusterNumbers& out);
+
+// The member tracebacks of the sorted seqnos [lo, hi) once every target is final (k_trace_wave, one wave per member):
+// queries of at most kTwSplit nt go to a launch of their own, whose one-stripe direction store lets more waves share
+// a CU, the longer ones to a second launch.  Members take consecutive traceback slots from x0 on, the first launch's
+// before the second's, each in seqno order.
+constexpr int32_t kTwSplit = 64;
+struct TracePlan {
+  int32_t x0 = 0;                // the first launch's first slot
+  int32_t n1 = 0, n2 = 0;        // members of the first launch (slots [x0, x0 + n1)) and of the second (the next n2)
+  int32_t maxq1 = 0, maxq2 = 0;  // each launch's longest query (0: no member)
+};
+// hlen, target and strand are indexed by absolute seqno (target[s] < 0: a centroid, not traced).  slot[s - lo] = the
+// member's slot (a centroid's entry is left alone), pq[x] = (member seqno << 1) | strand and pt[x] = its centroid's
+// seqno for every slot x given out; pq and pt are indexed by slot and hold x0 + (members of [lo, hi)) entries.
+TracePlan plan_traceback(const uint8_t* hlen, const int32_t* target, const uint8_t* strand, int32_t lo, int32_t hi,
+                         int32_t x0, int32_t* slot, uint32_t* pq, uint32_t* pt);
+// the longest sequence among the seqnos [s0, s1), which sizes a traceback wave's LDS (kMaxLen for an empty range)
+int32_t traceback_maxl(const uint8_t* hlen, int32_t s0, int32_t s1);
 
 }  // namespace uc

@@ -130,7 +130,7 @@ EXPORTS = [
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
-    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter",
+    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus",
 ]
 OVERLAP_MAX_REGIONS = 4096
 ABI_VERSION = 9  # include/umiclust.h UMICLUST_ABI_VERSION: the struct layouts below
@@ -215,6 +215,11 @@ def lib() -> C.CDLL:
     L.umiclust_align_pairs.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64),
                                        C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_int32,
                                        P(C.c_int32)]
+    L.umiclust_consensus.restype = C.c_int32
+    L.umiclust_consensus.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64, P(C.c_int32), C.c_int32,
+                                     P(C.c_int32), P(C.c_uint8), C.c_void_p, P(C.c_int32), C.c_int32, C.c_void_p,
+                                     P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_int64,
+                                     P(C.c_int64)]
     L.umiclust_prep.restype = C.c_int32
     L.umiclust_prep.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64, C.c_void_p,
                                 P(C.c_uint16), C.c_int32, P(C.c_int32)]
@@ -562,6 +567,57 @@ class Context:
             raw = ops.tobytes()
             out["ops"] = [raw[k * stride:k * stride + nops[k]].decode() for k in range(n)]
         return out
+
+    def consensus(self, p: Params, seqs, clusters, strands=None, ops=None) -> dict:
+        """umiclust_consensus: the member tracebacks (ops None) or the given ops, then the consensus kernel.
+        clusters: lists of record indices into seqs, centroid first; strands: the same shape, 1 = the member is read
+        as its reverse complement (default: all 0); ops: the same shape, an 'M' / 'D' / 'I' string per member (the
+        centroid's entry is ignored).  Returns per cluster the consensus and, in the shape of clusters, the ops the
+        consensus kernel read (strings, '' for centroids) and the traceback's score, matches and internal_len."""
+        buf, off = _pack(seqs)
+        n = len(off) - 1
+        K = len(clusters)
+        cstart = np.zeros(K + 1, np.int32)
+        if K:
+            np.cumsum([len(m) for m in clusters], out=cstart[1:])
+        nm = int(cstart[-1])
+        member = np.array([r for m in clusters for r in m] + [0], np.int32)
+        mstr = np.zeros(nm + 1, np.uint8)
+        if strands is not None:
+            mstr[:nm] = [int(x) for m in strands for x in m]
+        stride = 2 * MAX_LEN
+        P = C.POINTER
+        i32 = lambda a: a.ctypes.data_as(P(C.c_int32))  # noqa: E731
+        ops_in = ops_in_len = None
+        if ops is not None:
+            flat = [(o if isinstance(o, bytes) else str(o or "").encode()) for m in ops for o in m]
+            width = max([stride] + [len(o) for o in flat])  # an over-long member is the library's to reject
+            ops_in = np.zeros((nm + 1) * width, np.uint8)
+            ops_in_len = np.zeros(nm + 1, np.int32)
+            for x, o in enumerate(flat):
+                ops_in[x * width:x * width + len(o)] = np.frombuffer(o, np.uint8)
+                ops_in_len[x] = len(o)
+        else:
+            width = stride
+        ops_out = np.zeros((nm + 1) * width, np.uint8)
+        ops_out_len = np.zeros(nm + 1, np.int32)
+        sc, mt, il = (np.zeros(nm + 1, np.int32) for _ in range(3))
+        cons = np.zeros(K * stride + 1, np.uint8)
+        coff = np.zeros(K + 1, np.int64)
+        rc = lib().umiclust_consensus(self._h, C.byref(p), buf.ctypes.data, _i64(off), n, i32(cstart), K, i32(member),
+                                      mstr.ctypes.data_as(P(C.c_uint8)),
+                                      None if ops_in is None else ops_in.ctypes.data,
+                                      None if ops_in is None else i32(ops_in_len), width, ops_out.ctypes.data,
+                                      i32(ops_out_len), i32(sc), i32(mt), i32(il), cons.ctypes.data, len(cons),
+                                      _i64(coff))
+        self._check(rc, "consensus")
+        raw, oraw = cons.tobytes(), ops_out.tobytes()
+
+        def shaped(a):
+            return [list(a[cstart[k]:cstart[k + 1]]) for k in range(K)]
+        out_ops = [oraw[x * width:x * width + ops_out_len[x]].decode() for x in range(nm)]
+        return dict(consensus=[raw[coff[k]:coff[k + 1]].decode() for k in range(K)], ops=shaped(out_ops),
+                    score=shaped(sc[:nm]), matches=shaped(mt[:nm]), internal_len=shaped(il[:nm]))
 
     def prefilter(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30) -> dict:
         """umiclust_prefilter on the current load: the top and peer lists of the block [q0, q0 + nq) against the

@@ -1,6 +1,7 @@
 """The HIP-free planning core (ont-tcrconsensus_amd/csrc/plan.cpp) under ASan + UBSan, without a GPU:
 tools/plan_check_main.cpp drives the block planner (how a bin's sorted queries are cut into greedy blocks, re-cut after
-a peer overflow and regrown after clean blocks) and the cluster numbering.  Expected plans of the smallest shapes that
+a peer overflow and regrown after clean blocks), the cluster numbering and the plan of the member tracebacks (which
+member goes to which launch and slot).  Expected plans of the smallest shapes that
 can go wrong are written out by hand; seeded random inputs check the invariants every plan must keep; the numbering
 is compared with a numpy restatement and, for one case, with the CPU oracle.  A sanitizer report fails the test."""
 import os
@@ -287,3 +288,87 @@ def test_number_vs_oracle(plan_check):
     got = parse_numbers(plan_check("number", [number_case([0, n], cent.tolist(), target.tolist(), 1, 0)])[0])
     assert np.array_equal(got["ocl"], cl)
     assert np.array_equal(got["omemb"][got["ostart"][:-1]], cent[np.argsort(got["rank_of"])])
+
+
+# ---- mode 3: trace ----
+def trace_case(hlen, target, strand=None, lo=0, hi=None, x0=0):
+    n = len(hlen)
+    return [lo, n if hi is None else hi, x0, n, *hlen, *target, *(strand or [0] * n)]
+
+
+def parse_trace(lines):
+    out = {}
+    for line in lines:
+        name, *vals = line.split()
+        out[name] = [int(v) for v in vals]
+    out["maxl"] = out["maxl"][0]
+    return out
+
+
+def trace(plan_check, **kw):
+    return parse_trace(plan_check("trace", [trace_case(**kw)])[0])
+
+
+def test_trace_split_at_64(plan_check):
+    # seqno 0 is the centroid; 64 is the last length of the first launch, 65 the first of the second; within a launch
+    # the members keep their seqno order, and the first launch's slots come first
+    got = trace(plan_check, hlen=[70, 65, 64, 112, 63, 1], target=[-1, 0, 0, 0, 0, 0], strand=[0, 1, 0, 0, 1, 1])
+    assert got["tp"] == [0, 3, 2, 64, 112]
+    assert got["slot"] == [-1, 3, 0, 4, 1, 2]
+    assert got["pq"] == [2 << 1, (4 << 1) | 1, (5 << 1) | 1, (1 << 1) | 1, 3 << 1]
+    assert got["pt"] == [0] * 5
+    assert got["maxl"] == 112
+
+
+def test_trace_empty_launches(plan_check):
+    # every member short: the second launch is empty and its maxq stays 0 (launch_traceback sends nothing); maxl is
+    # the centroid's length, longer than every query
+    got = trace(plan_check, hlen=[100, 40, 33], target=[-1, 0, 0])
+    assert (got["tp"], got["slot"], got["maxl"]) == ([0, 2, 0, 40, 0], [-1, 0, 1], 100)
+    # every member long: the first launch is empty
+    got = trace(plan_check, hlen=[66, 65, 65], target=[-1, 0, 0])
+    assert (got["tp"], got["slot"], got["maxl"]) == ([0, 0, 2, 0, 65], [-1, 0, 1], 66)
+    # centroids only, and no sequence at all (an empty range sizes the LDS for kMaxLen)
+    got = trace(plan_check, hlen=[66, 65], target=[-1, -1])
+    assert (got["tp"], got["slot"], got["pq"], got["maxl"]) == ([0, 0, 0, 0, 0], [-1, -1], [], 66)
+    got = trace(plan_check, hlen=[], target=[])
+    assert (got["tp"], got["slot"], got["maxl"]) == ([0, 0, 0, 0, 0], [], 112)
+
+
+def test_trace_range_and_slot_offset(plan_check):
+    # only the seqnos [lo, hi) are planned, slots count from x0, targets may lie outside the range, and maxl looks at
+    # the range alone
+    got = trace(plan_check, hlen=[112, 80, 70, 64, 30, 90], target=[-1, 0, -1, 2, 0, 0], strand=[0, 0, 0, 1, 0, 0],
+                lo=1, hi=5, x0=7)
+    assert got["tp"] == [7, 2, 1, 64, 80]
+    assert got["slot"] == [9, -1, 7, 8]
+    assert got["pq"] == [(3 << 1) | 1, 4 << 1, 1 << 1] and got["pt"] == [2, 0, 0]
+    assert got["maxl"] == 80
+
+
+def test_trace_random_plans_keep_the_invariants(plan_check):
+    rng = np.random.default_rng(4242)
+    cases, meta = [], []
+    for _ in range(200):
+        n = int(rng.integers(0, 60))
+        hlen = rng.integers(1, 113, n).tolist()
+        if n and rng.random() < 0.5:  # lengths at the split
+            hlen = [int(rng.choice([63, 64, 65, 112, 1])) for _ in range(n)]
+        target = [int(rng.integers(0, n)) if rng.random() < 0.7 else -1 for _ in range(n)]
+        strand = rng.integers(0, 2, n).tolist()
+        lo = int(rng.integers(0, n + 1))
+        hi = int(rng.integers(lo, n + 1))
+        x0 = int(rng.integers(0, 5))
+        cases.append(trace_case(hlen, target, strand, lo, hi, x0))
+        meta.append((hlen, target, strand, lo, hi, x0))
+    for lines, (hlen, target, strand, lo, hi, x0) in zip(plan_check("trace", cases), meta):
+        got = parse_trace(lines)
+        mem = [s for s in range(lo, hi) if target[s] >= 0]
+        short = [s for s in mem if hlen[s] <= 64]
+        long_ = [s for s in mem if hlen[s] > 64]
+        assert got["tp"] == [x0, len(short), len(long_), max([hlen[s] for s in short] + [0]),
+                             max([hlen[s] for s in long_] + [0])]
+        order = short + long_  # slot order
+        assert got["slot"] == [x0 + order.index(s) if s in order else -1 for s in range(lo, hi)]
+        assert got["pq"] == [(s << 1) | strand[s] for s in order] and got["pt"] == [target[s] for s in order]
+        assert got["maxl"] == (max(hlen[lo:hi]) if hi > lo else 112)

@@ -1,12 +1,15 @@
 // plan_check_main.cpp -- stand-alone driver of csrc/plan.cpp for the CPU suite (tests/test_plan_cpu.py), built with
 // ASan + UBSan.  Reads whitespace-separated integers from a file, any number of cases one after another, and prints
-// what the planner / the numbering makes of each.
+// what the planner / the numbering / the traceback plan makes of each.
 //
 //   plan_check blocks FILE    case: B mix o4_T regrow b_hint pack bin0 nbins  bin_s[nbins + 1]  hlen[bin_s[nbins]]
 //                                   nops  then per op:  0 k (overflowed)  |  1 k D max_npeer (resolved)  |  2 q (halve)
 //     prints "case", then after the start and after every op one line:  ret b_eff clean : first,n first,n ...
 //   plan_check number FILE    case: sort pack bin0 nbins  bin_s[nbins + 1]  K cent[K]  target[bin_s[0] .. bin_s[nbins])
 //     prints "case", then the lines cno, rank_of, ocl, ostart, omemb, bin_k
+//   plan_check trace FILE     case: lo hi x0 n  hlen[n]  target[n]  strand[n]   (seqnos 0 .. n - 1, lo <= hi <= n)
+//     prints "case", then the lines tp (x0 n1 n2 maxq1 maxq2), slot (of the seqnos [lo, hi); -1: left alone), pq and
+//     pt (of the slots given out), maxl (traceback_maxl of [lo, hi))
 // Seqnos are absolute: the bins cover [bin_s[0], bin_s[nbins]) and hlen starts at seqno 0.
 #include <cstdio>
 #include <cstdlib>
@@ -120,11 +123,36 @@ void number_case(Reader& in, long sort) {
   print_vec("bin_k", out.bin_k.data(), out.bin_k.size());
 }
 
+void trace_case(Reader& in, long lo_) {
+  const int32_t lo = (int32_t)lo_, hi = (int32_t)in.get(), x0 = (int32_t)in.get();
+  const size_t n = (size_t)in.get();
+  std::vector<uint8_t> hlen(n), strand(n);
+  std::vector<int32_t> target(n);
+  for (auto& x : hlen) x = (uint8_t)in.get();
+  for (auto& x : target) x = (int32_t)in.get();
+  for (auto& x : strand) x = (uint8_t)in.get();
+  size_t members = 0;
+  for (int32_t s = lo; s < hi; s++) members += target[s] >= 0;
+  // exactly as large as the plan may fill: a slot past the members, or an entry outside [lo, hi), is an ASan report
+  std::vector<int32_t> slot((size_t)(hi - lo), -1);
+  std::vector<uint32_t> pq((size_t)x0 + members, 0), pt((size_t)x0 + members, 0);
+  const TracePlan tp = plan_traceback(hlen.data(), target.data(), strand.data(), lo, hi, x0, slot.data(), pq.data(),
+                                      pt.data());
+  printf("case\n");
+  printf("tp %d %d %d %d %d\n", tp.x0, tp.n1, tp.n2, tp.maxq1, tp.maxq2);
+  print_vec("slot", slot.data(), slot.size());
+  printf("pq");
+  for (size_t x = (size_t)x0; x < pq.size(); x++) printf(" %u", pq[x]);
+  printf("\npt");
+  for (size_t x = (size_t)x0; x < pt.size(); x++) printf(" %u", pt[x]);
+  printf("\nmaxl %d\n", traceback_maxl(hlen.data(), lo, hi));
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 3 || (strcmp(argv[1], "blocks") && strcmp(argv[1], "number"))) {
-    fprintf(stderr, "usage: plan_check blocks|number FILE\n");
+  if (argc != 3 || (strcmp(argv[1], "blocks") && strcmp(argv[1], "number") && strcmp(argv[1], "trace"))) {
+    fprintf(stderr, "usage: plan_check blocks|number|trace FILE\n");
     return 2;
   }
   Reader in{fopen(argv[2], "r")};
@@ -136,7 +164,8 @@ int main(int argc, char** argv) {
   long first;
   while (in.next(first)) {
     if (blocks) blocks_case(in, first);
-    else number_case(in, first);
+    else if (!strcmp(argv[1], "number")) number_case(in, first);
+    else trace_case(in, first);
   }
   fclose(in.f);
   return 0;
