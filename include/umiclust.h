@@ -415,6 +415,62 @@ int32_t umiclust_prefilter(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent
                            int32_t nprev, int32_t append_step, uint32_t *top_seqno, uint8_t *top_count,
                            uint8_t *ntop, uint16_t *peer_id, uint8_t *peer_count, uint8_t *npeer, int64_t *info);
 
+/* One whole device pass (the prefilter, then k_walk, the per-length alignment rounds, k_peer_rel / k_peer_pairs and
+ * k_pack), launched as the pipeline launches it, with everything the host's resolve step reads of it.  cent, ncent,
+ * q0, nq, nprev, append_step, the load it needs, what it refuses and its error codes are umiclust_prefilter's.
+ * flags bit 0: lazy peers (no peer is aligned speculatively; the masks are zero, the records still written).
+ * flags bit 1 (needs nprev >= 1, else UMICLUST_EINVAL): the pass of the block before, [q0 - nq, q0), is enqueued
+ *   first on the other buffer set, with the window's earlier blocks as its peers and no resolve in between, as the
+ *   pipeline queues consecutive passes; the pass under test then reads that pass's final walk states to tell which
+ *   of its peers there are expected to become members.  Without bit 1 every other buffer set is marked unused
+ *   first, so that no pass an earlier umiclust_cluster left on the context is taken for the block before: the
+ *   outputs depend on the arguments alone.
+ * Outputs, each optional (NULL), per query-strand qs = (q - q0) * both + strand:
+ *   top_seqno .. npeer   the prefilter's lists, as umiclust_prefilter returns them
+ *   hostqs[nqs]          k_pack's outcomes (umiclust_pass_qs)
+ *   rec[rec_cap]         k_pack's record words; *rec_total = the words the pass used.  More than rec_cap:
+ *                        the first rec_cap words and every other output are filled, then UMICLUST_ERANGE
+ *   res[nqs * 160]       the raw result words (matches | internal_len << 8 | (score & 0xffff) << 16): walk candidate
+ *                        x of qs at [qs * 32 + x] (valid for x < e), peer y at [nqs * 32 + qs * 128 + y] (valid where
+ *                        its aligned bit is set)
+ *   aligned[nqs * 2]     bit y % 64 of word qs * 2 + y / 64: peer y was aligned in this pass
+ *   walk[nqs]            the final walk states (umiclust_pass_walk)
+ *   counters[16]         the pass counters as the host receives them: [8] peer pairs, [12..13] / [14..15] (64 bits
+ *                        each, low word first) the cells of the emitted walk pairs / of the peer pairs
+ *   info[0..4]           as umiclust_prefilter's
+ * Not covered (each keeps its end-to-end tests): split passes, packs, policy O4 rounds, more than one counter
+ * segment, and -- on a lone context -- blocks of more than 4096 queries, whose outcomes and records go through device
+ * buffers and copies instead of straight into host memory (the entry point returns them all the same).  Leaves the
+ * context loaded and not clustered.  (An added function: the struct layouts above and the ABI version are
+ * unchanged.) */
+typedef struct umiclust_pass_qs {
+  uint32_t best_t;     /* best accepted target seqno (0xffffffff: none) */
+  uint32_t cells;      /* sum of qlen * tlen over the walked candidates */
+  uint32_t rec;        /* word offset of the record, 0xffffffff if none */
+  uint16_t best_rank;  /* identity rank of the best accepted hit */
+  uint8_t w;           /* candidates walked */
+  uint8_t flags;       /* bit 0: an accepted hit; bit 1: peer list overflow */
+  uint16_t nrel;       /* relevant peers */
+  uint8_t e;           /* walk candidates with a result */
+  uint8_t npeer;       /* peers in the window (255: overflow) */
+  uint16_t rel[6];     /* window ids of the first 6 relevant peers, peer order */
+} umiclust_pass_qs;
+typedef struct umiclust_pass_walk {
+  uint64_t lastkey;    /* (127 - count) << 56 | length << 48 | seqno of the last walked candidate; 0 before any */
+  uint32_t best_t;
+  uint32_t cells;
+  uint16_t best_rank;
+  uint8_t w, done, acc, e;
+  uint8_t pad[2];
+} umiclust_pass_walk;
+#define UMICLUST_PASS_LAZY 1u
+#define UMICLUST_PASS_PREV 2u
+int32_t umiclust_pass(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
+                      int32_t append_step, uint32_t flags, uint32_t *top_seqno, uint8_t *top_count, uint8_t *ntop,
+                      uint16_t *peer_id, uint8_t *peer_count, uint8_t *npeer, umiclust_pass_qs *hostqs, uint32_t *rec,
+                      int64_t rec_cap, int64_t *rec_total, uint32_t *res, uint64_t *aligned, umiclust_pass_walk *walk,
+                      uint32_t *counters, int64_t *info);
+
 /* ---- measurement (bench.py; no reference counterpart) ---- */
 /* Process-wide device timeline of the counting launches (kind 0) and the alignment chains
  * (kind 1) of every context: busy_s = the union of their HIP-event brackets since the last

@@ -2725,75 +2725,167 @@ int64_t umiclust_cluster_pack(umiclust_ctx* c, int32_t first, int32_t nbins, umi
   });
 }
 
-// The prefilter of one block against a caller-chosen index and peer window, through the pipeline's own steps: the
-// bin's clean slate, arena and pass buffers (ClusterRun), append_centroids in steps of append_step, the window's peer
-// tiles (ClusterRun::build_peer) and one whole pass (ClusterRun::second_half -> enqueue_pass) whose top and peer lists
-// are copied out.  The walk and alignments the pass also enqueues run and are dropped.
+// What umiclust_prefilter and umiclust_pass share.  check_block_args: the refusals (`who` names the entry point).
+// stage_block: the pipeline's own steps up to the pass -- the bin's clean slate, arena and pass buffers (ClusterRun),
+// append_centroids in steps of append_step, and the window's peer tiles (ClusterRun::build_peer) with the window's
+// blocks as the plan, oldest first, the block under test last (index nprev), as ClusterRun::prime enqueues a first pass.
+static void check_block_args(umiclust_ctx* c, const char* who, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq,
+                      int32_t nprev, int32_t append_step) {
+  if (!c->loaded) c->fail(UMICLUST_ESTATE, "%s before umiclust_load", who);
+  if (c->bin_s.size() != 2) c->fail(UMICLUST_EINVAL, "%s: the load holds several bins", who);
+  if (c->o4_T) c->fail(UMICLUST_EINVAL, "%s: batched rounds (policy O4) are not covered", who);
+  if ((!cent && ncent > 0) || ncent < 0 || nq < 1 || nq > kMaxBlock || nprev < 0 || nprev > kPeerTiles - 1 ||
+      append_step < 1 || q0 < 0 || (int64_t)q0 + nq > c->n || (int64_t)q0 - (int64_t)nprev * nq < 0)
+    c->fail(UMICLUST_EINVAL, "%s: block, window or append step out of range", who);
+  if (ncent > kSegCentroids) c->fail(UMICLUST_EINVAL, "%s: more than one counter segment", who);
+  const int32_t w0 = q0 - nprev * nq;
+  for (int32_t i = 0; i < ncent; i++)
+    if (cent[i] < (i ? cent[i - 1] + 1 : 0) || cent[i] >= w0)
+      c->fail(UMICLUST_EINVAL, "%s: centroid seqnos must increase and precede the window", who);
+  if (block_maxlen(c, q0, nq) - block_minlen(c, q0, nq) + 1 > kSegLens)
+    c->fail(UMICLUST_EINVAL, "%s: block spans more than %d query lengths", who, kSegLens);
+}
+static void stage_block(umiclust_ctx* c, ClusterRun& r, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq,
+                 int32_t nprev, int32_t append_step) {
+  const int32_t w0 = q0 - nprev * nq;
+  c->rec_direct = g_live_ctx.load() > 1;
+  c->clustered = false;
+  for (auto& bo : c->bout) bo.done = false;
+  r.reset_bin();
+  r.plan_blocks();
+  r.layout_arena();
+  if (nq > c->pass_B)
+    for (Pass& P : c->pass) ensure_pass_buffers(c, P, nq);
+  c->ix_st = nullptr;
+  c->last_r_ev = nullptr;
+  for (Pass& P : c->pass) P.live = P.a_live = false;
+  std::vector<int32_t> step;
+  for (int32_t i = 0; i < ncent; i += (int32_t)step.size()) {
+    step.assign(cent + i, cent + std::min<int64_t>(ncent, (int64_t)i + append_step));
+    append_centroids(c, step);
+  }
+  r.plan.blocks.clear();
+  for (int32_t j = 0; j <= nprev; j++) r.plan.blocks.push_back({w0 + j * nq, nq});
+  for (int32_t j = 0; j <= nprev; j++) r.build_peer(j, false);
+  c->hip(c->h_pf_nunits.ensure(1), "pin");
+  c->h_pf_nunits.p[0] = 0;
+}
+static void sync_streams(umiclust_ctx* c) {
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  c->hip(hipStreamSynchronize(c->st_al), "sync");
+  c->hip(hipStreamSynchronize(c->st_b), "sync");
+}
+// the prefilter's lists of pass P and info[0..4], copied out
+static void fetch_lists(umiclust_ctx* c, const Pass& P, const PfCapture& cap, size_t nqs, uint32_t* top_seqno,
+                 uint8_t* top_count, uint8_t* ntop, uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer,
+                 int64_t* info) {
+  auto out = [&](void* dst, const void* src, size_t bytes) {
+    if (dst) c->hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "d2h prefilter lists");
+  };
+  out(top_seqno, P.d_top_seqno.p, nqs * kTopHits * 4);
+  out(top_count, P.d_top_count.p, nqs * kTopHits);
+  out(ntop, P.d_ntop.p, nqs);
+  out(peer_id, P.d_peer_id.p, nqs * kPeerCap * 2);
+  out(peer_count, P.d_peer_count.p, nqs * kPeerCap);
+  out(npeer, P.d_npeer.p, nqs);
+  if (info) {
+    info[0] = c->h_pf_nunits.p[0];
+    info[1] = cap.ntiles;
+    info[2] = cap.nseg;
+    info[3] = cap.one_wave;
+    info[4] = c->both;
+  }
+}
+
+// The prefilter of one block against a caller-chosen index and peer window, through the pipeline's own steps
+// (stage_block) and one whole pass (ClusterRun::second_half -> enqueue_pass) whose top and peer lists are copied out.
+// The walk and alignments the pass also enqueues run and are dropped.
 int32_t umiclust_prefilter(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
                            int32_t append_step, uint32_t* top_seqno, uint8_t* top_count, uint8_t* ntop,
                            uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer, int64_t* info) {
   UC_GUARD(c, {
-    if (!c->loaded) c->fail(UMICLUST_ESTATE, "umiclust_prefilter before umiclust_load");
-    if (c->bin_s.size() != 2) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: the load holds several bins");
-    if (c->o4_T) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: batched rounds (policy O4) are not covered");
-    if ((!cent && ncent > 0) || ncent < 0 || nq < 1 || nq > kMaxBlock || nprev < 0 || nprev > kPeerTiles - 1 ||
-        append_step < 1 || q0 < 0 || (int64_t)q0 + nq > c->n || (int64_t)q0 - (int64_t)nprev * nq < 0)
-      c->fail(UMICLUST_EINVAL, "umiclust_prefilter: block, window or append step out of range");
-    if (ncent > kSegCentroids) c->fail(UMICLUST_EINVAL, "umiclust_prefilter: more than one counter segment");
-    const int32_t w0 = q0 - nprev * nq;
-    for (int32_t i = 0; i < ncent; i++)
-      if (cent[i] < (i ? cent[i - 1] + 1 : 0) || cent[i] >= w0)
-        c->fail(UMICLUST_EINVAL, "umiclust_prefilter: centroid seqnos must increase and precede the window");
-    if (block_maxlen(c, q0, nq) - block_minlen(c, q0, nq) + 1 > kSegLens)
-      c->fail(UMICLUST_EINVAL, "umiclust_prefilter: block spans more than %d query lengths", kSegLens);
-    c->rec_direct = g_live_ctx.load() > 1;
-    c->clustered = false;
-    for (auto& bo : c->bout) bo.done = false;
+    check_block_args(c, "umiclust_prefilter", cent, ncent, q0, nq, nprev, append_step);
     ClusterRun r(c, 0, 1, false);
-    r.reset_bin();
-    r.plan_blocks();
-    r.layout_arena();
-    if (nq > c->pass_B)
-      for (Pass& P : c->pass) ensure_pass_buffers(c, P, nq);
-    c->ix_st = nullptr;
-    c->last_r_ev = nullptr;
-    for (Pass& P : c->pass) P.live = P.a_live = false;
-    std::vector<int32_t> step;
-    for (int32_t i = 0; i < ncent; i += (int32_t)step.size()) {
-      step.assign(cent + i, cent + std::min<int64_t>(ncent, (int64_t)i + append_step));
-      append_centroids(c, step);
-    }
-    // the window's blocks, oldest first, the block under test last; as ClusterRun::prime enqueues a first pass
-    r.plan.blocks.clear();
-    for (int32_t j = 0; j <= nprev; j++) r.plan.blocks.push_back({w0 + j * nq, nq});
-    for (int32_t j = 0; j <= nprev; j++) r.build_peer(j, false);
-    c->hip(c->h_pf_nunits.ensure(1), "pin");
-    c->h_pf_nunits.p[0] = 0;
+    stage_block(c, r, cent, ncent, q0, nq, nprev, append_step);
     PfCapture cap;
     cap.h_nunits = c->h_pf_nunits.p;
     r.second_half(nprev, 0, false, &cap);
     Pass& P = c->pass[nprev % 2];
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    c->hip(hipStreamSynchronize(c->st_al), "sync");
-    c->hip(hipStreamSynchronize(c->st_b), "sync");
+    sync_streams(c);
     P.live = false;
-    const size_t nqs = (size_t)nq * c->both;
-    auto out = [&](void* dst, const void* src, size_t bytes) {
-      if (dst) c->hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "d2h prefilter lists");
-    };
-    out(top_seqno, P.d_top_seqno.p, nqs * kTopHits * 4);
-    out(top_count, P.d_top_count.p, nqs * kTopHits);
-    out(ntop, P.d_ntop.p, nqs);
-    out(peer_id, P.d_peer_id.p, nqs * kPeerCap * 2);
-    out(peer_count, P.d_peer_count.p, nqs * kPeerCap);
-    out(npeer, P.d_npeer.p, nqs);
-    if (info) {
-      info[0] = c->h_pf_nunits.p[0];
-      info[1] = cap.ntiles;
-      info[2] = cap.nseg;
-      info[3] = cap.one_wave;
-      info[4] = c->both;
+    fetch_lists(c, P, cap, (size_t)nq * c->both, top_seqno, top_count, ntop, peer_id, peer_count, npeer, info);
+    return UMICLUST_OK;
+  });
+}
+
+// The same pass with everything the host's resolve step reads of it copied out (the walk, the peer pairs and k_pack
+// against tests/pass_ref.py).  With UMICLUST_PASS_PREV the pass of the block before is queued first on the other
+// buffer set, unresolved, as ClusterRun's pipelines queue consecutive passes; without it the other buffer sets are
+// marked unused, so enqueue_pass's search for the block before (Q.q0 + Q.nq == q0) finds nothing an earlier
+// clustering left behind.
+static_assert(sizeof(umiclust_pass_qs) == sizeof(HostQs) && offsetof(umiclust_pass_qs, rel) == offsetof(HostQs, rel) &&
+                  offsetof(umiclust_pass_qs, nrel) == offsetof(HostQs, nrel) &&
+                  offsetof(umiclust_pass_qs, npeer) == offsetof(HostQs, npeer),
+              "umiclust_pass_qs mirrors HostQs");
+static_assert(sizeof(umiclust_pass_walk) == sizeof(WalkState) &&
+                  offsetof(umiclust_pass_walk, best_rank) == offsetof(WalkState, best_rank) &&
+                  offsetof(umiclust_pass_walk, e) == offsetof(WalkState, e),
+              "umiclust_pass_walk mirrors WalkState");
+int32_t umiclust_pass(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
+                      int32_t append_step, uint32_t flags, uint32_t* top_seqno, uint8_t* top_count, uint8_t* ntop,
+                      uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer, umiclust_pass_qs* hostqs, uint32_t* rec,
+                      int64_t rec_cap, int64_t* rec_total, uint32_t* res, uint64_t* aligned, umiclust_pass_walk* walk,
+                      uint32_t* counters, int64_t* info) {
+  UC_GUARD(c, {
+    check_block_args(c, "umiclust_pass", cent, ncent, q0, nq, nprev, append_step);
+    if (flags & ~(UMICLUST_PASS_LAZY | UMICLUST_PASS_PREV)) c->fail(UMICLUST_EINVAL, "umiclust_pass: unknown flag");
+    if ((flags & UMICLUST_PASS_PREV) && nprev < 1)
+      c->fail(UMICLUST_EINVAL, "umiclust_pass: the previous block's pass needs nprev >= 1");
+    if (rec_cap < 0) c->fail(UMICLUST_EINVAL, "umiclust_pass: record buffer");
+    ClusterRun r(c, 0, 1, false);
+    // The set-up re-plans the bin, after which every buffer set zeroes its counters with a memset (ensure_pass_buffers).
+    // A set whose last k_pack re-zeroed them, and whose counters were not reallocated, keeps that knowledge here: its
+    // next pass takes the no-memset path, as every pass after a bin's first ones does in a clustering call (every
+    // stream is drained first, so the counters are as that k_pack left them).
+    const uint32_t* ctr_p[kPeerTiles];
+    bool ctr_z[kPeerTiles];
+    for (int i = 0; i < kPeerTiles; i++) {
+      ctr_p[i] = c->pass[i].d_counters.p;
+      ctr_z[i] = c->pass[i].ctr_zeroed;
     }
+    stage_block(c, r, cent, ncent, q0, nq, nprev, append_step);
+    sync_streams(c);
+    for (int i = 0; i < kPeerTiles; i++)
+      if (ctr_p[i] && c->pass[i].d_counters.p == ctr_p[i]) c->pass[i].ctr_zeroed = ctr_z[i];
+    r.lazy = (flags & UMICLUST_PASS_LAZY) != 0;
+    Pass& P = c->pass[nprev % 2];
+    for (Pass& Q : c->pass)
+      if (&Q != &P) Q.nq = 0;
+    if (flags & UMICLUST_PASS_PREV) r.second_half(nprev - 1, 0, false);
+    PfCapture cap;
+    cap.h_nunits = c->h_pf_nunits.p;
+    r.second_half(nprev, 0, false, &cap);
+    sync_streams(c);
+    for (Pass& Q : c->pass) Q.live = false;
+    const size_t nqs = (size_t)nq * c->both;
+    fetch_lists(c, P, cap, nqs, top_seqno, top_count, ntop, peer_id, peer_count, npeer, info);
+    auto out = [&](void* dst, const void* src, size_t bytes) {
+      if (dst && bytes) c->hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "d2h pass");
+    };
+    if (hostqs) memcpy(hostqs, P.h_hq.p, nqs * sizeof(HostQs));  // pinned: written by k_pack or copied by the pass
+    const int64_t total = *P.h_reccount.p;
+    if (rec_total) *rec_total = total;
+    if (rec) {
+      const size_t nw = (size_t)std::min<int64_t>(total, rec_cap);
+      if (P.rec_direct) memcpy(rec, P.h_rec.p, nw * 4);
+      else out(rec, P.d_rec.p, nw * 4);
+    }
+    out(res, P.d_res.p, nqs * (kWalk + kPeerCap) * 4);
+    out(aligned, P.d_paligned.p, nqs * (kPeerCap / 64) * 8);
+    out(walk, P.d_ws.p, nqs * sizeof(WalkState));
+    if (counters) memcpy(counters, P.h_counters.p, 16 * 4);
+    if (rec && total > rec_cap) c->fail(UMICLUST_ERANGE, "umiclust_pass: %lld record words, room for %lld",
+                                         (long long)total, (long long)rec_cap);
     return UMICLUST_OK;
   });
 }

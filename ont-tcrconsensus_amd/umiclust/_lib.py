@@ -130,9 +130,15 @@ EXPORTS = [
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
-    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus",
+    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
 ]
 OVERLAP_MAX_REGIONS = 4096
+# umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
+PASS_QS = np.dtype([("best_t", "<u4"), ("cells", "<u4"), ("rec", "<u4"), ("best_rank", "<u2"), ("w", "u1"),
+                    ("flags", "u1"), ("nrel", "<u2"), ("e", "u1"), ("npeer", "u1"), ("rel", "<u2", (6,))])
+PASS_WALK = np.dtype([("lastkey", "<u8"), ("best_t", "<u4"), ("cells", "<u4"), ("best_rank", "<u2"), ("w", "u1"),
+                      ("done", "u1"), ("acc", "u1"), ("e", "u1"), ("pad", "u1", (2,))])
+PASS_REC_WORDS = 1 + 2 * 32 + 8 + 2 * 128
 ABI_VERSION = 9  # include/umiclust.h UMICLUST_ABI_VERSION: the struct layouts below
 
 _lib = None
@@ -240,6 +246,11 @@ def lib() -> C.CDLL:
     L.umiclust_prefilter.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
                                      P(C.c_uint8), P(C.c_int64)]
+    L.umiclust_pass.restype = C.c_int32
+    L.umiclust_pass.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_uint32, P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
+                                P(C.c_uint8), C.c_void_p, P(C.c_uint32), C.c_int64, P(C.c_int64), P(C.c_uint32),
+                                P(C.c_uint64), C.c_void_p, P(C.c_uint32), P(C.c_int64)]
     _lib = L
     return L
 
@@ -640,6 +651,46 @@ class Context:
         n = nq * int(info[4])
         return dict(top_seqno=top_seqno[:n], top_count=top_count[:n], ntop=ntop[:n], peer_id=peer_id[:n],
                     peer_count=peer_count[:n], npeer=npeer[:n], info=info[:4], both=int(info[4]))
+
+    def run_pass(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30, lazy: bool = False,
+                 prev: bool = False, rec_cap: int | None = None) -> dict:
+        """umiclust_pass on the current load: one whole device pass of the block [q0, q0 + nq) -- the prefilter's
+        lists (as prefilter()), k_pack's outcomes `hostqs` (PASS_QS records), the record words `rec` (rec_total of
+        them), the raw result words `res` (walk: [qs, x]) and `peer_res` ([qs, y]), the `aligned` masks ([qs, 2]), the
+        final walk states `walk` (PASS_WALK records) and the 16 pass counters.  rec_cap: room for the records (default:
+        the largest a pass can write); a pass that needs more raises UmiclustError(-34)."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        nqs = max(nq, 1) * 2
+        top_seqno = np.zeros((nqs, 41), np.uint32)
+        top_count = np.zeros((nqs, 41), np.uint8)
+        ntop = np.zeros(nqs, np.uint8)
+        peer_id = np.zeros((nqs, 128), np.uint16)
+        peer_count = np.zeros((nqs, 128), np.uint8)
+        npeer = np.zeros(nqs, np.uint8)
+        hostqs = np.zeros(nqs, PASS_QS)
+        cap = nqs * PASS_REC_WORDS if rec_cap is None else rec_cap
+        rec = np.zeros(max(cap, 1), np.uint32)
+        total = np.zeros(1, np.int64)
+        res = np.zeros(nqs * 160, np.uint32)
+        aligned = np.zeros((nqs, 2), np.uint64)
+        walk = np.zeros(nqs, PASS_WALK)
+        counters = np.zeros(16, np.uint32)
+        info = np.zeros(8, np.int64)
+        P = C.POINTER
+        u8 = lambda a: a.ctypes.data_as(P(C.c_uint8))  # noqa: E731
+        u32 = lambda a: a.ctypes.data_as(P(C.c_uint32))  # noqa: E731
+        rc = lib().umiclust_pass(self._h, ce.ctypes.data_as(P(C.c_int32)), len(ce), q0, nq, nprev, append_step,
+                                 (1 if lazy else 0) | (2 if prev else 0), u32(top_seqno), u8(top_count), u8(ntop),
+                                 peer_id.ctypes.data_as(P(C.c_uint16)), u8(peer_count), u8(npeer), hostqs.ctypes.data,
+                                 u32(rec), cap, _i64(total), u32(res), aligned.ctypes.data_as(P(C.c_uint64)),
+                                 walk.ctypes.data, u32(counters), _i64(info))
+        self._check(rc, "pass")
+        n = nq * int(info[4])
+        return dict(top_seqno=top_seqno[:n], top_count=top_count[:n], ntop=ntop[:n], peer_id=peer_id[:n],
+                    peer_count=peer_count[:n], npeer=npeer[:n], info=info[:4], both=int(info[4]), hostqs=hostqs[:n],
+                    rec=rec[:min(int(total[0]), cap)], rec_total=int(total[0]), res=res[:n * 32].reshape(n, 32),
+                    peer_res=res[n * 32:n * 160].reshape(n, 128), aligned=aligned[:n], walk=walk[:n],
+                    counters=counters)
 
     def prep(self, p: Params, seqs) -> dict:
         b, o = _pack(seqs)
