@@ -345,6 +345,54 @@ int64_t umiclust_fastq_filter(umiclust_ctx *ctx, const umiclust_fastq_filter_par
 int64_t umiclust_fastq_filter_argv(umiclust_ctx *ctx, int32_t argc, const char *const *argv,
                                    umiclust_fastq_filter_result *result);
 
+/* ---- consensus alignment filter and cs-tag census (row f6) ---- */
+/* Replaces the per-record loops of ont_tcr_consensus/minimap2_align.py: count_cs_tags (:21-37, called on every
+ * library's raw-read BAM at :140 and on the filtered consensus BAM at :341), calculate_blast_id (:13-18) and the
+ * record loop and BAM output of filter_consensus_alignments (:158-359, :209-245).  A BAM session on the context:
+ * open inflates the file on the host threads, scans every record on the device (class, refID, l_seq,
+ * reference_length, the M/I/D column sum of :14-16, the NM and cs:Z aux tags) and groups the primary records by
+ * their cs string exactly (hashed on the device, every member compared with its group's first record, re-run with
+ * another seed on a collision).  The columns, names and strings are then read back in bulk and the Python drop-in
+ * (umiclust/minimap2_align.py) forms every float and every line of text from them.
+ * Memory model: umiclust_region_split's.  The whole inflated file is held on the host for the session and on the
+ * device during open; chunked streaming is out of scope.
+ * Errors: UMICLUST_EIO (unreadable or not BGZF), UMICLUST_EFORMAT (not BAM, a truncated record, or a primary
+ * record whose fields or aux tags do not fit it -- unknown type byte, a field past the record end, a Z/H string
+ * without NUL, an NM that is no integer, a cs that is no Z; the message names the record), UMICLUST_ESTATE (no
+ * open session), UMICLUST_ERANGE (buf too small: a call with cap = 0 returns the size needed). */
+/* inflate, scan, group; returns the number of records.  State lives in ctx until umiclust_bam_close or the next
+ * open.  hash_bits: 64 normally; a smaller value masks the hash on the FIRST pass only (test hook: forces the
+ * collision re-run) */
+int64_t umiclust_bam_open(umiclust_ctx *ctx, const char *bam_file, int32_t hash_bits);
+/* out[0..4] = n_records, n_refs, n_cs_groups, n_hash_reruns, index of the first malformed record or -1.  In an
+ * open session out[4] covers layout defects only (variable-length fields that overrun block_size) of a record that is
+ * unmapped, secondary or supplementary: the aux fields of such records are not walked, because the reference never
+ * reads them, and any defect of a primary record has already failed the open with UMICLUST_EFORMAT */
+int32_t umiclust_bam_counts(umiclust_ctx *ctx, int64_t *out);
+/* DIAGNOSTIC, not part of the drop-in: out[0..2] = seconds of the last open: host inflate, host-to-device copy (HIP
+ * events), scan + group + verify kernels of every hashing pass (HIP events).  tools/bam_scan_bench.py reads the
+ * figures of DESIGN.md §9b through it */
+int32_t umiclust_bam_times(umiclust_ctx *ctx, double *out);
+/* n-sized arrays, each may be NULL.  cls: 0 unmapped (flag & 4, tested first as :28 does), 1 secondary or
+ * supplementary (flag & 0x900), 2 primary mapped.  l_seq is pysam's query_length.  reference_length: M/D/N/=/X
+ * lengths, a zero sum counted as 1 (htslib bam_endpos).  cols: M/I/D lengths only (:14-16).  nm / nm_present: the
+ * NM tag of any integer type (primary records only, as cs_group).  cs_group: -1 = no cs tag */
+int32_t umiclust_bam_columns(umiclust_ctx *ctx, int8_t *cls, int32_t *ref, int32_t *l_seq, int64_t *reference_length,
+                             int64_t *cols, int64_t *nm, uint8_t *nm_present, int32_t *cs_group);
+/* reference names and lengths of the header: names NUL-joined into buf, off[n_refs+1]; returns the bytes needed */
+int32_t umiclust_bam_refs(umiclust_ctx *ctx, char *buf, int64_t cap, int64_t *off, int64_t *len);
+/* bulk gather for m records: kind 0 = query_name, 1 = cs string; bytes into buf, off[m+1]; returns bytes needed */
+int64_t umiclust_bam_strings(umiclust_ctx *ctx, int32_t kind, const int64_t *rec, int64_t m, char *buf, int64_t cap,
+                             int64_t *off);
+/* per group (n_cs_groups, first-seen order): count over primary records, representative (= first) record */
+int32_t umiclust_bam_cs_groups(umiclust_ctx *ctx, int64_t *count, int64_t *rep);
+/* header + the records with keep[r] != 0, as BGZF (blocks of at most 0xff00 payload bytes, EOF block last): the
+ * file inflates to the input's header bytes and the kept records' bytes verbatim, in input order (what
+ * pysam.AlignmentFile(..., "wb", template=bam_in).write(entry) leaves, :207/:245, up to the compressed form);
+ * returns the number written */
+int64_t umiclust_bam_write(umiclust_ctx *ctx, const uint8_t *keep, const char *out_bam);
+int32_t umiclust_bam_close(umiclust_ctx *ctx);
+
 /* ---- kernel-level entry points (parity tests) ---- */
 /* The quality kernel alone: record i = quals[offsets[i] .. offsets[i+1]); ee_fx[i] = sum over its bytes b with
  * 0 <= b - fastq_ascii <= 93 of llrint(10^(-(b - fastq_ascii)/10) * 2^40) (other bytes add 0), qlo[i] / qhi[i] = its

@@ -1,0 +1,70 @@
+// bam_host.h -- the HIP-free host side of the BAM readers and of the BAM writer (rows f4 and f6):
+// header parsing and record offsets (shared by umiclust_region_split and the umiclust_bam_* session), the host
+// restatement of k_bam_scan (csrc/bamscan.hip) and the BGZF writer.  Compiled by g++ (no HIP), so the CPU suite
+// builds it with ASan + UBSan (tools/bam_check_main.cpp, tests/test_bam_filter_cpu.py).
+#pragma once
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+namespace uc {
+namespace bam {
+
+struct Header {
+  size_t text_len = 0;                 // l_text
+  std::vector<std::string> ref_name;   // without the NUL
+  std::vector<int64_t> ref_len;
+  size_t end = 0;                      // offset of the first record = the bytes a writer copies verbatim
+};
+// raw = the inflated file.  false + err: not BAM / a header field runs past the buffer
+bool parse_header(const uint8_t* raw, size_t n, Header& h, std::string& err);
+// offsets of every record's block_size field from `start` on; false + err when the last record is cut short or a
+// block_size is smaller than the 32 fixed bytes
+bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int64_t>& roff, std::string& err);
+
+// block_size of the record whose block_size field is at p
+inline uint32_t rd_block(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// ---- the per-record columns of k_bam_scan ----
+constexpr uint64_t kCsEmpty = ~0ull;   // the group table's empty key: never a cs_hash
+enum : int8_t { kScanUnmapped = 0, kScanSecondary = 1, kScanPrimary = 2 };
+struct ScanRow {
+  int8_t cls = 0, bad = 0;
+  uint8_t nm_present = 0;
+  int32_t ref = -1, l_seq = 0, cs_len = -1;
+  int64_t reference_length = 0, cols = 0, nm = 0, cs_off = 0;
+  uint64_t cs_hash = 0;
+};
+// The hash of a cs string, order-independent over its bytes so that a wave can sum 64 positions a step:
+// mix(sum over x of mix(seed + (x + 1) * K1 + (byte + 1) * K2) ^ len * K3) & hmask, kCsEmpty mapped to kCsEmpty - 1.
+inline uint64_t mix64(uint64_t h) {
+  h ^= h >> 33;
+  h *= 0xff51afd7ed558ccdull;
+  h ^= h >> 33;
+  h *= 0xc4ceb9fe1a85ec53ull;
+  h ^= h >> 33;
+  return h;
+}
+constexpr uint64_t kCsK1 = 0x9e3779b97f4a7c15ull, kCsK2 = 0xd6e8feb86659fd93ull, kCsK3 = 0xa0761d6478bd642full;
+inline uint64_t cs_term(uint64_t seed, uint64_t x, uint8_t b) { return mix64(seed + (x + 1) * kCsK1 + ((uint64_t)b + 1) * kCsK2); }
+inline uint64_t cs_finish(uint64_t sum, uint64_t len, uint64_t hmask) {
+  const uint64_t h = mix64(sum ^ (len * kCsK3)) & hmask;
+  return h == kCsEmpty ? h - 1 : h;
+}
+// seed of hashing pass k (pass 0 first; a detected collision moves on to k + 1)
+inline uint64_t cs_seed(int k) { return 0x243f6a8885a308d3ull + (uint64_t)k * 0x13198a2e03707345ull; }
+
+// one record, exactly as the kernel computes it (roff = offset of its block_size field)
+void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask, ScanRow& out);
+
+// ---- BGZF writer ----
+// The file at `path` inflates to raw[0, header_end) followed by the records r with keep[r] != 0 (record r =
+// raw[roff[r], roff[r] + 4 + block_size)), in input order: blocks of at most 0xff00 payload bytes, raw deflate, the BC
+// extra field with BSIZE, CRC32 and ISIZE, then the 28-byte EOF block.  Blocks are compressed on `threads` threads
+// and written in order.  Returns the number of records written, -1 + err on an I/O failure.
+int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
+                   const uint8_t* keep, int threads, std::string& err);
+
+}  // namespace bam
+}  // namespace uc

@@ -51,6 +51,7 @@
 #include <zlib.h>
 
 #include "../../include/umiclust.h"
+#include "bam_host.h"
 #include "fastq_filter.h"
 #include "host_io.h"
 #include "plan.h"
@@ -483,6 +484,19 @@ struct umiclust_ctx {
   DevBuf<int32_t> t_cstart, t_mseq, t_mops, t_over;
   DevBuf<char> t_cons;
   hipEvent_t tev[2] = {nullptr, nullptr};
+  // BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
+  // the columns of the device scan
+  struct BamSession {
+    bool open = false;
+    std::vector<uint8_t> raw;
+    uc::bam::Header hdr;
+    std::vector<int64_t> roff, reflen, cols, nm, cs_off, g_count, g_rep;
+    std::vector<int32_t> ref, l_seq, cs_len, cs_group;
+    std::vector<int8_t> cls;
+    std::vector<uint8_t> nm_present;
+    int64_t n_reruns = 0, first_bad = -1;
+    double t_inflate = 0, t_h2d = 0, t_dev = 0;
+  } bs;
 
   void fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -3581,22 +3595,17 @@ int64_t umiclust_region_split(umiclust_ctx* c, const char* bam_file, int32_t nre
       c->fail(UMICLUST_EINVAL, "bad argument");
     std::vector<uint8_t> raw;
     if (!io::inflate_bgzf(bam_file, raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
-    if (raw.size() < 12 || memcmp(raw.data(), "BAM\1", 4) != 0) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
     // header: text, then the reference names, matched to the regions of the reference FASTA
+    bam::Header hdr;
+    std::string herr;
+    if (!bam::parse_header(raw.data(), raw.size(), hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
     std::unordered_map<std::string, int32_t> rid;
     for (int32_t r = 0; r < nregions; r++) rid.emplace(region_names[r], r);
-    size_t o = 4;
-    const int32_t lt = rd_i32(raw.data() + o);
-    o += 4 + (size_t)lt;
-    const int32_t nref = rd_i32(raw.data() + o);
-    o += 4;
-    std::vector<std::string> refname(nref);
+    const int32_t nref = (int32_t)hdr.ref_name.size();
+    const std::vector<std::string>& refname = hdr.ref_name;
     std::vector<int64_t> rlen(nref, -1);
     std::vector<int32_t> rclu(nref, -1), rreg(nref, -1);
     for (int32_t r = 0; r < nref; r++) {
-      const int32_t ln = rd_i32(raw.data() + o);
-      refname[r] = std::string((const char*)raw.data() + o + 4, (size_t)std::max(0, ln - 1));
-      o += 4 + (size_t)ln + 4;
       auto it = rid.find(refname[r]);
       if (it != rid.end()) {
         rreg[r] = it->second;
@@ -3605,11 +3614,7 @@ int64_t umiclust_region_split(umiclust_ctx* c, const char* bam_file, int32_t nre
       }
     }
     std::vector<int64_t> roff;
-    while (o + 4 <= raw.size()) {
-      roff.push_back((int64_t)o);
-      o += 4 + (size_t)rd_i32(raw.data() + o);
-    }
-    if (o != raw.size()) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
+    if (!bam::record_offsets(raw.data(), raw.size(), hdr.end, roff, herr)) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
     const int64_t n = (int64_t)roff.size();
     // device: classify every record
     DevBuf<uint8_t> d_raw;
@@ -3715,6 +3720,257 @@ int64_t umiclust_region_split(umiclust_ctx* c, const char* bam_file, int32_t nre
     }
     if (ncl > ncluster_cap) c->fail(UMICLUST_ERANGE, "cluster ids up to %d exceed the counter capacity", ncl - 1);
     return (int64_t)used.size();
+  });
+}
+
+// ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
+int64_t umiclust_bam_open(umiclust_ctx* c, const char* bam_file, int32_t hash_bits) {
+  UC_GUARD(c, {
+    if (!bam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
+    c->bs = umiclust_ctx::BamSession();
+    umiclust_ctx::BamSession S;
+    const double t0 = now_s();
+    if (!io::inflate_bgzf(bam_file, S.raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    S.t_inflate = now_s() - t0;
+    std::string herr;
+    if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
+      c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    const int64_t n = (int64_t)S.roff.size();
+    uint64_t m = 1024;
+    while (m < 2 * (uint64_t)n) m <<= 1;
+    DevBuf<uint8_t> d_raw, d_nmp;
+    DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
+    DevBuf<int32_t> d_ref, d_lseq, d_cslen;
+    DevBuf<int8_t> d_cls, d_bad;
+    DevBuf<uint64_t> d_hash;
+    DevBuf<unsigned long long> d_keys, d_rep;
+    DevBuf<uint32_t> d_cnt, d_coll;
+    const size_t n1 = (size_t)n + 1;
+    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
+    c->hip(d_roff.ensure(n1), "alloc");
+    c->hip(d_reflen.ensure(n1), "alloc");
+    c->hip(d_cols.ensure(n1), "alloc");
+    c->hip(d_nm.ensure(n1), "alloc");
+    c->hip(d_csoff.ensure(n1), "alloc");
+    c->hip(d_slot.ensure(n1), "alloc");
+    c->hip(d_ref.ensure(n1), "alloc");
+    c->hip(d_lseq.ensure(n1), "alloc");
+    c->hip(d_cslen.ensure(n1), "alloc");
+    c->hip(d_cls.ensure(n1), "alloc");
+    c->hip(d_bad.ensure(n1), "alloc");
+    c->hip(d_nmp.ensure(n1), "alloc");
+    c->hip(d_hash.ensure(n1), "alloc");
+    c->hip(d_keys.ensure((size_t)m), "alloc");
+    c->hip(d_rep.ensure((size_t)m), "alloc");
+    c->hip(d_cnt.ensure((size_t)m), "alloc");
+    c->hip(d_coll.ensure(1), "alloc");
+    float ms = 0.f;
+    c->hip(hipEventRecord(c->ev0, c->st), "event");
+    c->hip(hipMemcpyAsync(d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
+    if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(hipEventRecord(c->ev1, c->st), "event");
+    c->hip(hipEventSynchronize(c->ev1), "sync");
+    c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+    S.t_h2d = ms * 1e-3;
+    const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
+                        d_bad.p};
+    // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
+    constexpr int kMaxPasses = 8;
+    int pass = 0;
+    for (;; pass++) {
+      if (pass == kMaxPasses) c->fail(UMICLUST_EDEVICE, "cs hash collisions under %d seeds", kMaxPasses);
+      const uint64_t hmask = (pass == 0 && hash_bits < 64) ? ((1ull << hash_bits) - 1) : ~0ull;
+      uint32_t coll = 0;
+      c->hip(hipEventRecord(c->ev0, c->st), "event");
+      c->hip(launch_bam_scan(d_raw.p, (int64_t)S.raw.size(), d_roff.p, n, bam::cs_seed(pass), hmask, o, c->st), "bam scan");
+      c->hip(launch_cs_group(d_raw.p, o, n, m - 1, d_keys.p, d_rep.p, d_cnt.p, d_slot.p, d_coll.p, c->st), "cs group");
+      c->hip(hipEventRecord(c->ev1, c->st), "event");
+      c->hip(hipMemcpyAsync(&coll, d_coll.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipStreamSynchronize(c->st), "sync");
+      c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+      S.t_dev += ms * 1e-3;
+      if (!coll) break;
+    }
+    S.n_reruns = pass;
+    S.cls.resize(n), S.ref.resize(n), S.l_seq.resize(n), S.reflen.resize(n), S.cols.resize(n), S.nm.resize(n);
+    S.nm_present.resize(n), S.cs_off.resize(n), S.cs_len.resize(n), S.cs_group.assign(n, -1);
+    std::vector<int8_t> bad(n);
+    std::vector<int64_t> slot(n);
+    std::vector<unsigned long long> rep((size_t)m);
+    std::vector<uint32_t> cnt((size_t)m);
+    if (n) {
+      auto d2h = [&](void* dst, const void* src, size_t bytes) {
+        c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
+      };
+      d2h(S.cls.data(), d_cls.p, (size_t)n), d2h(S.ref.data(), d_ref.p, (size_t)n * 4);
+      d2h(S.l_seq.data(), d_lseq.p, (size_t)n * 4), d2h(S.reflen.data(), d_reflen.p, (size_t)n * 8);
+      d2h(S.cols.data(), d_cols.p, (size_t)n * 8), d2h(S.nm.data(), d_nm.p, (size_t)n * 8);
+      d2h(S.nm_present.data(), d_nmp.p, (size_t)n), d2h(S.cs_off.data(), d_csoff.p, (size_t)n * 8);
+      d2h(S.cs_len.data(), d_cslen.p, (size_t)n * 4), d2h(bad.data(), d_bad.p, (size_t)n);
+      d2h(slot.data(), d_slot.p, (size_t)n * 8), d2h(rep.data(), d_rep.p, (size_t)m * 8);
+      d2h(cnt.data(), d_cnt.p, (size_t)m * 4);
+      c->hip(hipStreamSynchronize(c->st), "sync");
+    }
+    for (int64_t r = 0; r < n; r++)
+      if (bad[r] && S.first_bad < 0) S.first_bad = r;  // a primary one fails below: what stays is a record never read
+    for (int64_t r = 0; r < n; r++)
+      if (S.cls[r] == bam::kScanPrimary && bad[r]) {
+        const uint8_t* f = S.raw.data() + S.roff[r] + 4;
+        const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(S.raw.data() + S.roff[r]) - 32);
+        const std::string name((const char*)f + 32, lrn ? strnlen((const char*)f + 32, lrn) : 0);
+        c->fail(UMICLUST_EFORMAT, "malformed BAM record %lld (%s): a field or an aux tag does not fit the record",
+                (long long)r, name.c_str());
+      }
+    // dense group ids in order of the representative = first-seen order (a representative is its group's first record)
+    std::vector<int32_t> gid_of_slot;
+    gid_of_slot.assign((size_t)m, -1);
+    for (int64_t r = 0; r < n; r++) {
+      const int64_t s = slot[r];
+      if (s < 0) continue;
+      if ((int64_t)rep[s] == r) {
+        gid_of_slot[s] = (int32_t)S.g_rep.size();
+        S.g_rep.push_back(r);
+        S.g_count.push_back((int64_t)cnt[s]);
+      }
+      S.cs_group[r] = gid_of_slot[s];
+    }
+    S.open = true;
+    c->bs = std::move(S);
+    return n;
+  });
+}
+
+namespace {
+umiclust_ctx::BamSession* bam_session(umiclust_ctx* c) {
+  if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
+  return &c->bs;
+}
+}  // namespace
+
+int32_t umiclust_bam_counts(umiclust_ctx* c, int64_t* out) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
+    out[0] = (int64_t)S.roff.size();
+    out[1] = (int64_t)S.hdr.ref_name.size();
+    out[2] = (int64_t)S.g_rep.size();
+    out[3] = S.n_reruns;
+    out[4] = S.first_bad;
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_times(umiclust_ctx* c, double* out) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
+    out[0] = S.t_inflate, out[1] = S.t_h2d, out[2] = S.t_dev;
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_columns(umiclust_ctx* c, int8_t* cls, int32_t* ref, int32_t* l_seq, int64_t* reference_length,
+                             int64_t* cols, int64_t* nm, uint8_t* nm_present, int32_t* cs_group) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const size_t n = S.roff.size();
+    if (n) {
+      if (cls) memcpy(cls, S.cls.data(), n);
+      if (ref) memcpy(ref, S.ref.data(), n * 4);
+      if (l_seq) memcpy(l_seq, S.l_seq.data(), n * 4);
+      if (reference_length) memcpy(reference_length, S.reflen.data(), n * 8);
+      if (cols) memcpy(cols, S.cols.data(), n * 8);
+      if (nm) memcpy(nm, S.nm.data(), n * 8);
+      if (nm_present) memcpy(nm_present, S.nm_present.data(), n);
+      if (cs_group) memcpy(cs_group, S.cs_group.data(), n * 4);
+    }
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_refs(umiclust_ctx* c, char* buf, int64_t cap, int64_t* off, int64_t* len) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    int64_t need = 0;
+    for (const std::string& s : S.hdr.ref_name) need += (int64_t)s.size() + 1;
+    if (need > INT32_MAX) c->fail(UMICLUST_ERANGE, "reference names exceed 2 GiB");
+    if (cap == 0) return (int32_t)need;
+    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
+    int64_t o = 0;
+    for (size_t r = 0; r < S.hdr.ref_name.size(); r++) {
+      off[r] = o;
+      memcpy(buf + o, S.hdr.ref_name[r].c_str(), S.hdr.ref_name[r].size() + 1);
+      o += (int64_t)S.hdr.ref_name[r].size() + 1;
+      if (len) len[r] = S.hdr.ref_len[r];
+    }
+    off[S.hdr.ref_name.size()] = o;
+    return (int32_t)need;
+  });
+}
+
+int64_t umiclust_bam_strings(umiclust_ctx* c, int32_t kind, const int64_t* rec, int64_t m, char* buf, int64_t cap,
+                             int64_t* off) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const int64_t n = (int64_t)S.roff.size();
+    if ((kind != 0 && kind != 1) || m < 0 || (m > 0 && !rec)) c->fail(UMICLUST_EINVAL, "bad argument");
+    auto span = [&](int64_t r, const uint8_t*& p) -> int64_t {
+      if (kind == 1) {
+        p = S.raw.data() + S.cs_off[r];
+        return std::max<int64_t>(0, S.cs_len[r]);
+      }
+      const uint8_t* f = S.raw.data() + S.roff[r] + 4;
+      p = f + 32;
+      const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(S.raw.data() + S.roff[r]) - 32);
+      return (int64_t)(lrn ? strnlen((const char*)p, lrn) : 0);
+    };
+    int64_t need = 0;
+    const uint8_t* p = nullptr;
+    for (int64_t x = 0; x < m; x++) {
+      if (rec[x] < 0 || rec[x] >= n) c->fail(UMICLUST_EINVAL, "record %lld out of range", (long long)rec[x]);
+      need += span(rec[x], p);
+    }
+    if (cap == 0) return need;
+    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
+    int64_t o = 0;
+    for (int64_t x = 0; x < m; x++) {
+      const int64_t ln = span(rec[x], p);
+      off[x] = o;
+      if (ln) memcpy(buf + o, p, (size_t)ln);
+      o += ln;
+    }
+    off[m] = o;
+    return need;
+  });
+}
+
+int32_t umiclust_bam_cs_groups(umiclust_ctx* c, int64_t* count, int64_t* rep) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const size_t g = S.g_rep.size();
+    if (g && count) memcpy(count, S.g_count.data(), g * 8);
+    if (g && rep) memcpy(rep, S.g_rep.data(), g * 8);
+    return UMICLUST_OK;
+  });
+}
+
+int64_t umiclust_bam_write(umiclust_ctx* c, const uint8_t* keep, const char* out_bam) {
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out_bam || (!keep && !S.roff.empty())) c->fail(UMICLUST_EINVAL, "null argument");
+    std::string err;
+    const int64_t k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
+    if (k < 0) c->fail(UMICLUST_EIO, "%s", err.c_str());
+    return k;
+  });
+}
+
+int32_t umiclust_bam_close(umiclust_ctx* c) {
+  UC_GUARD(c, {
+    (void)bam_session(c);
+    c->bs = umiclust_ctx::BamSession();
+    return UMICLUST_OK;
   });
 }
 

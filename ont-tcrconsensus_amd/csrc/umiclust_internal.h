@@ -276,4 +276,26 @@ hipError_t launch_bam_classify(const uint8_t* raw, const int64_t* roff, int64_t 
 hipError_t launch_bam_emit(const uint8_t* raw, const int64_t* roff, int64_t n, const int8_t* cls, const int64_t* pos,
                            char* out, hipStream_t st);
 
+// ---- BAM record scan with tags and the cs:Z group-by (bamscan.hip) ----
+struct BamScanCols {  // one entry per record
+  int8_t* cls;        // bam::kScanUnmapped / kScanSecondary / kScanPrimary
+  int32_t* ref;
+  int32_t* l_seq;
+  int64_t* reflen;    // M/D/N/=/X lengths, 0 -> 1
+  int64_t* cols;      // M/I/D lengths
+  int64_t* nm;
+  uint8_t* nm_present;
+  int64_t* cs_off;    // offset of the cs:Z bytes in raw
+  int32_t* cs_len;    // -1: no cs tag
+  uint64_t* cs_hash;
+  int8_t* bad;        // malformed layout or aux field (aux fields are walked on primary records only)
+};
+hipError_t launch_bam_scan(const uint8_t* raw, int64_t raw_len, const int64_t* roff, int64_t n, uint64_t seed,
+                           uint64_t hmask, const BamScanCols& o, hipStream_t st);
+// table of mask + 1 slots (at least twice the records): slot[r] (-1: not grouped), per slot the lowest record and the
+// count; *collision != 0 when two different strings shared a hash
+hipError_t launch_cs_group(const uint8_t* raw, const BamScanCols& o, int64_t n, uint64_t mask, unsigned long long* keys,
+                           unsigned long long* rep, uint32_t* cnt, int64_t* slot, uint32_t* collision,
+                           hipStream_t st);
+
 }  // namespace uc

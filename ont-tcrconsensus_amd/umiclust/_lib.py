@@ -131,6 +131,8 @@ EXPORTS = [
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
+    "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
+    "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_close",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -251,6 +253,26 @@ def lib() -> C.CDLL:
                                 C.c_uint32, P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
                                 P(C.c_uint8), C.c_void_p, P(C.c_uint32), C.c_int64, P(C.c_int64), P(C.c_uint32),
                                 P(C.c_uint64), C.c_void_p, P(C.c_uint32), P(C.c_int64)]
+    L.umiclust_bam_open.restype = C.c_int64
+    L.umiclust_bam_open.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.umiclust_bam_counts.restype = C.c_int32
+    L.umiclust_bam_counts.argtypes = [C.c_void_p, P(C.c_int64)]
+    L.umiclust_bam_times.restype = C.c_int32
+    L.umiclust_bam_times.argtypes = [C.c_void_p, P(C.c_double)]
+    L.umiclust_bam_columns.restype = C.c_int32
+    L.umiclust_bam_columns.argtypes = [C.c_void_p, P(C.c_int8), P(C.c_int32), P(C.c_int32), P(C.c_int64), P(C.c_int64),
+                                       P(C.c_int64), P(C.c_uint8), P(C.c_int32)]
+    L.umiclust_bam_refs.restype = C.c_int32
+    L.umiclust_bam_refs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), P(C.c_int64)]
+    L.umiclust_bam_strings.restype = C.c_int64
+    L.umiclust_bam_strings.argtypes = [C.c_void_p, C.c_int32, P(C.c_int64), C.c_int64, C.c_void_p, C.c_int64,
+                                       P(C.c_int64)]
+    L.umiclust_bam_cs_groups.restype = C.c_int32
+    L.umiclust_bam_cs_groups.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_int64)]
+    L.umiclust_bam_write.restype = C.c_int64
+    L.umiclust_bam_write.argtypes = [C.c_void_p, P(C.c_uint8), C.c_char_p]
+    L.umiclust_bam_close.restype = C.c_int32
+    L.umiclust_bam_close.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -557,6 +579,11 @@ class Context:
         self._check(rc, "region_split")
         return counts, rpc[:cap], det[:R]
 
+    def bam_open(self, bam_file: str, hash_bits: int = 64) -> "BamSession":
+        """umiclust_bam_open: the BAM session of this context (one at a time; row f6)."""
+        self._check(lib().umiclust_bam_open(self._h, os.fspath(bam_file).encode(), hash_bits), "bam_open")
+        return BamSession(self)
+
     def align_pairs(self, p: Params, queries, targets, with_ops: bool = False) -> dict:
         qb, qo = _pack(queries)
         tb, to = _pack(targets)
@@ -707,3 +734,75 @@ class Context:
         return dict(masked=[mb[o[i]:o[i + 1]].decode() for i in range(n)],
                     kmers=[[list(km[(2 * i + s) * kst:(2 * i + s) * kst + nk[2 * i + s]]) for s in range(2)]
                            for i in range(n)])
+
+
+class BamSession:
+    """The columns of an open BAM session (umiclust_bam_*), read once; names and cs strings are gathered in bulk on
+    request.  The attributes are what umiclust.minimap2_align's formatting half takes from any source: n, cls, ref,
+    l_seq, reference_length, cols, nm, nm_present, cs_group, ref_names, ref_lengths, query_names(idx),
+    cs_strings(idx), write(keep, path)."""
+
+    def __init__(self, ctx: Context):
+        self._ctx = ctx
+        L, h, P = lib(), ctx._h, C.POINTER
+        cnt = np.zeros(5, np.int64)
+        ctx._check(L.umiclust_bam_counts(h, _i64(cnt)), "bam_counts")
+        self.n, self.n_refs, self.n_cs_groups, self.n_hash_reruns, self.first_malformed = (int(x) for x in cnt)
+        t = np.zeros(3, np.float64)
+        ctx._check(L.umiclust_bam_times(h, t.ctypes.data_as(P(C.c_double))), "bam_times")
+        self.times = {"inflate_s": float(t[0]), "h2d_s": float(t[1]), "device_s": float(t[2])}
+        n = self.n
+        self.cls, self.ref, self.l_seq = np.zeros(n, np.int8), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.reference_length, self.cols, self.nm = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.nm_present, self.cs_group = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        ctx._check(L.umiclust_bam_columns(
+            h, self.cls.ctypes.data_as(P(C.c_int8)), self.ref.ctypes.data_as(P(C.c_int32)),
+            self.l_seq.ctypes.data_as(P(C.c_int32)), _i64(self.reference_length), _i64(self.cols), _i64(self.nm),
+            self.nm_present.ctypes.data_as(P(C.c_uint8)), self.cs_group.ctypes.data_as(P(C.c_int32))), "bam_columns")
+        need = ctx._check(L.umiclust_bam_refs(h, None, 0, None, None), "bam_refs")
+        buf, off = np.zeros(max(need, 1), np.uint8), np.zeros(self.n_refs + 1, np.int64)
+        self.ref_lengths = np.zeros(self.n_refs, np.int64)
+        if self.n_refs:
+            ctx._check(L.umiclust_bam_refs(h, buf.ctypes.data, need, _i64(off), _i64(self.ref_lengths)), "bam_refs")
+        raw = buf.tobytes()
+        self.ref_names = [raw[off[r]:off[r + 1] - 1].decode("ascii") for r in range(self.n_refs)]
+        self.group_count, self.group_rep = np.zeros(self.n_cs_groups, np.int64), np.zeros(self.n_cs_groups, np.int64)
+        ctx._check(L.umiclust_bam_cs_groups(h, _i64(self.group_count), _i64(self.group_rep)), "bam_cs_groups")
+
+    def _strings(self, kind: int, idx) -> list:
+        idx = np.ascontiguousarray(idx, np.int64)
+        m = len(idx)
+        if m == 0:
+            return []
+        L, h = lib(), self._ctx._h
+        need = self._ctx._check(L.umiclust_bam_strings(h, kind, _i64(idx), m, None, 0, None), "bam_strings")
+        buf, off = np.zeros(max(need, 1), np.uint8), np.zeros(m + 1, np.int64)
+        if need:
+            self._ctx._check(L.umiclust_bam_strings(h, kind, _i64(idx), m, buf.ctypes.data, need, _i64(off)),
+                             "bam_strings")
+        raw = buf.tobytes()
+        return [raw[off[x]:off[x + 1]].decode("ascii") for x in range(m)]
+
+    def query_names(self, idx) -> list:
+        return self._strings(0, idx)
+
+    def cs_strings(self, idx) -> list:
+        return self._strings(1, idx)
+
+    def write(self, keep, path) -> int:
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        if len(keep) != self.n:
+            raise ValueError("keep needs one entry per record")
+        return int(self._ctx._check(lib().umiclust_bam_write(
+            self._ctx._h, keep.ctypes.data_as(C.POINTER(C.c_uint8)), os.fspath(path).encode()), "bam_write"))
+
+    def close(self) -> None:
+        if self._ctx is not None:
+            self._ctx._check(lib().umiclust_bam_close(self._ctx._h), "bam_close")
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -1,0 +1,243 @@
+"""The consensus alignment filter and the cs-tag census (row f6) without a GPU.
+
+tests/golden/bam_filter/*.json hold what the reference's own filter_consensus_alignments and count_cs_tags left on
+each case (tests/golden/make_golden_bam_filter.py).  Here: tests/bam_ref.py (the plain reference of the device scan and
+group-by) reproduces every fixture; the formatting half of umiclust.minimap2_align, fed bam_ref's columns, reproduces
+every CSV and log byte for byte; and tools/bam_check_main.cpp -- bam_host.cpp under ASan + UBSan -- prints the same
+columns as bam_ref and round-trips the BGZF writer.  A sanitizer report fails the test."""
+import collections
+import glob
+import json
+import os
+import shutil
+import subprocess
+import warnings
+
+import numpy as np
+import pytest
+from umiclust import _lib, minimap2_align
+
+import bam_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = {os.path.basename(p)[:-5]: json.load(open(p))
+         for p in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "bam_filter", "*.json")))}
+RUNNING = [k for k, c in CASES.items() if "eformat_record" not in c]
+MALFORMED = [k for k, c in CASES.items() if "eformat_record" in c]
+SAN_ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+ERRORS = {"KeyError": KeyError, "ZeroDivisionError": ZeroDivisionError}
+
+
+def test_fixture_set():
+    assert len(CASES) >= 14 and len(MALFORMED) == 2
+    for c in CASES.values():
+        assert len(c["records"]) <= 400
+        assert all(len(t[2]) <= 300 for r in c["records"] for t in r["tags"] if t[0] == "cs" and t[1] == "Z")
+    distinct = {t[2] for r in CASES["forced_collision"]["records"] for t in r["tags"] if t[0] == "cs"}
+    assert len(distinct) >= 300 and CASES["forced_collision"]["hash_bits"] == 8  # more strings than 8-bit hashes
+    assert sorted(c["expect"]["error"][0] for c in CASES.values() if c.get("expect", {}).get("error")) == \
+        ["KeyError", "KeyError", "ZeroDivisionError"]
+
+
+def test_exports_and_abi():
+    names = {"umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns",
+             "umiclust_bam_refs", "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write",
+             "umiclust_bam_close"}
+    assert names <= set(_lib.EXPORTS)
+    lib = _lib.lib()
+    for n in names:
+        assert hasattr(lib, n), n
+    assert lib.umiclust_abi_version() == 9
+
+
+# ---------------------------------------------------------------- bam_ref against the fixtures
+@pytest.mark.parametrize("name", RUNNING)
+def test_bam_ref_reproduces_the_census(name):
+    case, e = CASES[name], CASES[name]["expect"]
+    col = bam_ref.Columns(bam_ref.build_raw(case["refs"], case["records"]))
+    if e["cs_error"] is None:
+        assert [[s, n] for s, n in zip(col.group_strings, col.group_count)] == e["cs_counter"]
+        regions = {}
+        for i in np.flatnonzero(col.cs_group >= 0):
+            regions.setdefault(col.cs[i], {}).setdefault(col.ref_names[col.ref[i]], 0)
+            regions[col.cs[i]][col.ref_names[col.ref[i]]] += 1
+        assert list(regions) == col.group_strings
+        assert [[[r, n] for r, n in v.items()] for v in regions.values()] == e["cs_region_counter"]
+        blast = {}
+        for i in np.flatnonzero(col.cs_group >= 0):
+            x = (int(col.cols[i]) - int(col.nm[i])) / int(col.cols[i])
+            blast.setdefault(col.cs[i], {}).setdefault(x, 0)
+            blast[col.cs[i]][x] += 1
+        assert [[[x, n] for x, n in v.items()] for v in blast.values()] == e["cs_blast_id_counter"]
+    assert [int(r) for r in col.group_rep] == [int(np.flatnonzero(col.cs_group == g)[0]) for g in range(len(col.group_rep))]
+
+
+@pytest.mark.parametrize("name", MALFORMED)
+def test_bam_ref_refuses_the_malformed_primary_record(name):
+    case = CASES[name]
+    with pytest.raises(bam_ref.Malformed) as ei:
+        bam_ref.Columns(bam_ref.build_raw(case["refs"], case["records"]))
+    assert ei.value.record == case["eformat_record"]
+
+
+# ---------------------------------------------------------------- the formatting half on bam_ref's columns
+def run_drop_in(src, case, tmp_path, monkeypatch, name):
+    """filter_consensus_alignments_from on `src` (None: filter_consensus_alignments on the BAM file itself);
+    (return or None, error or None, files, kept, inflated output)"""
+    calls = []
+    monkeypatch.setattr(minimap2_align.subprocess, "run", lambda *a, **k: calls.append(a[0]))
+    logs = tmp_path / "logs"
+    logs.mkdir()
+    fasta = tmp_path / "ref.fa"
+    bam_ref.write_fasta(fasta, case["regions"])
+    bam = str(tmp_path / (name + ".bam"))
+    ret, err = None, None
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # numpy's mean / median of an empty list, as in the reference
+        try:
+            if src is None:
+                ret = minimap2_align.filter_consensus_alignments(bam, str(fasta), str(logs), **case["params"])
+            else:
+                ret = minimap2_align.filter_consensus_alignments_from(src, bam, str(fasta), str(logs), **case["params"])
+            ret = os.path.basename(ret)
+            assert calls == [["samtools", "index", str(tmp_path / (name + "_filtered.bam"))]]
+        except (KeyError, ZeroDivisionError) as e:
+            err = [type(e).__name__, [str(a) for a in e.args]]
+    files = {f: open(logs / f).read() for f in sorted(os.listdir(logs))}
+    stream = bam_ref.check_bgzf(tmp_path / (name + "_filtered.bam"))
+    index = {r["name"]: i for i, r in enumerate(case["records"])}
+    kept = [index[r.query_name] for r in bam_ref.decode(stream)[2]]
+    return ret, err, files, kept, stream
+
+
+def check_against_fixture(got, case, raw):
+    ret, err, files, kept, stream = got
+    e = case["expect"]
+    assert err == e["error"] and ret == e["return"]
+    assert kept == e["kept"]
+    assert sorted(files) == sorted(e["files"])
+    for f in e["files"]:
+        assert files[f] == e["files"][f], f
+    keep = np.zeros(len(case["records"]), bool)
+    keep[e["kept"]] = True
+    assert stream == bam_ref.Columns(raw).expected_stream(keep)
+
+
+def report_of(e):
+    """the three log blocks of minimap2_ont_align (:141-150) from the reference's counters, which the fixture holds in
+    their insertion order: the order Counter.most_common breaks ties by"""
+    a = collections.Counter(dict(e["cs_counter"]))
+    b = {k: collections.Counter(dict(map(tuple, v))) for k, v in zip(a, e["cs_region_counter"])}
+    c = {k: collections.Counter(dict(map(tuple, v))) for k, v in zip(a, e["cs_blast_id_counter"])}
+    top = a.most_common(40)
+    out = ["\nTop 40 most common cs tags:\n"] + [str(t) + "\n" for t in top]
+    out.append("\nTop 4 most common regions counted for each of the top 40 most common cs tags:\n")
+    out += [str(t[0]) + " " + str(b[t[0]].most_common(4)) + "\n" for t in top]
+    out.append("\nTop 4 most common blast identities counted for each of the top 40 most common cs tags:\n")
+    out += [str(t[0]) + " " + str(c[t[0]].most_common(4)) + "\n" for t in top]
+    return "".join(out)
+
+
+def check_census(src, case):
+    e = case["expect"]
+    if e["cs_error"] is not None:
+        with pytest.raises(ERRORS[e["cs_error"][0]]) as ei:
+            minimap2_align.count_cs_tags(src)
+        assert [str(a) for a in ei.value.args] == e["cs_error"][1]
+        return
+    a, b, c = minimap2_align.count_cs_tags(src)
+    assert [[k, v] for k, v in a.items()] == e["cs_counter"]
+    assert list(a) == list(b) == list(c)  # the fixture stores the two dicts of Counters without their keys
+    assert [[[r, n] for r, n in v.items()] for v in b.values()] == e["cs_region_counter"]
+    assert [[[x, n] for x, n in v.items()] for v in c.values()] == e["cs_blast_id_counter"]
+    assert minimap2_align.cs_tag_report(src) == report_of(e)
+
+
+@pytest.mark.parametrize("name", RUNNING)
+def test_formatting_half_reproduces_every_file(name, tmp_path, monkeypatch):
+    case = CASES[name]
+    raw = bam_ref.build_raw(case["refs"], case["records"])
+    src = bam_ref.Columns(raw)
+    check_against_fixture(run_drop_in(src, case, tmp_path, monkeypatch, name), case, raw)
+    check_census(src, case)
+
+
+def test_the_cut_at_rank_40_follows_first_seen_order():
+    e = CASES["grouping"]["expect"]
+    counts = [n for _, n in e["cs_counter"]]
+    ranked = sorted(range(len(counts)), key=lambda x: (-counts[x], x))
+    assert counts[ranked[39]] == counts[ranked[40]]  # ranks 40 and 41 tie: only first-seen order decides
+    top = [e["cs_counter"][x][0] for x in ranked[:40]]
+    lines = report_of(e).split("\n")
+    assert [ln for ln in lines[2:42]] == [str((t, counts[ranked[x]])) for x, t in enumerate(top)]
+    half = [k for k, _ in e["cs_counter"]].index("=half")
+    assert e["cs_blast_id_counter"][half] == [[0.5, 4], [0.51, 1]]  # (100, 50), (200, 100), (150, 75): one key
+
+
+# ---------------------------------------------------------------- bam_host.cpp under ASan + UBSan
+@pytest.fixture(scope="module")
+def bam_check(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    out = tmp_path_factory.mktemp("bam_check")
+    b = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "ont-tcrconsensus_amd"), "bam_check", f"SAN_OUT={out}"],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr
+    assert "warning" not in b.stderr, b.stderr
+
+    def run(bam, prefix, threads=3, rc=0):
+        r = subprocess.run([str(out / "bam_check"), str(bam), str(prefix), str(threads)], capture_output=True, text=True,
+                           timeout=300, env=SAN_ENV)
+        assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+        assert r.returncode == rc, (r.stdout[-2000:], r.stderr[-2000:])
+        return r.stdout.split("\n")
+
+    return run
+
+
+def parse_rows(lines):
+    rows = {}
+    for ln in lines:
+        if ln.startswith("rec "):
+            head, cs = ln.split(" cs=", 1)
+            rows[int(head.split()[1])] = [int(x) for x in head.split()[2:]] + [cs]
+    return rows
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_bam_check_columns_and_writer_roundtrip(bam_check, name, tmp_path):
+    case = CASES[name]
+    bam = tmp_path / "in.bam"
+    raw = bam_ref.write_bam(bam, case["refs"], case["records"], block=4000 if name == "aux_walk" else 60000)
+    lines = bam_check(bam, tmp_path / "out", threads=1 if name == "cigar" else 3)
+    assert "roundtrip ok" in lines
+    assert [ln for ln in lines if ln.startswith("ref ")] == ["ref %s %d" % (n, ln) for n, ln in case["refs"]]
+    rows = parse_rows(lines)
+    _, start, recs = bam_ref.decode(raw)
+    assert len(rows) == len(recs)
+    if "eformat_record" in case:
+        assert [r for r, v in rows.items() if v[8]] == [case["eformat_record"]]
+    else:
+        col = bam_ref.Columns(raw)
+        for r in range(col.n):
+            want = [int(col.cls[r]), int(col.ref[r]), int(col.l_seq[r]), int(col.reference_length[r]), int(col.cols[r]),
+                    int(col.nm[r]), int(col.nm_present[r]), len(col.cs[r]) if col.cs[r] is not None else -1, 0,
+                    col.cs[r] or ""]
+            assert rows[r] == want, r
+    # the writer: well-formed BGZF that inflates to the header and the kept records
+    assert bam_ref.check_bgzf(str(tmp_path / "out.all.bam")) == raw
+    assert bam_ref.check_bgzf(str(tmp_path / "out.alt.bam")) == \
+        raw[:start] + b"".join(r.bytes for i, r in enumerate(recs) if i % 2 == 0)
+
+
+def test_bam_check_refuses_what_is_not_bam(bam_check, tmp_path):
+    p = tmp_path / "x.bam"
+    p.write_bytes(b"not gzip at all")
+    assert any(ln.startswith("err=cannot read BGZF") for ln in bam_check(p, tmp_path / "o", rc=2))
+    bam_ref.write_bgzf(p, b"SAM\x01" + b"\0" * 20)
+    assert "err=not BAM" in bam_check(p, tmp_path / "o", rc=2)
+    raw = bam_ref.build_raw([["r", 10]], [{"name": "a_1", "flag": 0, "ref": 0, "cigar": [["M", 5]], "l_seq": 5, "tags": []}])
+    bam_ref.write_bgzf(p, raw[:-3])  # the last record is cut short
+    assert any(ln.startswith("err=truncated BAM record 0") for ln in bam_check(p, tmp_path / "o", rc=2))
+    bam_ref.write_bgzf(p, raw[:30])  # the header is cut short
+    assert any(ln.startswith("err=truncated BAM header") for ln in bam_check(p, tmp_path / "o", rc=2))
