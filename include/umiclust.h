@@ -287,7 +287,9 @@ int64_t umiclust_extract_umis_file(umiclust_ctx *ctx, const char *fastx_file, co
  * record aligned to region r.  Returns the number of cluster files appended to.  A record aligned to a
  * reference missing from the regions (or from the cluster JSON once it passes the filters) stops the loop
  * as the reference's KeyError does: the records before it are written and UMICLUST_EFORMAT is returned with
- * the name in missing_name. */
+ * the name in missing_name.  A record whose l_read_name, n_cigar_op or l_seq do not fit its block_size is
+ * refused before anything runs on the device: UMICLUST_EFORMAT naming the record, missing_name not written,
+ * nothing written. */
 int64_t umiclust_region_split(umiclust_ctx *ctx, const char *bam_file, int32_t nregions,
                               const char *const *region_names, const int64_t *region_lengths,
                               const int32_t *region_clusters, double minimal_region_overlap,

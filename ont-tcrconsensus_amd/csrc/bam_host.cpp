@@ -76,6 +76,21 @@ bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int6
   return true;
 }
 
+bool check_record_fields(const uint8_t* raw, const std::vector<int64_t>& roff, std::string& err) {
+  for (size_t r = 0; r < roff.size(); r++) {
+    const uint8_t* f = raw + roff[r] + 4;
+    const int64_t bs = (int64_t)ld_u32(raw + roff[r]);
+    const int64_t lrn = f[8], ncig = ld_u16(f + 12), lseq = (int32_t)ld_u32(f + 16);
+    // offsets from the block_size field: 36 fixed bytes, name, CIGAR, 4-bit sequence, qualities
+    if (lrn < 1 || lseq < 0 || 36 + lrn + 4 * ncig + (lseq + 1) / 2 + lseq > 4 + bs) {
+      err = "BAM record " + std::to_string(r) + ": l_read_name " + std::to_string(lrn) + ", n_cigar_op " +
+            std::to_string(ncig) + ", l_seq " + std::to_string(lseq) + " do not fit block_size " + std::to_string(bs);
+      return false;
+    }
+  }
+  return true;
+}
+
 void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask, ScanRow& out) {
   out = ScanRow();
   const uint8_t* f = raw + roff + 4;

@@ -23,6 +23,12 @@ bool parse_header(const uint8_t* raw, size_t n, Header& h, std::string& err);
 // block_size is smaller than the 32 fixed bytes
 bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int64_t>& roff, std::string& err);
 
+// the variable-length fields of every record stay inside the record: l_read_name >= 1, l_seq >= 0 and
+// 36 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size.  The f4 kernels (regionsplit.hip)
+// index the name, the CIGAR and the sequence by these fields alone, so umiclust_region_split checks them before any
+// launch.  false + err naming the first record that fails
+bool check_record_fields(const uint8_t* raw, const std::vector<int64_t>& roff, std::string& err);
+
 // block_size of the record whose block_size field is at p
 inline uint32_t rd_block(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 

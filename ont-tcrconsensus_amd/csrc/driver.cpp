@@ -3615,6 +3615,8 @@ int64_t umiclust_region_split(umiclust_ctx* c, const char* bam_file, int32_t nre
     }
     std::vector<int64_t> roff;
     if (!bam::record_offsets(raw.data(), raw.size(), hdr.end, roff, herr)) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
+    // the kernels index each record by its own l_read_name, n_cigar_op and l_seq
+    if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
     const int64_t n = (int64_t)roff.size();
     // device: classify every record
     DevBuf<uint8_t> d_raw;

@@ -23,6 +23,16 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
 }
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
+// region_length * (2 - minimal_region_overlap) + (max_softclip_5_end + max_softclip_3_end) as the reference evaluates
+// it (:264-267): the product rounded to a double, then the add.  Contracted into one fma (the compiler's default, and
+// __dmul_rn / __dadd_rn do not prevent it) the bound can land one ulp lower, and a read exactly at it drops as long:
+// region 400, overlap 0.93, slack 141 gives 569.0 rounded and 568.9999999999999 fused.
+__device__ __forceinline__ double long_bound(double L, double minov, int32_t slack) {
+#pragma clang fp contract(off)
+  const double prod = L * (2.0 - minov);
+  return prod + (double)slack;
+}
+
 // per record: class (kBamUnmapped ... kBamNoCluster), cluster, output bytes
 __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* __restrict__ roff, int64_t n,
                                int32_t nref, const int64_t* __restrict__ ref_len, const int32_t* __restrict__ ref_cluster,
@@ -54,9 +64,10 @@ __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* _
     // or only I/S/H/P ops) as 1: such a record is 1 base long and drops as short (:261-263)
     if (rl == 0) rl = 1;
     const double L = (double)ref_len[ref];
+    const double bound = long_bound(L, minov, s5 + s3);
     if ((double)rl < L * minov) {
       c = kBamShort;
-    } else if ((double)lseq > L * (2.0 - minov) + (double)(s5 + s3)) {
+    } else if ((double)lseq > bound) {
       c = kBamLong;
     } else if (ref_cluster[ref] < 0) {
       c = kBamNoCluster;  // region_cluster_dict[entry.reference_name] raises

@@ -17,7 +17,8 @@ O(m n) dynamic program:
     reversed target prefix [0, e]: among the reversed positions p with distance = the edit distance, the
     LAST (largest) one, start = e - p ("ensures that alignment will not start with insertion").
   * equality: identical bytes, or a pair of additionalEqualities, in either order.
-PARITY UNPINNED against edlib itself (no binary, no fixture); the tests pin it on hand-derived cases.
+PARITY UNPINNED against edlib itself (no binary, no fixture); the tests pin it on hand-derived cases and against
+a brute-force definition over every substring (tests/extract_ref.py, tests/test_extract_cpu.py).
 """
 from __future__ import annotations
 

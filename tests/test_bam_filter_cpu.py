@@ -230,6 +230,33 @@ def test_bam_check_columns_and_writer_roundtrip(bam_check, name, tmp_path):
         raw[:start] + b"".join(r.bytes for i, r in enumerate(recs) if i % 2 == 0)
 
 
+@pytest.mark.parametrize("field,value", [("l_read_name", 255), ("l_read_name", 5), ("l_read_name", 0),
+                                         ("n_cigar_op", 65535), ("n_cigar_op", 3), ("l_seq", 1000), ("l_seq", 11),
+                                         ("l_seq", -1), ("l_seq", 0x7fffffff)])
+def test_bam_check_names_the_record_whose_fields_overrun_it(bam_check, tmp_path, field, value):
+    """bam::check_record_fields, which umiclust_region_split runs before its kernels (they index the name, the CIGAR
+    and the sequence by l_read_name, n_cigar_op and l_seq alone): record 2 of 4 claims a name, a CIGAR or a sequence
+    that its block_size does not hold -- by far, and by the smallest step (a record without tags fills its block_size
+    exactly: name 4 -> 5, 2 ops -> 3, l_seq 10 -> 11).  CPU only: no such record is ever given to the device."""
+    import struct
+    recs = [{"name": "a_%d" % i, "flag": 16 * (i & 1), "ref": 0, "cigar": [["M", 6], ["S", 4]], "l_seq": 10,
+             "tags": [["NM", "C", 1]] if i == 3 else []} for i in range(4)]
+    raw = bytearray(bam_ref.build_raw([["r", 10]], recs))
+    p = tmp_path / "ok.bam"
+    bam_ref.write_bgzf(p, bytes(raw))
+    assert "fields=ok" in bam_check(p, tmp_path / "o")
+    o = bam_ref.record_offsets(bytes(raw), bam_ref.parse_header(bytes(raw))[1])[2]
+    assert struct.unpack_from("<B", raw, o + 12)[0] == 4 and struct.unpack_from("<H", raw, o + 16)[0] == 2
+    assert struct.unpack_from("<i", raw, o + 20)[0] == 10
+    struct.pack_into(*{"l_read_name": ("<B", raw, o + 12), "n_cigar_op": ("<H", raw, o + 16),
+                       "l_seq": ("<i", raw, o + 20)}[field], value)
+    p = tmp_path / "bad.bam"
+    bam_ref.write_bgzf(p, bytes(raw))
+    lines = bam_check(p, tmp_path / "o")
+    msg = [ln for ln in lines if ln.startswith("fields=")]
+    assert len(msg) == 1 and msg[0].startswith("fields=BAM record 2: ") and f"{field} {value}" in msg[0], msg
+
+
 def test_bam_check_refuses_what_is_not_bam(bam_check, tmp_path):
     p = tmp_path / "x.bam"
     p.write_bytes(b"not gzip at all")

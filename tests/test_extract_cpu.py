@@ -46,6 +46,60 @@ def test_first_end_and_leftmost_start():
     assert ox.hw_locate("ACG", "AG", 1) == (1, 0, 1)
 
 
+def test_hw_locate_vs_brute_force_definition():
+    """hw_locate (the GPU kernels' checker) against tests/extract_ref.py, which takes the minimum over every substring
+    with a plain Levenshtein distance and shares no code with it: 1,500 seeded cases, patterns of 1..8 symbols over
+    ACGTVBN, windows of 0..14 over alphabets of 1, 2, 4 and 5 letters, k in {0, 1, 2, m, m + 1}."""
+    import random
+
+    import extract_ref
+    rng = random.Random(20261020)
+    found = 0
+    for case in range(1500):
+        m = rng.randint(1, 8)
+        pat = "".join(rng.choice("ACGTVBN") for _ in range(m))
+        alpha = rng.choice(["A", "AC", "ACGT", "ACGTN"])
+        w = "".join(rng.choice(alpha) for _ in range(rng.randint(0, 14)))
+        k = rng.choice([0, 1, 2, m, m + 1])
+        want = extract_ref.locate(pat, w, k)
+        assert ox.hw_locate(pat, w, k) == want, (case, pat, w, k)
+        found += want is not None
+    assert 300 < found < 1400  # both outcomes are well covered
+    for a in "ACGTMRWSYKVHDBNacgtmrwsykvhdbn=X":
+        for b in "ACGTMRWSYKVHDBNacgtmrwsykvhdbn=X":
+            assert ox.eq(a, b) == extract_ref.eq(a, b), (a, b)
+
+
+def test_pattern_of_64_symbols():
+    """m = 64 fills the kernel's word: hand-derived answers, the last pattern symbol (the word's high bit) decisive."""
+    a64 = "A" * 64
+    assert ox.hw_locate(a64, a64, 0) == (0, 0, 63)
+    assert ox.hw_locate(a64, "C" + a64 + "C", 0) == (0, 1, 64)
+    assert ox.hw_locate(a64, "A" * 63, 0) is None
+    assert ox.hw_locate(a64, "A" * 63, 1) == (1, 0, 62)  # one deletion, and only the whole window reaches it
+    # exactly 63 A and the closing C: the end is the C, the start 63 before it
+    assert ox.hw_locate("A" * 63 + "C", "A" * 70 + "C", 0) == (0, 7, 70)
+    assert ox.hw_locate("C" + "A" * 63, "C" + "A" * 70, 0) == (0, 0, 63)  # the first end with the distance
+    assert ox.hw_locate("A" * 63 + "C", "A" * 70 + "G", 0) is None
+    assert ox.hw_locate("A" * 63 + "C", "A" * 70 + "G", 1) == (1, 0, 62)  # 63 A, the C deleted: first end 62
+    assert ox.hw_locate("A" * 63 + "V", "T" + "A" * 63 + "G", 0) == (0, 1, 64)  # V = G in the high bit
+
+
+def test_k_at_least_the_pattern_length():
+    """With k >= m every non-empty window has a location: the empty alignment costs m.  Hand-derived."""
+    assert ox.hw_locate("ACG", "TTTT", 2) is None
+    assert ox.hw_locate("ACG", "TTTT", 3) == (3, 0, 0)  # nothing matches: distance m at the first column
+    assert ox.hw_locate("ACG", "TTTT", 6) == (3, 0, 0)
+    assert ox.hw_locate("A", "C", 1) == (1, 0, 0) and ox.hw_locate("A", "C", 5) == (1, 0, 0)
+    assert ox.hw_locate("A", "", 5) is None  # an empty window has no location at any k
+    # AC in GA: "A" alone costs 1 (end 1), "GA" costs 2, so the start is 1
+    assert ox.hw_locate("AC", "GA", 2) == (1, 1, 1)
+    assert ox.hw_locate("AC", "GA", 1) == (1, 1, 1) and ox.hw_locate("AC", "GA", 0) is None
+    import extract_ref
+    for pat, w, k in [("ACG", "TTTT", 3), ("A", "C", 5), ("AC", "GA", 2), ("A", "", 5)]:
+        assert extract_ref.locate(pat, w, k) == ox.hw_locate(pat, w, k)
+
+
 def test_records_and_strand():
     u5 = "TTTACTTGACGTTCAGCTTGGAATTACGCTTT"
     u3 = "AAACGTCAACTGCAATGTCAAGGCTAACTAAA"

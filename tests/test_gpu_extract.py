@@ -82,6 +82,106 @@ def test_window_sizes_vs_oracle(gpu_ctx, a5, a3):
             assert g == (want if want else (-1, -1, -1)), (i, w, a5, a3)
 
 
+def _check_every_window(ctx, seqs, a5, a3, k, fwd, rev, note=()):
+    """Every window of every read against hw_locate, exactly (Python slicing: seq[:a5], seq[-a3:])."""
+    got = ctx.extract_umis(seqs, a5, a3, k, fwd, rev)
+    assert got.shape == (len(seqs), 6)
+    for i, s in enumerate(seqs):
+        for w, (pat, win) in enumerate(((fwd, s[:a5]), (rev, s[-a3:]))):
+            want = ox.hw_locate(pat, win, k)
+            g = tuple(int(x) for x in got[i, 3 * w:3 * w + 3])
+            assert g == (want if want else (-1, -1, -1)), (note, i, w, a5, a3, k, pat, win)
+
+
+IUPAC = {"M": "AC", "R": "AG", "W": "AT", "S": "CG", "Y": "CT", "K": "GT", "V": "ACG", "H": "ACT", "D": "AGT",
+         "B": "CGT", "N": "ACGT"}
+
+
+def _instance(rng, pat):
+    return "".join(rng.choice(IUPAC.get(c, c)) for c in pat)
+
+
+# both orders of each pair, so that a swap of the two pattern lengths (or of their match masks) shows; 64 fills the
+# kernel's word (mask ~0, high bit 1 << 63), 1 leaves only the high bit, 31 / 32 / 33 lie around the half word
+@pytest.mark.parametrize("path", ["staged", "whole_read"])
+@pytest.mark.parametrize("m_fwd,m_rev", [(1, 64), (64, 1), (2, 63), (63, 2), (31, 33), (33, 32), (32, 31), (64, 63)])
+def test_pattern_lengths_vs_oracle(gpu_ctx, m_fwd, m_rev, path):
+    """Patterns over the 15 IUPAC letters; a read is an instance of each pattern with 0..6 edits between random flanks;
+    k below, at and above the pattern lengths.  Once through the LDS-staged kernel (a5 = a3 = 100) and once through the
+    whole-read kernel (a5 = 256, a3 = 0: the 3' window is the whole read)."""
+    rng = random.Random(1000 * m_fwd + m_rev)
+    fwd = "".join(rng.choice("ACGTMRWSYKVHDBN") for _ in range(m_fwd))
+    rev = "".join(rng.choice("ACGTMRWSYKVHDBN") for _ in range(m_rev))
+    a5, a3 = (100, 100) if path == "staged" else (256, 0)
+    for k in sorted({0, 3, m_fwd, m_fwd + 3, m_rev, m_rev + 3}):
+        seqs = []
+        for _ in range(16 if m_fwd + m_rev > 100 else 24):
+            flank = ["".join(rng.choice("ACGT") for _ in range(rng.randint(0, 15))) for _ in range(3)]
+            u5 = _mut(rng, _instance(rng, fwd), rng.randint(0, 6))
+            u3 = _mut(rng, _instance(rng, rev), rng.randint(0, 6))
+            seqs.append(flank[0] + u5 + flank[1] + u3 + flank[2])
+        _check_every_window(gpu_ctx, seqs, a5, a3, k, fwd, rev)
+
+
+def test_pattern_lengths_outside_one_word_are_refused(gpu_ctx):
+    from umiclust import _lib
+    for fwd, rev in (("", "ACG"), ("ACG", ""), ("A" * 65, "ACG"), ("ACG", "A" * 65)):
+        with pytest.raises(_lib.UmiclustError) as e:
+            gpu_ctx.extract_umis(["ACGTACGT"], 73, 68, 3, fwd, rev)
+        assert e.value.code == -22  # UMICLUST_EINVAL
+    _check_every_window(gpu_ctx, ["ACGTACGT"], 73, 68, 3, "A" * 64, "C")  # and the context still works
+
+
+# slot S = (a5 + a3 + 3) & ~3: every residue of (a5 + a3) mod 4, the largest slot (252) reached two ways, and one
+# byte more (S = 256), which goes to the whole-read kernel
+@pytest.mark.parametrize("a5,a3", [(0, 1), (1, 1), (1, 2), (73, 68), (126, 126), (251, 1), (127, 126)])
+def test_staged_geometry_vs_oracle(gpu_ctx, a5, a3):
+    """Read counts on both sides of the 128 reads a workgroup stages (1, 127, 128, 129, 257) and read lengths at every
+    boundary of the window arithmetic: 0 (the reference accepts an empty sequence: no UMI), 1, below the pattern
+    length, below a3, below a5, exactly a5, below and at a5 + a3 (overlapping windows), and longer."""
+    fwd, rev = "ACVBT", "TNGA"
+    rng = random.Random(100 * a5 + a3)
+    edges = sorted({max(0, x) for x in (0, 1, len(rev) - 1, len(fwd) - 1, a3 - 1, a3, a5 - 1, a5, a5 + 1, a5 + a3 - 1,
+                                       a5 + a3, a5 + a3 + 1, a5 + a3 + 40)})
+    for n in (1, 127, 128, 129, 257):
+        seqs = []
+        for i in range(n):
+            ln = edges[i % len(edges)] if rng.random() < 0.7 else rng.randint(0, a5 + a3 + 60)
+            s = [rng.choice("ACGT") for _ in range(ln)]
+            for pat in (fwd, rev):  # an instance somewhere, often against either end
+                if ln >= len(pat) and rng.random() < 0.6:
+                    at = rng.choice([0, ln - len(pat), rng.randint(0, ln - len(pat))])
+                    s[at:at + len(pat)] = _instance(rng, pat)
+            seqs.append("".join(s))
+        if n == 1:
+            _check_every_window(gpu_ctx, [""], a5, a3, 1, fwd, rev, note="one empty read")
+        _check_every_window(gpu_ctx, seqs, a5, a3, 1, fwd, rev, note=n)
+    _check_every_window(gpu_ctx, [""] * 130, a5, a3, 1, fwd, rev, note="all empty")
+
+
+@pytest.mark.parametrize("a5,a3", [(40, 40), (256, 0)])
+def test_ties_vs_oracle(gpu_ctx, a5, a3):
+    """Windows full of equally good locations: locations[0] is the first end, and its start the leftmost one.
+    Homopolymer and dinucleotide-repeat windows under repeat patterns, two exact copies of the instance, all-N windows
+    (N equals A, C, G, T but no other code), lowercase reads under uppercase patterns (a equals A, but not V)."""
+    rng = random.Random(a5)
+    pats = ["A" * 8, "AC" * 6, "TTTVVVVTTT"]
+    seqs = []
+    for unit in ("A", "C", "T", "N", "AC", "CA", "TA", "TG", "AN", "a", "ac", "n", "Ac"):
+        for ln in (1, 7, 8, 9, 13, 40, 41, 81):
+            seqs.append((unit * ln)[:ln])
+    for pat in pats:
+        for _ in range(20):
+            u = _instance(rng, pat)
+            mid = "".join(rng.choice("ACGT") for _ in range(rng.randint(0, 6)))
+            pre = "".join(rng.choice("ACGT") for _ in range(rng.randint(0, 5)))
+            s = pre + u + mid + u + pre[::-1]  # two exact copies inside one window
+            seqs.append(s.lower() if rng.random() < 0.3 else s)
+    for fwd, rev in zip(pats, pats[1:] + pats[:1]):
+        for k in (0, 2, 8):
+            _check_every_window(gpu_ctx, seqs, a5, a3, k, fwd, rev)
+
+
 def test_single_window_helper(gpu_ctx):
     for name, s in _reads(4, 50):
         assert ge.extract_umi(s[:73], FWD, 3) == ox.extract_umi(s[:73], FWD, 3)

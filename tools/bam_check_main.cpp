@@ -5,7 +5,8 @@
 //   bam_check <in.bam> <out prefix> <threads>
 //       inflates the file, parses the header, finds the record offsets, scans every record and prints
 //         refs=<n> then one `ref <name> <length>` line per reference,
-//         records=<n> then per record `rec <r> cls ref l_seq reference_length cols nm nm_present cs_len bad cs=<string>`,
+//         records=<n>, `fields=ok` or `fields=<message of bam::check_record_fields>` (what umiclust_region_split
+//         refuses before its kernels run), then per record `rec <r> cls ref l_seq reference_length cols nm nm_present cs_len bad cs=<string>`,
 //       then round-trips the writer twice -- every record kept (<prefix>.all.bam) and every second record kept
 //       (<prefix>.alt.bam) -- re-inflates both and compares them with the header bytes + the kept records; prints
 //       `roundtrip ok`.  Exit status 0, or 2 with `err=<message>` when the file is not BGZF / BAM.
@@ -42,6 +43,7 @@ int main(int argc, char** argv) {
   printf("refs=%zu\n", hdr.ref_name.size());
   for (size_t r = 0; r < hdr.ref_name.size(); r++) printf("ref %s %lld\n", hdr.ref_name[r].c_str(), (long long)hdr.ref_len[r]);
   printf("records=%zu\n", roff.size());
+  printf("fields=%s\n", bam::check_record_fields(raw.data(), roff, err) ? "ok" : err.c_str());
   for (size_t r = 0; r < roff.size(); r++) {
     bam::ScanRow s;
     bam::scan_record(raw.data(), roff[r], bam::cs_seed(0), ~0ull, s);
