@@ -1,0 +1,181 @@
+// ctx.h -- the context core: what every entry point of the C ABI (include/umiclust.h) needs of a context, and the
+// state of the drop-ins (dropin_*.cpp), which share nothing else with clustering.  driver.cpp derives umiclust_ctx from
+// uc::Ctx; the drop-ins see umiclust_ctx only as the ABI's incomplete type and reach this base through uc::core.
+#pragma once
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/umiclust.h"
+#include "bam_host.h"
+#include "host_io.h"
+#include "tunables.h"
+#include "umiclust_internal.h"
+
+namespace uc {
+
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// An owned array in device memory (DevBuf) or in pinned host memory (PinBuf), grown by ensure() and never shrunk.
+// Kernels write pinned buffers directly (pinned host memory is device-accessible); the host reads them only after the
+// writing kernel's completion event, and copies what it scans into pageable vectors first.
+template <typename T, bool kPinned>
+struct HipBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  HipBuf() = default;
+  HipBuf(const HipBuf&) = delete;
+  HipBuf& operator=(const HipBuf&) = delete;
+  ~HipBuf() { release(); }
+  void release() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    n = 0;
+  }
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    release();
+    const size_t c = count ? count : 1;
+    void** q = reinterpret_cast<void**>(&p);
+    const hipError_t e = kPinned ? hipHostMalloc(q, c * sizeof(T), hipHostMallocDefault) : hipMalloc(q, c * sizeof(T));
+    if (e == hipSuccess) n = c;
+    return e;
+  }
+};
+template <typename T>
+using DevBuf = HipBuf<T, false>;
+template <typename T>
+using PinBuf = HipBuf<T, true>;
+// c->hip(b.ensure(count), "alloc") for each buffer, in order
+template <typename C, typename... B>
+void alloc_each(C* c, size_t count, B&... b) {
+  (c->hip(b.ensure(count), "alloc"), ...);
+}
+
+struct Fail {
+  int code;
+};
+
+// UMI extraction (f1): gathered adapter windows, kept across calls
+struct ExtractState {
+  PinBuf<char> win;
+  PinBuf<uint8_t> len;
+  DevBuf<char> dwin;
+  DevBuf<uint8_t> dlen;
+  DevBuf<int32_t> dout;
+  DevBuf<ExtractPatterns> dpat;
+};
+
+// quality filtering (f5): two pinned staging slots (one being gathered while the other is on the device), one set
+// of device buffers, kept across calls
+struct FqState {
+  struct Slot {
+    PinBuf<uint8_t> q, lo, hi;
+    PinBuf<int64_t> offs, ee;
+  } slot[2];
+  DevBuf<uint8_t> dq, dlo, dhi;
+  DevBuf<int64_t> doffs, dee;
+  DevBuf<uint64_t> dtab;
+  hipEvent_t ev[3] = {};  // copy begin, kernel begin, kernel end
+  ~FqState() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
+// the columns of the device scan
+struct BamSession {
+  bool open = false;
+  std::vector<uint8_t> raw;
+  bam::Header hdr;
+  std::vector<int64_t> roff, reflen, cols, nm, cs_off, g_count, g_rep;
+  std::vector<int32_t> ref, l_seq, cs_len, cs_group;
+  std::vector<int8_t> cls;
+  std::vector<uint8_t> nm_present;
+  int64_t n_reruns = 0, first_bad = -1;
+  double t_inflate = 0, t_h2d = 0, t_dev = 0;
+};
+
+struct Ctx {
+  int dev = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::string err;
+  Tunables tun;  // the UMICLUST_* switches, as umiclust_create read them (tunables.h)
+  umiclust_stats stats{};
+  ExtractState ex;
+  FqState fq;
+  BamSession bs;
+  // runs after the derived context's destructor (which selects the device) and before the members above are freed
+  ~Ctx() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (st) (void)hipStreamDestroy(st);
+  }
+
+  void fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    err = buf;
+    throw Fail{code};
+  }
+  void hip(hipError_t e, const char* what) {
+    if (e != hipSuccess) fail(UMICLUST_EDEVICE, "%s: %s", what, hipGetErrorString(e));
+  }
+};
+
+// the core of a context (driver.cpp: the upcast); null for null
+Ctx* core(umiclust_ctx* c);
+
+// A packed sequence set on the device: the bytes of records [0, n) into d_seq and their offsets, relative to offs[0],
+// into d_off, both copies queued on st.  `rel` is what the offset copy reads: it must live until st has run it.
+inline void upload_seqs(Ctx* c, const char* seqs, const int64_t* offs, int64_t n, DevBuf<char>& d_seq,
+                        DevBuf<int64_t>& d_off, std::vector<int64_t>& rel, hipStream_t st) {
+  const int64_t bytes = n > 0 ? offs[n] - offs[0] : 0;
+  rel.resize((size_t)n + 1);
+  for (int64_t i = 0; i <= n; i++) rel[i] = n > 0 ? offs[i] - offs[0] : 0;
+  c->hip(d_seq.ensure((size_t)bytes + 1), "alloc");
+  c->hip(d_off.ensure((size_t)n + 1), "alloc");
+  if (bytes > 0) c->hip(hipMemcpyAsync(d_seq.p, seqs + offs[0], (size_t)bytes, hipMemcpyHostToDevice, st), "h2d");
+  c->hip(hipMemcpyAsync(d_off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st), "h2d");
+}
+
+// the records of one packed set appended to `all`, their end offsets to `off` (which starts as {0})
+inline void append_set(const char* s, const int64_t* o, int64_t n, std::vector<char>& all, std::vector<int64_t>& off) {
+  for (int64_t i = 0; i < n; i++) {
+    all.insert(all.end(), s + o[i], s + o[i + 1]);
+    off.push_back((int64_t)all.size());
+  }
+}
+
+}  // namespace uc
+
+// Body of an entry point: selects the device; what the body throws becomes the ABI's error code and last-error text.
+#define UC_GUARD(c, ...)                                \
+  do {                                                  \
+    if (!(c)) return UMICLUST_EINVAL;                   \
+    try {                                               \
+      (void)hipSetDevice((c)->dev);                     \
+      __VA_ARGS__                                       \
+    } catch (const uc::Fail& f__) {                     \
+      return f__.code;                                  \
+    } catch (const uc::io::IoError& e__) {              \
+      (c)->err = e__.msg;                               \
+      return e__.code;                                  \
+    } catch (const std::bad_alloc&) {                   \
+      (c)->err = "host allocation failed";              \
+      return UMICLUST_ENOMEM;                           \
+    } catch (...) {                                     \
+      (c)->err = "unexpected exception";                \
+      return UMICLUST_EDEVICE;                          \
+    }                                                   \
+  } while (0)

@@ -1,4 +1,5 @@
-// driver.cpp -- host side of the MI355X UMI clustering hot path and the C ABI (include/umiclust.h).
+// driver.cpp -- host side of the MI355X UMI clustering hot path, the context's life cycle and the kernel-level probes
+// of the C ABI (include/umiclust.h).  The drop-ins (f1, f3-f6) are dropin_*.cpp, on the context core of ctx.h.
 //
 // Replaces the `vsearch --cluster_fast` subprocess of
 // /root/reference/ont_tcr_consensus/vsearch_umi_cluster.py:21-54 (round 1) and :71-97 (round 2).
@@ -26,102 +27,29 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cerrno>
-#include <chrono>
-#include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fcntl.h>
 #include <string>
 #include <sys/mman.h>
-#include <sys/stat.h>
-#include <condition_variable>
 #include <exception>
-#include <functional>
 #include <memory>
 #include <mutex>
-#include <pthread.h>
 #include <sched.h>
 #include <thread>
 #include <unistd.h>
-#include <unordered_map>
 #include <vector>
-#include <zlib.h>
 
-#include "../../include/umiclust.h"
-#include "bam_host.h"
-#include "fastq_filter.h"
-#include "host_io.h"
+#include "ctx.h"
 #include "plan.h"
 #include "resolve.h"
-#include "tunables.h"
-#include "umiclust_internal.h"
 
 using namespace uc;
 using uc::io::Fasta;
 using uc::io::io_threads;
 using uc::io::parallel_for;
-using uc::io::pjoin;
-using uc::io::Sv;
-using uc::io::split1;
 
 namespace {
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    release();
-    size_t c = count ? count : 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), c * sizeof(T));
-    if (e == hipSuccess) n = c;
-    return e;
-  }
-};
-
-template <typename T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  PinBuf() = default;
-  PinBuf(const PinBuf&) = delete;
-  PinBuf& operator=(const PinBuf&) = delete;
-  ~PinBuf() { release(); }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  // Kernels write these buffers directly (pinned host memory is device-accessible); the host reads
-  // them only after the writing kernel's completion event, and copies what it scans into pageable
-  // vectors first.
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    release();
-    size_t c = count ? count : 1;
-    const unsigned flags = hipHostMallocDefault;
-    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), c * sizeof(T), flags);
-    if (e == hipSuccess) n = c;
-    return e;
-  }
-};
 
 // Policy constants of the host side, with what they were measured against (the block planner's are in plan.h)
 constexpr int32_t kDelta = 8192;  // centroids in the per-block delta tile before folding into base
@@ -178,10 +106,6 @@ inline size_t tile_cap(int64_t nseq) {
   return (size_t)((raw + 7 * std::min<int64_t>(kBins, raw) + 64) & ~int64_t(7));
 }
 
-struct Fail {
-  int code;
-};
-
 // One greedy block in flight: its own peer tile, device outputs and pinned mirrors, so the device
 // runs block k+1 while the host resolves block k.
 struct Pass {
@@ -237,7 +161,6 @@ struct Pass {
 }  // namespace
 
 static std::atomic<int> g_live_ctx{0};  // contexts alive in this process (L3Pin)
-struct umiclust_ctx;
 
 // Process-wide timeline of the counting launches (kind 0) and the alignment chains (kind 1), for
 // umiclust_timeline: with several contexts (lanes) on one device their HIP-event brackets overlap, so the sum of
@@ -298,36 +221,17 @@ static void tl_add(int dev, int kind, hipEvent_t a, hipEvent_t b) {
   }
 }
 
-struct umiclust_ctx {
-  int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::string err;
-
+// Clustering's state, on the core every entry point shares (ctx.h: device, main stream, error text, tunables, stats
+// and the drop-ins' own state).
+struct umiclust_ctx : uc::Ctx {
   umiclust_params p{};
   Scoring sc{};
   int both = 2;
   bool ambig = false;             // some kept sequence holds a non-ACGT (IUPAC) symbol
   bool loaded = false;
   bool clustered = false;
+  bool counted = false;           // this context is one of g_live_ctx
   DevBuf<unsigned long long> pf_prof;  // prefilter phase clocks (UMICLUST_PFPROF)
-  // UMI extraction (f1): gathered adapter windows, kept across calls
-  PinBuf<char> ex_win;
-  PinBuf<uint8_t> ex_len;
-  DevBuf<char> ex_dwin;
-  DevBuf<uint8_t> ex_dlen;
-  DevBuf<int32_t> ex_dout;
-  DevBuf<ExtractPatterns> ex_dpat;
-  // quality filtering (f5): two pinned staging slots (one being gathered while the other is on the device), one set
-  // of device buffers, kept across calls
-  struct FqSlot {
-    PinBuf<uint8_t> q, lo, hi;
-    PinBuf<int64_t> offs, ee;
-  } fq_slot[2];
-  DevBuf<uint8_t> fq_dq, fq_dlo, fq_dhi;
-  DevBuf<int64_t> fq_doffs, fq_dee;
-  DevBuf<uint64_t> fq_dtab;
-  hipEvent_t fq_ev[3] = {};  // copy begin, kernel begin, kernel end
 
   // input (host copies kept only for the file path outputs).  A load holds one or more independent
   // region bins (umiclust_load_bins): bin b is input records [bin_in[b], bin_in[b+1]) and sorted
@@ -388,7 +292,6 @@ struct umiclust_ctx {
   Pass pass[kPeerTiles];          // passes in flight (kDepth of them, <= kPeerTiles)
   Tile blk_tile[kPeerTiles + 1], solo_tile;  // per-block peer tiles (ring of depth + 1), overflow re-runs
   Tile round_tile[2];             // O4 batched rounds: a pass's window from its first query's round start
-  Tunables tun;                   // the UMICLUST_* switches, as umiclust_create read them (tunables.h)
   DevBuf<int32_t> d_seq2ord;      // [seqno - bin start] centroid ordinal or -1 (the merge's flagged hits)
   PinBuf<int32_t> h_seq2ord;
   hipEvent_t a_ev[4][3] = {};     // counting halves, ring by block: begin / end / spare
@@ -440,7 +343,6 @@ struct umiclust_ctx {
     std::vector<int64_t> cons_off;
   };
   std::vector<BinOut> bout;
-  umiclust_stats stats{};
   // k_pack writes the outcomes and records straight into pinned host memory (true) or into device buffers copied by
   // DMA (false).  Set per clustering call: DMA with one context in the process (config 2: 4.33-4.36 vs 4.21-4.22 M
   // UMIs/s, the direct PCIe writes held k_pack at 133 us on the pass chain), direct with several (config 3, 8 lanes:
@@ -484,32 +386,7 @@ struct umiclust_ctx {
   DevBuf<int32_t> t_cstart, t_mseq, t_mops, t_over;
   DevBuf<char> t_cons;
   hipEvent_t tev[2] = {nullptr, nullptr};
-  // BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
-  // the columns of the device scan
-  struct BamSession {
-    bool open = false;
-    std::vector<uint8_t> raw;
-    uc::bam::Header hdr;
-    std::vector<int64_t> roff, reflen, cols, nm, cs_off, g_count, g_rep;
-    std::vector<int32_t> ref, l_seq, cs_len, cs_group;
-    std::vector<int8_t> cls;
-    std::vector<uint8_t> nm_present;
-    int64_t n_reruns = 0, first_bad = -1;
-    double t_inflate = 0, t_h2d = 0, t_dev = 0;
-  } bs;
-
-  void fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    err = buf;
-    throw Fail{code};
-  }
-  void hip(hipError_t e, const char* what) {
-    if (e != hipSuccess) fail(UMICLUST_EDEVICE, "%s: %s", what, hipGetErrorString(e));
-  }
+  ~umiclust_ctx();  // umiclust_destroy, and every failure of umiclust_create (ev0 / ev1 / st go with the core)
 };
 
 namespace {
@@ -2102,11 +1979,8 @@ void stage_impl(umiclust_ctx* c, const char* seqs, const int64_t* offs, int64_t 
   const int64_t bytes = n > 0 ? offs[n] - offs[0] : 0;
   c->hip(c->d_ascii.ensure((size_t)bytes + 1), "alloc ascii");
   c->hip(c->d_offs.ensure((size_t)n + 1), "alloc offs");
-  std::vector<int64_t> rel((size_t)n + 1);
-  for (int64_t i = 0; i <= n; i++) rel[i] = offs[i] - offs[0];
-  if (bytes > 0)
-    c->hip(hipMemcpyAsync(c->d_ascii.p, seqs + offs[0], (size_t)bytes, hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(hipMemcpyAsync(c->d_offs.p, rel.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->st), "h2d");
+  std::vector<int64_t> rel;
+  upload_seqs(c, seqs, offs, n, c->d_ascii, c->d_offs, rel, c->st);  // allocated above: the same two copies
   c->hip(hipStreamSynchronize(c->st), "sync stage");  // `rel` goes out of scope
   c->staged = true;
 }
@@ -2430,6 +2304,26 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
 
 }  // namespace
 
+uc::Ctx* uc::core(umiclust_ctx* c) { return c; }
+
+umiclust_ctx::~umiclust_ctx() {
+  join_release();
+  (void)hipSetDevice(dev);
+  for (Tile* t : tiles) delete t;
+  for (hipEvent_t e : {evb[0], evb[1], tev[0], tev[1], pt_ev, ix_done})
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : ix_events) {
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
+  for (hipStream_t s : {st_b, st_copy, st_al})
+    if (s) (void)hipStreamDestroy(s);
+  for (auto& r : a_ev)
+    for (hipEvent_t e : r)
+      if (e) (void)hipEventDestroy(e);
+  if (counted) io::set_live_contexts(--g_live_ctx);
+}
+
 // ====================================================================== C ABI
 extern "C" {
 
@@ -2483,16 +2377,17 @@ static int al_priority() {
 }
 
 umiclust_ctx* umiclust_create(int32_t device_id, int32_t* err) {
+  // every early return: the context, if there is one, releases what it holds so far and gives its count back
+  auto failed = [&](umiclust_ctx* c, int32_t code) -> umiclust_ctx* {
+    delete c;
+    if (err) *err = code;
+    return nullptr;
+  };
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    if (err) *err = UMICLUST_EDEVICE;
-    return nullptr;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev)
+    return failed(nullptr, UMICLUST_EDEVICE);
   umiclust_ctx* c = new (std::nothrow) umiclust_ctx();
-  if (!c) {
-    if (err) *err = UMICLUST_ENOMEM;
-    return nullptr;
-  }
+  if (!c) return failed(nullptr, UMICLUST_ENOMEM);
   c->dev = device_id;
   if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&c->st_b, hipStreamNonBlocking) != hipSuccess ||
@@ -2504,21 +2399,15 @@ umiclust_ctx* umiclust_create(int32_t device_id, int32_t* err) {
           for (hipEvent_t& e : P.ev)
             if (hipEventCreate(&e) != hipSuccess) return true;
         return false;
-      }()) {
-    delete c;
-    if (err) *err = UMICLUST_EDEVICE;
-    return nullptr;
-  }
+      }())
+    return failed(c, UMICLUST_EDEVICE);
   warn_unknown_env();
   c->tun = read_tunables();
   io::set_live_contexts(++g_live_ctx);
-  if (c->tun.pf_prof) {
-    if (c->pf_prof.ensure(24) != hipSuccess || hipMemset(c->pf_prof.p, 0, 24 * sizeof(unsigned long long)) != hipSuccess) {
-      delete c;
-      if (err) *err = UMICLUST_EDEVICE;
-      return nullptr;
-    }
-  }
+  c->counted = true;
+  if (c->tun.pf_prof &&
+      (c->pf_prof.ensure(24) != hipSuccess || hipMemset(c->pf_prof.p, 0, 24 * sizeof(unsigned long long)) != hipSuccess))
+    return failed(c, UMICLUST_EDEVICE);
   if (err) *err = UMICLUST_OK;
   return c;
 }
@@ -2548,56 +2437,9 @@ int32_t umiclust_wait_host(umiclust_ctx* c) {
   return UMICLUST_OK;
 }
 
-void umiclust_destroy(umiclust_ctx* c) {
-  if (!c) return;
-  c->join_release();
-  io::set_live_contexts(--g_live_ctx);
-  (void)hipSetDevice(c->dev);
-  for (Tile* t : c->tiles) delete t;
-  c->tiles.clear();
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  for (hipEvent_t e : c->evb)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->fq_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ix_events) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  if (c->st_b) (void)hipStreamDestroy(c->st_b);
-  if (c->pt_ev) (void)hipEventDestroy(c->pt_ev);
-  if (c->st_copy) (void)hipStreamDestroy(c->st_copy);
-  if (c->st_al) (void)hipStreamDestroy(c->st_al);
-  if (c->ix_done) (void)hipEventDestroy(c->ix_done);
-  for (auto& r : c->a_ev)
-    for (hipEvent_t e : r)
-      if (e) (void)hipEventDestroy(e);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;
-}
+void umiclust_destroy(umiclust_ctx* c) { delete c; }
 
 const char* umiclust_last_error(const umiclust_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-#define UC_GUARD(c, ...)                                \
-  do {                                                  \
-    if (!(c)) return UMICLUST_EINVAL;                   \
-    try {                                               \
-      (void)hipSetDevice((c)->dev);                     \
-      __VA_ARGS__                                       \
-    } catch (const Fail& f__) {                         \
-      return f__.code;                                  \
-    } catch (const uc::io::IoError& e__) {              \
-      (c)->err = e__.msg;                               \
-      return e__.code;                                  \
-    } catch (const std::bad_alloc&) {                   \
-      (c)->err = "host allocation failed";              \
-      return UMICLUST_ENOMEM;                           \
-    } catch (...) {                                     \
-      (c)->err = "unexpected exception";                \
-      return UMICLUST_EDEVICE;                          \
-    }                                                   \
-  } while (0)
 
 int64_t umiclust_run_fasta(umiclust_ctx* c, const umiclust_params* p, const char* in_fasta,
                            const char* clusters_prefix, const char* consout, const char* log_path,
@@ -2904,6 +2746,41 @@ int32_t umiclust_pass(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32
   });
 }
 
+// What umiclust_align_pairs, umiclust_consensus and umiclust_prep share: n records on the device, beside whatever load
+// the context holds, and k_prep over them.  The uploads have completed when probe_prep returns, the kernel is queued.
+struct ProbeSeqs {
+  DevBuf<char> d_a, d_m;
+  DevBuf<int64_t> d_o;
+  DevBuf<uint32_t> d_codes, d_amb;
+  DevBuf<uint8_t> d_lens, d_nk;
+  DevBuf<uint16_t> d_km;
+  DevSeqs ds() const { return DevSeqs{d_codes.p, d_lens.p, d_km.p, d_nk.p}; }
+};
+static void probe_prep(umiclust_ctx* c, ProbeSeqs& S, const char* seqs, const int64_t* offs, int64_t n, int dust,
+                       bool masked, bool amb) {
+  std::vector<int64_t> rel;
+  upload_seqs(c, seqs, offs, n, S.d_a, S.d_o, rel, c->st);
+  c->hip(hipStreamSynchronize(c->st), "sync");  // `rel` goes out of scope
+  c->hip(S.d_codes.ensure((size_t)n * 2 * kCodeWords + 1), "alloc");
+  c->hip(S.d_lens.ensure((size_t)n + 1), "alloc");
+  c->hip(S.d_km.ensure((size_t)n * 2 * kKmerStride + 1), "alloc");
+  c->hip(S.d_nk.ensure((size_t)n * 2 + 1), "alloc");
+  if (masked) c->hip(S.d_m.ensure((size_t)n * kMaxLen + 1), "alloc");
+  if (amb) {
+    c->hip(S.d_amb.ensure(2), "alloc");
+    c->hip(hipMemsetAsync(S.d_amb.p, 0, 8, c->st), "memset");
+  }
+  c->hip(launch_prep(S.d_a.p, S.d_o.p, nullptr, (int32_t)n, dust, S.d_codes.p, S.d_lens.p, S.d_km.p, S.d_nk.p,
+                     masked ? S.d_m.p : nullptr, amb ? S.d_amb.p : nullptr, c->st),
+         "prep");
+}
+// an alignment result word: matches, the alignment's internal length, the score
+static void unpack_result(uint32_t r, int64_t k, int32_t* matches, int32_t* internal_len, int32_t* score) {
+  if (matches) matches[k] = (int32_t)(r & 0xffu);
+  if (internal_len) internal_len[k] = (int32_t)((r >> 8) & 0xffu);
+  if (score) score[k] = (int32_t)(int16_t)(r >> 16);
+}
+
 int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const char* q, const int64_t* q_off,
                              const char* t, const int64_t* t_off, int64_t npairs, int32_t* score,
                              int32_t* matches, int32_t* internal_len, char* cigar_ops, int32_t ops_stride,
@@ -2916,41 +2793,20 @@ int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const ch
     validate(c, pp);
     // load queries then targets as one sequence set without filtering/sorting
     std::vector<char> all;
-    std::vector<int64_t> off;
-    off.push_back(0);
-    for (int64_t k = 0; k < npairs; k++) {
-      all.insert(all.end(), q + q_off[k], q + q_off[k + 1]);
-      off.push_back((int64_t)all.size());
-    }
-    for (int64_t k = 0; k < npairs; k++) {
-      all.insert(all.end(), t + t_off[k], t + t_off[k + 1]);
-      off.push_back((int64_t)all.size());
-    }
+    std::vector<int64_t> off{0};
+    append_set(q, q_off, npairs, all, off);
+    append_set(t, t_off, npairs, all, off);
     const int64_t ns = 2 * npairs;
     for (int64_t i = 0; i < ns; i++)
       if (off[i + 1] - off[i] < 1 || off[i + 1] - off[i] > kMaxLen) c->fail(UMICLUST_ERANGE, "pair sequence length");
     Scoring sc = to_scoring(pp);
-    DevBuf<char> d_a;
-    DevBuf<int64_t> d_o;
-    DevBuf<uint32_t> d_codes, d_pq, d_pt, d_out;
-    DevBuf<uint8_t> d_lens, d_nk, d_ops;
-    DevBuf<uint16_t> d_km, d_nops;
-    c->hip(d_a.ensure(all.size() + 1), "alloc");
-    c->hip(d_o.ensure(off.size()), "alloc");
-    c->hip(d_codes.ensure((size_t)ns * 2 * kCodeWords + 1), "alloc");
-    c->hip(d_lens.ensure((size_t)ns + 1), "alloc");
-    c->hip(d_km.ensure((size_t)ns * 2 * kKmerStride + 1), "alloc");
-    c->hip(d_nk.ensure((size_t)ns * 2 + 1), "alloc");
-    if (!all.empty()) c->hip(hipMemcpy(d_a.p, all.data(), all.size(), hipMemcpyHostToDevice), "h2d");
-    c->hip(hipMemcpy(d_o.p, off.data(), off.size() * 8, hipMemcpyHostToDevice), "h2d");
-    DevBuf<uint32_t> d_amb;
-    c->hip(d_amb.ensure(1), "alloc");
-    c->hip(hipMemsetAsync(d_amb.p, 0, 4, c->st), "memset");
-    c->hip(launch_prep(d_a.p, d_o.p, nullptr, (int32_t)ns, 0, d_codes.p, d_lens.p, d_km.p, d_nk.p, nullptr,
-                       d_amb.p, c->st),
-           "prep");
+    ProbeSeqs S;
+    DevBuf<uint32_t> d_pq, d_pt, d_out;
+    DevBuf<uint8_t> d_ops;
+    DevBuf<uint16_t> d_nops;
+    probe_prep(c, S, all.data(), off.data(), ns, 0, false, true);
     uint32_t amb = 0;
-    c->hip(hipMemcpyAsync(&amb, d_amb.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
+    c->hip(hipMemcpyAsync(&amb, S.d_amb.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
     c->hip(hipStreamSynchronize(c->st), "sync");
     // pairs grouped by query length (the aligner is compiled per query length)
     std::vector<int64_t> ord(npairs);
@@ -2974,7 +2830,7 @@ int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const ch
       c->hip(hipMemcpyAsync(d_pq.p, pq.data(), npairs * 4, hipMemcpyHostToDevice, c->st), "h2d");
       c->hip(hipMemcpyAsync(d_pt.p, pt.data(), npairs * 4, hipMemcpyHostToDevice, c->st), "h2d");
     }
-    DevSeqs ds{d_codes.p, d_lens.p, d_km.p, d_nk.p};
+    const DevSeqs ds = S.ds();
     std::vector<uint32_t> sres(npairs);
     std::vector<uint8_t> ops;
     std::vector<uint16_t> nops;
@@ -3016,11 +2872,7 @@ int32_t umiclust_align_pairs(umiclust_ctx* c, const umiclust_params* p, const ch
         if (ops_len) ops_len[k] = n;
       }
     }
-    for (int64_t k = 0; k < npairs; k++) {
-      if (matches) matches[k] = (int32_t)(res[k] & 0xffu);
-      if (internal_len) internal_len[k] = (int32_t)((res[k] >> 8) & 0xffu);
-      if (score) score[k] = (int32_t)(int16_t)(res[k] >> 16);
-    }
+    for (int64_t k = 0; k < npairs; k++) unpack_result(res[k], k, matches, internal_len, score);
     return UMICLUST_OK;
   });
 }
@@ -3043,14 +2895,11 @@ int32_t umiclust_consensus(umiclust_ctx* c, const umiclust_params* p, const char
     validate(c, pp);
     const Scoring sc = to_scoring(pp);
     const int32_t ns = (int32_t)n, K = nclusters;
-    // the records: lengths, and offsets from the first record's byte
-    std::vector<uint8_t> hlen((size_t)ns);
-    std::vector<int64_t> off((size_t)ns + 1, 0);
+    std::vector<uint8_t> hlen((size_t)ns);  // the records' lengths
     for (int32_t i = 0; i < ns; i++) {
       const int64_t L = offsets[i + 1] - offsets[i];
       if (L < 1 || L > kMaxLen) c->fail(UMICLUST_ERANGE, "record %d: length %lld outside 1..%d", i, (long long)L, kMaxLen);
       hlen[i] = (uint8_t)L;
-      off[i + 1] = offsets[i + 1] - offsets[0];
     }
     // the clusters: every record in at most one, its centroid first
     if (K > 0 && cstart[0] != 0) c->fail(UMICLUST_EINVAL, "cstart[0] must be 0");
@@ -3089,24 +2938,9 @@ int32_t umiclust_consensus(umiclust_ctx* c, const umiclust_params* p, const char
                     nM + nD, (int)hlen[member[cstart[k]]], (int)hlen[member[x]]);
         }
     // the sequences' codes, beside whatever load the context holds
-    DevBuf<char> d_a;
-    DevBuf<int64_t> d_o;
-    DevBuf<uint32_t> d_codes, d_amb;
-    DevBuf<uint8_t> d_lens, d_nk;
-    DevBuf<uint16_t> d_km;
-    c->hip(d_a.ensure((size_t)off[ns] + 1), "alloc");
-    c->hip(d_o.ensure(off.size()), "alloc");
-    c->hip(d_codes.ensure((size_t)ns * 2 * kCodeWords + 1), "alloc");
-    c->hip(d_lens.ensure((size_t)ns + 1), "alloc");
-    c->hip(d_km.ensure((size_t)ns * 2 * kKmerStride + 1), "alloc");
-    c->hip(d_nk.ensure((size_t)ns * 2 + 1), "alloc");
-    c->hip(d_amb.ensure(2), "alloc");
-    if (off[ns] > 0) c->hip(hipMemcpy(d_a.p, seqs + offsets[0], (size_t)off[ns], hipMemcpyHostToDevice), "h2d");
-    c->hip(hipMemcpy(d_o.p, off.data(), off.size() * 8, hipMemcpyHostToDevice), "h2d");
-    c->hip(hipMemsetAsync(d_amb.p, 0, 8, c->st), "memset");
-    c->hip(launch_prep(d_a.p, d_o.p, nullptr, ns, 0, d_codes.p, d_lens.p, d_km.p, d_nk.p, nullptr, d_amb.p, c->st),
-           "prep");
-    const DevSeqs ds{d_codes.p, d_lens.p, d_km.p, d_nk.p};
+    ProbeSeqs S;
+    probe_prep(c, S, seqs, offsets, ns, 0, false, true);
+    const DevSeqs ds = S.ds();
     // slots and launches as ClusterRun::tw_launch plans them, records standing for the sorted seqnos
     ensure_traceback_buffers(c, ns);
     std::vector<int32_t> slot((size_t)ns, -1);
@@ -3156,9 +2990,7 @@ int32_t umiclust_consensus(umiclust_ctx* c, const umiclust_params* p, const char
         ops_out_len[x] = len;
         if (len > 0) memcpy(ops_out + (size_t)x * ops_stride, hops.data() + (size_t)sl * kOpsStride + kOpsStride - len, (size_t)len);
       }
-      if (matches) matches[x] = (int32_t)(r & 0xffu);
-      if (internal_len) internal_len[x] = (int32_t)((r >> 8) & 0xffu);
-      if (score) score[x] = (int32_t)(int16_t)(r >> 16);
+      unpack_result(r, x, matches, internal_len, score);
     }
     if (over) c->fail(UMICLUST_ERANGE, kConsOverMsg, over);
     int64_t total = 0;
@@ -3176,839 +3008,21 @@ int32_t umiclust_consensus(umiclust_ctx* c, const umiclust_params* p, const char
   });
 }
 
-// ---------------------------------------------------------------- region overlap (§8f f3)
-namespace {
-// n sequences of nreg regions on the device, one table pass (re-seeded on a 64-bit hash collision)
-struct OvRun {
-  DevBuf<char> d_seq;
-  DevBuf<int64_t> d_off, d_rs, d_slot;
-  DevBuf<uint64_t> d_hash;
-  DevBuf<int32_t> d_reg;
-  DevBuf<unsigned long long> d_keys, d_rep;
-  DevBuf<uint32_t> d_cnt, d_start, d_cursor, d_bsum, d_members, d_coll, d_big, d_nbig;
-  OvBuffers B{};
-  uint64_t mask = 0;
-};
-
-void overlap_table(umiclust_ctx* c, OvRun& R, const char* seqs, const int64_t* offs, int64_t n,
-                   const int64_t* rstart, int32_t nreg, bool csr) {
-  if (n < 0 || nreg < 1 || (n > 0 && (!seqs || !offs)) || !rstart) c->fail(UMICLUST_EINVAL, "null argument");
-  if (rstart[0] != 0 || rstart[nreg] != n) c->fail(UMICLUST_EINVAL, "region boundaries must span [0, n]");
-  for (int32_t r = 0; r < nreg; r++)
-    if (rstart[r + 1] < rstart[r]) c->fail(UMICLUST_EINVAL, "region boundaries must not decrease");
-  if (n > (int64_t)UINT32_MAX / 2) c->fail(UMICLUST_ERANGE, "too many sequences");
-  uint64_t m = 1024;
-  while (m < (uint64_t)(2 * n)) m <<= 1;
-  R.mask = m - 1;
-  const int64_t bytes = n > 0 ? offs[n] - offs[0] : 0;
-  std::vector<int64_t> rel((size_t)n + 1);
-  for (int64_t i = 0; i <= n; i++) rel[i] = n > 0 ? offs[i] - offs[0] : 0;
-  c->hip(R.d_seq.ensure((size_t)bytes + 1), "alloc");
-  c->hip(R.d_off.ensure((size_t)n + 1), "alloc");
-  c->hip(R.d_rs.ensure((size_t)nreg + 1), "alloc");
-  c->hip(R.d_slot.ensure((size_t)n + 1), "alloc");
-  c->hip(R.d_hash.ensure((size_t)n + 1), "alloc");
-  c->hip(R.d_reg.ensure((size_t)n + 1), "alloc");
-  c->hip(R.d_keys.ensure(m), "alloc");
-  c->hip(R.d_rep.ensure(m), "alloc");
-  c->hip(R.d_cnt.ensure(m), "alloc");
-  c->hip(R.d_start.ensure(m + 1), "alloc");
-  c->hip(R.d_cursor.ensure(m), "alloc");
-  c->hip(R.d_bsum.ensure(m / 1024 + 1), "alloc");
-  c->hip(R.d_members.ensure((size_t)n + 1), "alloc");
-  c->hip(R.d_coll.ensure(1), "alloc");
-  c->hip(R.d_big.ensure((size_t)n / (kOvSmallBucket + 1) + 1), "alloc");
-  c->hip(R.d_nbig.ensure(1), "alloc");
-  if (bytes > 0) c->hip(hipMemcpyAsync(R.d_seq.p, seqs + offs[0], (size_t)bytes, hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(hipMemcpyAsync(R.d_off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(hipMemcpyAsync(R.d_rs.p, rstart, ((size_t)nreg + 1) * 8, hipMemcpyHostToDevice, c->st), "h2d");
-  R.B = OvBuffers{R.d_hash.p, R.d_reg.p, R.d_keys.p, R.d_rep.p, R.d_slot.p, R.d_cnt.p, R.d_start.p, R.d_cursor.p,
-                  R.d_bsum.p, R.d_members.p, R.d_coll.p, R.d_big.p, R.d_nbig.p};
-  // a 64-bit collision between two different sequences is detected exactly; the next seed is tried
-  const uint64_t seeds[4] = {0x243f6a8885a308d3ull, 0x13198a2e03707344ull, 0xa4093822299f31d0ull,
-                             0x082efa98ec4e6c89ull};
-  const bool test_collide = env_overlap_test_collide();  // first pass: 8-bit hashes
-  for (int k = 0; k < 4; k++) {
-    uint32_t coll = 0;
-    const uint64_t hmask = (test_collide && k == 0) ? 0xffull : ~0ull;
-    c->hip(launch_overlap_table(R.d_seq.p, R.d_off.p, n, R.d_rs.p, nreg, seeds[k], hmask, R.mask, R.B, csr, &coll,
-                                c->st),
-           "overlap table");
-    c->stats.n_overlap_passes++;
-    if (!coll) return;
-  }
-  c->fail(UMICLUST_EDEVICE, "overlap: 64-bit hash collisions under four seeds");
-}
-}  // namespace
-
-int32_t umiclust_overlap_counts(umiclust_ctx* c, const char* s1, const int64_t* off1, int64_t n1, const char* s2,
-                                const int64_t* off2, int64_t n2, int64_t* counts) {
-  UC_GUARD(c, {
-    if (n1 < 0 || n2 < 0 || (n1 > 0 && (!s1 || !off1 || !counts)) || (n2 > 0 && (!s2 || !off2)))
-      c->fail(UMICLUST_EINVAL, "null argument");
-    // one buffer: set 1 then set 2
-    std::vector<char> all;
-    std::vector<int64_t> off{0};
-    for (int64_t i = 0; i < n1; i++) {
-      all.insert(all.end(), s1 + off1[i], s1 + off1[i + 1]);
-      off.push_back((int64_t)all.size());
-    }
-    for (int64_t i = 0; i < n2; i++) {
-      all.insert(all.end(), s2 + off2[i], s2 + off2[i + 1]);
-      off.push_back((int64_t)all.size());
-    }
-    const int64_t n = n1 + n2, rs[3] = {0, n1, n};
-    OvRun R;
-    overlap_table(c, R, all.data(), off.data(), n, rs, 2, false);
-    DevBuf<int64_t> d_counts;
-    c->hip(d_counts.ensure((size_t)n1 + 1), "alloc");
-    c->hip(launch_overlap_two(R.B, R.mask, n, n1, d_counts.p, c->st), "overlap counts");
-    if (n1 > 0) c->hip(hipMemcpyAsync(counts, d_counts.p, (size_t)n1 * 8, hipMemcpyDeviceToHost, c->st), "d2h");
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    return UMICLUST_OK;
-  });
-}
-
-int32_t umiclust_overlap_regions(umiclust_ctx* c, const char* seqs, const int64_t* offs, int64_t n,
-                                 const int64_t* region_start, int32_t nregions, int64_t* total, int32_t* maxcount) {
-  UC_GUARD(c, {
-    if (nregions < 1 || nregions > UMICLUST_OVERLAP_MAX_REGIONS || !total || !maxcount)
-      c->fail(UMICLUST_EINVAL, "1..%d regions and both outputs required", UMICLUST_OVERLAP_MAX_REGIONS);
-    OvRun R;
-    overlap_table(c, R, seqs, offs, n, region_start, nregions, true);
-    const size_t cells = (size_t)nregions * nregions;
-    DevBuf<unsigned long long> d_total;
-    DevBuf<uint32_t> d_max;
-    c->hip(d_total.ensure(cells), "alloc");
-    c->hip(d_max.ensure(cells), "alloc");
-    c->hip(hipMemsetAsync(d_total.p, 0, cells * 8, c->st), "memset");
-    c->hip(hipMemsetAsync(d_max.p, 0, cells * 4, c->st), "memset");
-    if (n > 0) c->hip(launch_overlap_pairs(R.B, R.mask, nregions, d_total.p, d_max.p, c->st), "overlap pairs");
-    std::vector<uint32_t> mx(cells);
-    c->hip(hipMemcpyAsync(total, d_total.p, cells * 8, hipMemcpyDeviceToHost, c->st), "d2h");
-    c->hip(hipMemcpyAsync(mx.data(), d_max.p, cells * 4, hipMemcpyDeviceToHost, c->st), "d2h");
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    for (size_t x = 0; x < cells; x++) maxcount[x] = (int32_t)mx[x];
-    return UMICLUST_OK;
-  });
-}
-
-// ---------------------------------------------------------------- UMI extraction (§8f f1)
-namespace {
-// additionalEqualities of extract_umis.py:26-87 (either order), plus identity
-constexpr const char* kIupacEq[] = {"MA", "MC", "RA", "RG", "WA", "WT", "SC", "SG", "YC", "YT", "KG", "KT", "VA", "VC",
-                                "VG", "HA", "HC", "HT", "DA", "DG", "DT", "BC", "BG", "BT", "NA", "NC", "NG", "NT",
-                                "ma", "mc", "ra", "rg", "wa", "wt", "sc", "sg", "yc", "yt", "kg", "kt", "va", "vc",
-                                "vg", "ha", "hc", "ht", "da", "dg", "dt", "bc", "bg", "bt", "na", "nc", "ng", "nt",
-                                "aA", "cC", "tT", "gG"};
-
-// symbol equality of edlib with the reference's additionalEqualities, built at compile time (constant
-// initialisation: contexts on different threads share it without a lazy first-use race)
-struct EqTable {
-  bool eq[256][256];
-};
-constexpr EqTable make_eq_table() {
-  EqTable t{};
-  for (int a = 0; a < 256; a++)
-    for (int b = 0; b < 256; b++) t.eq[a][b] = a == b;
-  for (const char* e : kIupacEq) {
-    t.eq[(uint8_t)e[0]][(uint8_t)e[1]] = true;
-    t.eq[(uint8_t)e[1]][(uint8_t)e[0]] = true;
-  }
-  return t;
-}
-constexpr EqTable kEqTable = make_eq_table();
-
-void build_patterns(umiclust_ctx* c, const char* fwd, const char* rev, ExtractPatterns& P) {
-  const auto& eqt = kEqTable.eq;
-  memset(&P, 0, sizeof(P));
-  const char* pats[2] = {fwd, rev};
-  for (int w = 0; w < 2; w++) {
-    if (!pats[w]) c->fail(UMICLUST_EINVAL, "null pattern");
-    const int m = (int)strlen(pats[w]);
-    if (m < 1 || m > 64) c->fail(UMICLUST_EINVAL, "UMI patterns of 1..64 symbols are supported (got %d)", m);
-    P.m[w] = m;
-    for (int ch = 0; ch < 256; ch++)
-      for (int i = 0; i < m; i++) {
-        if (eqt[(uint8_t)pats[w][i]][ch]) P.peq[w][ch] |= 1ull << i;
-        if (eqt[(uint8_t)pats[w][m - 1 - i]][ch]) P.peqr[w][ch] |= 1ull << i;
-      }
-  }
-}
-
-void extract_device(umiclust_ctx* c, const char* seqs, const int64_t* offs, int64_t n, int32_t a5, int32_t a3,
-                    int32_t k, const char* fwd, const char* rev, int32_t* out) {
-  if (n < 0 || (n > 0 && (!seqs || !offs || !out)) || a5 < 0 || a3 < 0 || k < 0)
-    c->fail(UMICLUST_EINVAL, "bad argument");
-  ExtractPatterns P;
-  build_patterns(c, fwd, rev, P);
-  if (n == 0) return;
-  // Only the adapter windows are read: with short windows the host gathers them (its threads, into pinned
-  // memory) and the device gets ~141 B per read instead of the whole read
-  const int32_t S = (a5 + a3 + 3) & ~3;
-  if (a3 > 0 && a5 + a3 > 0 && S <= kExMaxSlot && a5 <= 255 && a3 <= 255) {
-    PinBuf<char>& hw = c->ex_win;
-    PinBuf<uint8_t>& hl = c->ex_len;
-    c->hip(hw.ensure((size_t)n * S + 16), "alloc pinned");
-    c->hip(hl.ensure((size_t)n * 2), "alloc pinned");
-    const int T = n < 65536 ? 1 : io_threads();
-    parallel_for(T, [&](int t) {
-      const int64_t lo = n * t / T, hi = n * (t + 1) / T;
-      for (int64_t i = lo; i < hi; i++) {
-        const char* b = seqs + offs[i];
-        const int64_t len = offs[i + 1] - offs[i];
-        // Python slicing: seq[:a5] and seq[-a3:]
-        const int64_t l5 = a5 < len ? a5 : len, l3 = a3 < len ? a3 : len;
-        char* d = hw.p + i * S;
-        memcpy(d, b, (size_t)l5);
-        memcpy(d + a5, b + len - l3, (size_t)l3);
-        hl.p[2 * i] = (uint8_t)l5;
-        hl.p[2 * i + 1] = (uint8_t)l3;
-      }
-    });
-    DevBuf<char>& d_w = c->ex_dwin;
-    DevBuf<uint8_t>& d_l = c->ex_dlen;
-    DevBuf<int32_t>& d_out = c->ex_dout;
-    DevBuf<ExtractPatterns>& d_p = c->ex_dpat;
-    c->hip(d_w.ensure((size_t)n * S + 16), "alloc");
-    c->hip(d_l.ensure((size_t)n * 2), "alloc");
-    c->hip(d_out.ensure((size_t)n * 6), "alloc");
-    c->hip(d_p.ensure(1), "alloc");
-    c->hip(hipMemcpyAsync(d_w.p, hw.p, (size_t)n * S, hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(hipMemcpyAsync(d_l.p, hl.p, (size_t)n * 2, hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(hipMemcpyAsync(d_p.p, &P, sizeof(P), hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(launch_extract_win(d_w.p, d_l.p, n, S, a5, k, d_p.p, d_out.p, c->st), "extract");
-    c->hip(hipMemcpyAsync(out, d_out.p, (size_t)n * 6 * 4, hipMemcpyDeviceToHost, c->st), "d2h");
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    return;
-  }
-  const int64_t bytes = offs[n] - offs[0];
-  std::vector<int64_t> rel((size_t)n + 1);
-  for (int64_t i = 0; i <= n; i++) rel[i] = offs[i] - offs[0];
-  DevBuf<char> d_s;
-  DevBuf<int64_t> d_o;
-  DevBuf<ExtractPatterns> d_p;
-  DevBuf<int32_t> d_out;
-  c->hip(d_s.ensure((size_t)bytes + 1), "alloc");
-  c->hip(d_o.ensure((size_t)n + 1), "alloc");
-  c->hip(d_p.ensure(1), "alloc");
-  c->hip(d_out.ensure((size_t)n * 6), "alloc");
-  if (bytes > 0) c->hip(hipMemcpyAsync(d_s.p, seqs + offs[0], (size_t)bytes, hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(hipMemcpyAsync(d_o.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(hipMemcpyAsync(d_p.p, &P, sizeof(P), hipMemcpyHostToDevice, c->st), "h2d");
-  c->hip(launch_extract(d_s.p, d_o.p, n, a5, a3, k, d_p.p, d_out.p, c->st), "extract");
-  c->hip(hipMemcpyAsync(out, d_out.p, (size_t)n * 6 * 4, hipMemcpyDeviceToHost, c->st), "d2h");
-  c->hip(hipStreamSynchronize(c->st), "sync");
-}
-
-}  // namespace
-
-int32_t umiclust_extract_umis(umiclust_ctx* c, const char* seqs, const int64_t* offsets, int64_t n,
-                              int32_t adapter_length_5_end, int32_t adapter_length_3_end, int32_t max_pattern_dist,
-                              const char* umi_fwd, const char* umi_rev, int32_t* out) {
-  UC_GUARD(c, {
-    extract_device(c, seqs, offsets, n, adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd,
-                   umi_rev, out);
-    return UMICLUST_OK;
-  });
-}
-
-int64_t umiclust_extract_umis_file(umiclust_ctx* c, const char* fastx_file, const char* out_fasta,
-                                   int32_t adapter_length_5_end, int32_t adapter_length_3_end,
-                                   int32_t max_pattern_dist, const char* umi_fwd, const char* umi_rev) {
-  UC_GUARD(c, {
-    if (!fastx_file || !out_fasta) c->fail(UMICLUST_EINVAL, "null path");
-    Fasta f;
-    bool fastq = false;
-    {
-      FILE* fp = fopen(fastx_file, "rb");
-      if (!fp) c->fail(UMICLUST_EIO, "cannot read %s", fastx_file);
-      int ch;
-      while ((ch = fgetc(fp)) == '\n' || ch == '\r') {}
-      fastq = ch == '@';
-      fclose(fp);
-    }
-    if (!(fastq ? io::read_fastq(fastx_file, f) : io::read_fasta(fastx_file, f)))
-      c->fail(UMICLUST_EIO, "cannot parse %s", fastx_file);
-    const int64_t n = (int64_t)f.hdr_off.size();
-    std::vector<int32_t> res((size_t)std::max<int64_t>(n, 1) * 6);
-    extract_device(c, f.seq.data(), f.seq_off.data(), n, adapter_length_5_end, adapter_length_3_end, max_pattern_dist,
-                   umi_fwd, umi_rev, res.data());
-    // records in input order; the reference raises at the first record without a strand annotation, after
-    // writing the records before it: those are written, then the error is returned
-    int64_t ngood = n;
-    for (int64_t i = 0; i < n && ngood == n; i++) {
-      Sv st;
-      if (!split1(Sv{f.data + f.hdr_off[i], (size_t)f.hdr_len[i]}, "strand=", st)) ngood = i;
-    }
-    const int64_t tot = io::write_detected_umis(out_fasta, f, res.data(), ngood, adapter_length_3_end);
-    if (ngood < n) c->fail(UMICLUST_EFORMAT, "Read strand not annotated!");
-    return tot;
-  });
-}
-
-// ---------------------------------------------------------------- quality filtering (row f5)
-namespace {
-
-// The device behind fq::run_filter: a chunk's gathered qualities and offsets go up in two copies, k_fastq_ee runs,
-// the per-record sums and byte ranges come back.  reserve() runs on the parsing thread, run() on the caller's.
-struct FqDevice : fq::Backend {
-  umiclust_ctx* c;
-  explicit FqDevice(umiclust_ctx* ctx) : c(ctx) {}
-  bool reserve(int slot, size_t qual_bytes, size_t nrec, fq::Slot& s, std::string& err) override {
-    umiclust_ctx::FqSlot& h = c->fq_slot[slot];
-    auto grow = [](auto& b, size_t count) {  // with slack: chunks differ by a few records
-      return (b.p && count <= b.n) || b.ensure(count + count / 8 + 64) == hipSuccess;
-    };
-    if (hipSetDevice(c->dev) != hipSuccess || !grow(h.q, qual_bytes + 2 * fq::kPad) || !grow(h.offs, nrec + 1) ||
-        !grow(h.ee, nrec + 1) || !grow(h.lo, nrec + 1) || !grow(h.hi, nrec + 1)) {
-      (void)hipGetLastError();
-      err = "cannot allocate the pinned staging buffers";
-      return false;
-    }
-    s = fq::Slot{h.q.p, h.offs.p, h.ee.p, h.lo.p, h.hi.p};
-    return true;
-  }
-  bool run(int slot, size_t qual_bytes, int64_t nrec, const uint64_t* table, double* t_h2d_s, double* t_kernel_s,
-           std::string& err) override {
-    umiclust_ctx::FqSlot& h = c->fq_slot[slot];
-    const size_t n = (size_t)nrec;
-    auto grow = [](auto& b, size_t count) {
-      return (b.p && count <= b.n) || b.ensure(count + count / 8 + 64) == hipSuccess;
-    };
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t x) { return e == hipSuccess && (e = x) == hipSuccess; };
-    for (hipEvent_t& ev : c->fq_ev)
-      if (!ev) ok(hipEventCreate(&ev));
-    if (e == hipSuccess && !(grow(c->fq_dq, qual_bytes + 2 * fq::kPad) && grow(c->fq_doffs, n + 1) &&
-                             grow(c->fq_dee, n + 1) && grow(c->fq_dlo, n + 1) && grow(c->fq_dhi, n + 1) &&
-                             grow(c->fq_dtab, 256)))
-      e = hipErrorOutOfMemory;
-    hipStream_t st = c->st;
-    ok(hipMemcpyAsync(c->fq_dtab.p, table, 256 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    ok(hipEventRecord(c->fq_ev[0], st));
-    ok(hipMemcpyAsync(c->fq_dq.p, h.q.p, qual_bytes + 2 * fq::kPad, hipMemcpyHostToDevice, st));
-    ok(hipMemcpyAsync(c->fq_doffs.p, h.offs.p, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    ok(hipEventRecord(c->fq_ev[1], st));
-    if (e == hipSuccess)
-      ok(launch_fastq_ee(c->fq_dq.p + fq::kPad, c->fq_doffs.p, nrec, c->fq_dtab.p, c->fq_dee.p, c->fq_dlo.p,
-                         c->fq_dhi.p, st));
-    ok(hipEventRecord(c->fq_ev[2], st));
-    ok(hipMemcpyAsync(h.ee.p, c->fq_dee.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    ok(hipMemcpyAsync(h.lo.p, c->fq_dlo.p, n, hipMemcpyDeviceToHost, st));
-    ok(hipMemcpyAsync(h.hi.p, c->fq_dhi.p, n, hipMemcpyDeviceToHost, st));
-    ok(hipStreamSynchronize(st));
-    float ms0 = 0.f, ms1 = 0.f;
-    ok(hipEventElapsedTime(&ms0, c->fq_ev[0], c->fq_ev[1]));
-    ok(hipEventElapsedTime(&ms1, c->fq_ev[1], c->fq_ev[2]));
-    if (e != hipSuccess) {
-      err = std::string("fastq_filter device step: ") + hipGetErrorString(e);
-      return false;
-    }
-    *t_h2d_s = ms0 * 1e-3;
-    *t_kernel_s = ms1 * 1e-3;
-    return true;
-  }
-};
-
-int64_t fastq_filter_impl(umiclust_ctx* c, const umiclust_fastq_filter_params* p, const char* in_fastq,
-                          const char* fastqout, const char* fastqout_discarded, const char* log_path,
-                          umiclust_fastq_filter_result* result) {
-  if (!p || !in_fastq) c->fail(UMICLUST_EINVAL, "null params or input path");
-  FqDevice dev(c);
-  fq::Paths paths;
-  paths.in = in_fastq;
-  paths.out = fastqout;
-  paths.discarded = fastqout_discarded;
-  paths.log = log_path;
-  std::string err;
-  const int64_t rc = fq::run_filter(*p, paths, io_threads(), c->tun.fq_chunk, dev, result, err);
-  if (rc < 0) c->fail((int)rc, "%s", err.c_str());
-  return rc;
-}
-
-}  // namespace
-
-int64_t umiclust_fastq_filter(umiclust_ctx* c, const umiclust_fastq_filter_params* p, const char* in_fastq,
-                              const char* fastqout, const char* fastqout_discarded, const char* log_path,
-                              umiclust_fastq_filter_result* result) {
-  UC_GUARD(c, { return fastq_filter_impl(c, p, in_fastq, fastqout, fastqout_discarded, log_path, result); });
-}
-
-int64_t umiclust_fastq_filter_argv(umiclust_ctx* c, int32_t argc, const char* const* argv,
-                                   umiclust_fastq_filter_result* result) {
-  UC_GUARD(c, {
-    umiclust_fastq_filter_params p;
-    std::vector<char> in(4096), out(4096), dis(4096), lg(4096);
-    const int32_t rc =
-        umiclust_fastq_filter_params_from_argv(&p, argc, argv, in.data(), out.data(), dis.data(), lg.data(), 4096);
-    if (rc != UMICLUST_OK) c->fail(rc, "cannot parse the vsearch --fastq_filter argv");
-    return fastq_filter_impl(c, &p, in.data(), out[0] ? out.data() : nullptr, dis[0] ? dis.data() : nullptr,
-                             lg[0] ? lg.data() : nullptr, result);
-  });
-}
-
-int32_t umiclust_fastq_ee(umiclust_ctx* c, const uint8_t* quals, const int64_t* offsets, int64_t n,
-                          int32_t fastq_ascii, int64_t* ee_fx, uint8_t* qlo, uint8_t* qhi) {
-  UC_GUARD(c, {
-    if (n < 0 || (n > 0 && (!quals || !offsets || !ee_fx || !qlo || !qhi)) || (fastq_ascii != 33 && fastq_ascii != 64))
-      c->fail(UMICLUST_EINVAL, "bad argument");
-    if (n == 0) return UMICLUST_OK;
-    for (int64_t i = 0; i < n; i++) {
-      const int64_t len = offsets[i + 1] - offsets[i];
-      if (len < 0) c->fail(UMICLUST_EINVAL, "offsets decrease at record %lld", (long long)i);
-      if (len > fq::kDevMaxLen) c->fail(UMICLUST_ERANGE, "record %lld is longer than 2^22 bytes", (long long)i);
-    }
-    fq::Tables tab;
-    fq::build_tables(fastq_ascii, 0, 93, tab);
-    FqDevice dev(c);
-    fq::Slot s;
-    std::string err;
-    const size_t bytes = (size_t)(offsets[n] - offsets[0]);
-    if (!dev.reserve(0, bytes, (size_t)n, s, err)) c->fail(UMICLUST_ENOMEM, "%s", err.c_str());
-    memset(s.qual, 0, (size_t)fq::kPad);
-    memcpy(s.qual + fq::kPad, quals + offsets[0], bytes);
-    memset(s.qual + fq::kPad + bytes, 0, (size_t)fq::kPad);
-    for (int64_t i = 0; i <= n; i++) s.offs[i] = offsets[i] - offsets[0];
-    double t0, t1;
-    if (!dev.run(0, bytes, n, tab.fx, &t0, &t1, err)) c->fail(UMICLUST_EDEVICE, "%s", err.c_str());
-    memcpy(ee_fx, s.ee, (size_t)n * sizeof(int64_t));
-    memcpy(qlo, s.qlo, (size_t)n);
-    memcpy(qhi, s.qhi, (size_t)n);
-    return UMICLUST_OK;
-  });
-}
-
-// ---------------------------------------------------------------- region binning (§8f f4)
-namespace {
-int32_t rd_i32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
-}  // namespace
-
-int64_t umiclust_region_split(umiclust_ctx* c, const char* bam_file, int32_t nregions, const char* const* region_names,
-                              const int64_t* region_lengths, const int32_t* region_clusters,
-                              double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
-                              const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int32_t ncluster_cap,
-                              uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
-  UC_GUARD(c, {
-    if (!bam_file || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
-        !counts || ncluster_cap < 0 || (ncluster_cap > 0 && !reads_per_cluster))
-      c->fail(UMICLUST_EINVAL, "bad argument");
-    std::vector<uint8_t> raw;
-    if (!io::inflate_bgzf(bam_file, raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
-    // header: text, then the reference names, matched to the regions of the reference FASTA
-    bam::Header hdr;
-    std::string herr;
-    if (!bam::parse_header(raw.data(), raw.size(), hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
-    std::unordered_map<std::string, int32_t> rid;
-    for (int32_t r = 0; r < nregions; r++) rid.emplace(region_names[r], r);
-    const int32_t nref = (int32_t)hdr.ref_name.size();
-    const std::vector<std::string>& refname = hdr.ref_name;
-    std::vector<int64_t> rlen(nref, -1);
-    std::vector<int32_t> rclu(nref, -1), rreg(nref, -1);
-    for (int32_t r = 0; r < nref; r++) {
-      auto it = rid.find(refname[r]);
-      if (it != rid.end()) {
-        rreg[r] = it->second;
-        rlen[r] = region_lengths[it->second];
-        rclu[r] = region_clusters[it->second];
-      }
-    }
-    std::vector<int64_t> roff;
-    if (!bam::record_offsets(raw.data(), raw.size(), hdr.end, roff, herr)) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
-    // the kernels index each record by its own l_read_name, n_cigar_op and l_seq
-    if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
-    const int64_t n = (int64_t)roff.size();
-    // device: classify every record
-    DevBuf<uint8_t> d_raw;
-    DevBuf<int64_t> d_roff, d_rlen, d_outlen, d_pos;
-    DevBuf<int32_t> d_rclu, d_clu;
-    DevBuf<int8_t> d_cls;
-    c->hip(d_raw.ensure(raw.size() + 1), "alloc");
-    c->hip(d_roff.ensure((size_t)n + 1), "alloc");
-    c->hip(d_rlen.ensure((size_t)nref + 1), "alloc");
-    c->hip(d_rclu.ensure((size_t)nref + 1), "alloc");
-    c->hip(d_cls.ensure((size_t)n + 1), "alloc");
-    c->hip(d_clu.ensure((size_t)n + 1), "alloc");
-    c->hip(d_outlen.ensure((size_t)n + 1), "alloc");
-    c->hip(d_pos.ensure((size_t)n + 1), "alloc");
-    c->hip(hipMemcpyAsync(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
-    if (n) c->hip(hipMemcpyAsync(d_roff.p, roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
-    if (nref) {
-      c->hip(hipMemcpyAsync(d_rlen.p, rlen.data(), (size_t)nref * 8, hipMemcpyHostToDevice, c->st), "h2d");
-      c->hip(hipMemcpyAsync(d_rclu.p, rclu.data(), (size_t)nref * 4, hipMemcpyHostToDevice, c->st), "h2d");
-    }
-    c->hip(launch_bam_classify(d_raw.p, d_roff.p, n, nref, d_rlen.p, d_rclu.p, minimal_region_overlap,
-                               max_softclip_5_end, max_softclip_3_end, d_cls.p, d_clu.p, d_outlen.p, c->st),
-           "bam classify");
-    std::vector<int8_t> cls(n);
-    std::vector<int32_t> clu(n);
-    std::vector<int64_t> olen(n);
-    if (n) {
-      c->hip(hipMemcpyAsync(cls.data(), d_cls.p, (size_t)n, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipMemcpyAsync(clu.data(), d_clu.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipMemcpyAsync(olen.data(), d_outlen.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st), "d2h");
-    }
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    // the reference raises KeyError at the first record whose region is unknown, after the records before it
-    int64_t stop = n;
-    for (int64_t r = 0; r < n && stop == n; r++)
-      if (cls[r] == kBamNoRegion || cls[r] == kBamNoCluster) stop = r;
-    int32_t ncl = 0;
-    for (int64_t r = 0; r < stop; r++)
-      if (cls[r] == kBamKept) ncl = std::max(ncl, clu[r] + 1);
-    // output grouped by cluster, records in BAM order within a cluster
-    std::vector<int64_t> cbase((size_t)ncl + 1, 0), pos(n, -1);
-    for (int64_t r = 0; r < stop; r++)
-      if (cls[r] == kBamKept) cbase[clu[r] + 1] += olen[r];
-    for (int32_t k = 0; k < ncl; k++) cbase[k + 1] += cbase[k];
-    {
-      std::vector<int64_t> cur(cbase.begin(), cbase.end() - 1);
-      for (int64_t r = 0; r < stop; r++)
-        if (cls[r] == kBamKept) {
-          pos[r] = cur[clu[r]];
-          cur[clu[r]] += olen[r];
-        }
-    }
-    std::vector<char> outb((size_t)cbase[ncl] + 1);
-    DevBuf<char> d_out;
-    c->hip(d_out.ensure(outb.size()), "alloc");
-    if (stop) {
-      c->hip(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)stop * 8, hipMemcpyHostToDevice, c->st), "h2d");
-      c->hip(launch_bam_emit(d_raw.p, d_roff.p, stop, d_cls.p, d_pos.p, d_out.p, c->st), "bam emit");
-      c->hip(hipMemcpyAsync(outb.data(), d_out.p, (size_t)cbase[ncl], hipMemcpyDeviceToHost, c->st), "d2h");
-    }
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    // append per cluster (the reference opens region_cluster<k>.fasta with "a" for every record)
-    std::vector<int32_t> used;
-    for (int32_t k = 0; k < ncl; k++)
-      if (cbase[k + 1] > cbase[k]) used.push_back(k);
-    const int T = std::max(1, std::min<int>(io_threads(), (int)used.size()));
-    std::vector<int32_t> bad(T, -1);
-    parallel_for(T, [&](int t) {
-      for (size_t u = (size_t)t; u < used.size(); u += (size_t)T) {
-        const int32_t k = used[u];
-        const std::string fn = pjoin(out_dir, "region_cluster" + std::to_string(k) + ".fasta");
-        const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0666);
-        bool ok = fd >= 0 && io::write_all(fd, outb.data() + cbase[k], (size_t)(cbase[k + 1] - cbase[k]));
-        if (fd >= 0) ok = (close(fd) == 0) && ok;
-        if (!ok) bad[t] = k;
-      }
-    });
-    for (int32_t v : bad)
-      if (v >= 0) c->fail(UMICLUST_EIO, "cannot append region_cluster%d.fasta", v);
-    // counters of the records the reference reached
-    int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
-    if (reads_per_cluster) memset(reads_per_cluster, 0, sizeof(int64_t) * (size_t)ncluster_cap);
-    if (region_detected) memset(region_detected, 0, (size_t)nregions);
-    const int64_t last = stop < n ? stop + 1 : n;  // the failing record counts as a primary alignment too
-    for (int64_t r = 0; r < last; r++) {
-      const int8_t k = cls[r];
-      if (k == kBamUnmapped) cnt[0]++;
-      if (k >= kBamShort) cnt[1]++;
-      if (k == kBamShort) cnt[2]++;
-      if (k == kBamLong) cnt[3]++;
-      if (k == kBamKept && r < stop) {
-        if (clu[r] < ncluster_cap) reads_per_cluster[clu[r]]++;
-        const int32_t ref = rd_i32(raw.data() + roff[r] + 4);
-        if (region_detected && rreg[ref] >= 0) region_detected[rreg[ref]] = 1;
-      }
-    }
-    for (int x = 0; x < 4; x++) counts[x] = cnt[x];
-    if (stop < n) {
-      const int32_t ref = rd_i32(raw.data() + roff[stop] + 4);
-      const std::string nm = ref >= 0 && ref < nref ? refname[ref] : std::string("None");
-      if (missing_name && missing_cap > 0) snprintf(missing_name, (size_t)missing_cap, "%s", nm.c_str());
-      c->fail(UMICLUST_EFORMAT, "KeyError: '%s'", nm.c_str());
-    }
-    if (ncl > ncluster_cap) c->fail(UMICLUST_ERANGE, "cluster ids up to %d exceed the counter capacity", ncl - 1);
-    return (int64_t)used.size();
-  });
-}
-
-// ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
-int64_t umiclust_bam_open(umiclust_ctx* c, const char* bam_file, int32_t hash_bits) {
-  UC_GUARD(c, {
-    if (!bam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
-    c->bs = umiclust_ctx::BamSession();
-    umiclust_ctx::BamSession S;
-    const double t0 = now_s();
-    if (!io::inflate_bgzf(bam_file, S.raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
-    S.t_inflate = now_s() - t0;
-    std::string herr;
-    if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
-    if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
-      c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
-    const int64_t n = (int64_t)S.roff.size();
-    uint64_t m = 1024;
-    while (m < 2 * (uint64_t)n) m <<= 1;
-    DevBuf<uint8_t> d_raw, d_nmp;
-    DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
-    DevBuf<int32_t> d_ref, d_lseq, d_cslen;
-    DevBuf<int8_t> d_cls, d_bad;
-    DevBuf<uint64_t> d_hash;
-    DevBuf<unsigned long long> d_keys, d_rep;
-    DevBuf<uint32_t> d_cnt, d_coll;
-    const size_t n1 = (size_t)n + 1;
-    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
-    c->hip(d_roff.ensure(n1), "alloc");
-    c->hip(d_reflen.ensure(n1), "alloc");
-    c->hip(d_cols.ensure(n1), "alloc");
-    c->hip(d_nm.ensure(n1), "alloc");
-    c->hip(d_csoff.ensure(n1), "alloc");
-    c->hip(d_slot.ensure(n1), "alloc");
-    c->hip(d_ref.ensure(n1), "alloc");
-    c->hip(d_lseq.ensure(n1), "alloc");
-    c->hip(d_cslen.ensure(n1), "alloc");
-    c->hip(d_cls.ensure(n1), "alloc");
-    c->hip(d_bad.ensure(n1), "alloc");
-    c->hip(d_nmp.ensure(n1), "alloc");
-    c->hip(d_hash.ensure(n1), "alloc");
-    c->hip(d_keys.ensure((size_t)m), "alloc");
-    c->hip(d_rep.ensure((size_t)m), "alloc");
-    c->hip(d_cnt.ensure((size_t)m), "alloc");
-    c->hip(d_coll.ensure(1), "alloc");
-    float ms = 0.f;
-    c->hip(hipEventRecord(c->ev0, c->st), "event");
-    c->hip(hipMemcpyAsync(d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
-    if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(hipEventRecord(c->ev1, c->st), "event");
-    c->hip(hipEventSynchronize(c->ev1), "sync");
-    c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-    S.t_h2d = ms * 1e-3;
-    const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
-                        d_bad.p};
-    // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
-    constexpr int kMaxPasses = 8;
-    int pass = 0;
-    for (;; pass++) {
-      if (pass == kMaxPasses) c->fail(UMICLUST_EDEVICE, "cs hash collisions under %d seeds", kMaxPasses);
-      const uint64_t hmask = (pass == 0 && hash_bits < 64) ? ((1ull << hash_bits) - 1) : ~0ull;
-      uint32_t coll = 0;
-      c->hip(hipEventRecord(c->ev0, c->st), "event");
-      c->hip(launch_bam_scan(d_raw.p, (int64_t)S.raw.size(), d_roff.p, n, bam::cs_seed(pass), hmask, o, c->st), "bam scan");
-      c->hip(launch_cs_group(d_raw.p, o, n, m - 1, d_keys.p, d_rep.p, d_cnt.p, d_slot.p, d_coll.p, c->st), "cs group");
-      c->hip(hipEventRecord(c->ev1, c->st), "event");
-      c->hip(hipMemcpyAsync(&coll, d_coll.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipStreamSynchronize(c->st), "sync");
-      c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-      S.t_dev += ms * 1e-3;
-      if (!coll) break;
-    }
-    S.n_reruns = pass;
-    S.cls.resize(n), S.ref.resize(n), S.l_seq.resize(n), S.reflen.resize(n), S.cols.resize(n), S.nm.resize(n);
-    S.nm_present.resize(n), S.cs_off.resize(n), S.cs_len.resize(n), S.cs_group.assign(n, -1);
-    std::vector<int8_t> bad(n);
-    std::vector<int64_t> slot(n);
-    std::vector<unsigned long long> rep((size_t)m);
-    std::vector<uint32_t> cnt((size_t)m);
-    if (n) {
-      auto d2h = [&](void* dst, const void* src, size_t bytes) {
-        c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
-      };
-      d2h(S.cls.data(), d_cls.p, (size_t)n), d2h(S.ref.data(), d_ref.p, (size_t)n * 4);
-      d2h(S.l_seq.data(), d_lseq.p, (size_t)n * 4), d2h(S.reflen.data(), d_reflen.p, (size_t)n * 8);
-      d2h(S.cols.data(), d_cols.p, (size_t)n * 8), d2h(S.nm.data(), d_nm.p, (size_t)n * 8);
-      d2h(S.nm_present.data(), d_nmp.p, (size_t)n), d2h(S.cs_off.data(), d_csoff.p, (size_t)n * 8);
-      d2h(S.cs_len.data(), d_cslen.p, (size_t)n * 4), d2h(bad.data(), d_bad.p, (size_t)n);
-      d2h(slot.data(), d_slot.p, (size_t)n * 8), d2h(rep.data(), d_rep.p, (size_t)m * 8);
-      d2h(cnt.data(), d_cnt.p, (size_t)m * 4);
-      c->hip(hipStreamSynchronize(c->st), "sync");
-    }
-    for (int64_t r = 0; r < n; r++)
-      if (bad[r] && S.first_bad < 0) S.first_bad = r;  // a primary one fails below: what stays is a record never read
-    for (int64_t r = 0; r < n; r++)
-      if (S.cls[r] == bam::kScanPrimary && bad[r]) {
-        const uint8_t* f = S.raw.data() + S.roff[r] + 4;
-        const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(S.raw.data() + S.roff[r]) - 32);
-        const std::string name((const char*)f + 32, lrn ? strnlen((const char*)f + 32, lrn) : 0);
-        c->fail(UMICLUST_EFORMAT, "malformed BAM record %lld (%s): a field or an aux tag does not fit the record",
-                (long long)r, name.c_str());
-      }
-    // dense group ids in order of the representative = first-seen order (a representative is its group's first record)
-    std::vector<int32_t> gid_of_slot;
-    gid_of_slot.assign((size_t)m, -1);
-    for (int64_t r = 0; r < n; r++) {
-      const int64_t s = slot[r];
-      if (s < 0) continue;
-      if ((int64_t)rep[s] == r) {
-        gid_of_slot[s] = (int32_t)S.g_rep.size();
-        S.g_rep.push_back(r);
-        S.g_count.push_back((int64_t)cnt[s]);
-      }
-      S.cs_group[r] = gid_of_slot[s];
-    }
-    S.open = true;
-    c->bs = std::move(S);
-    return n;
-  });
-}
-
-namespace {
-umiclust_ctx::BamSession* bam_session(umiclust_ctx* c) {
-  if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
-  return &c->bs;
-}
-}  // namespace
-
-int32_t umiclust_bam_counts(umiclust_ctx* c, int64_t* out) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
-    out[0] = (int64_t)S.roff.size();
-    out[1] = (int64_t)S.hdr.ref_name.size();
-    out[2] = (int64_t)S.g_rep.size();
-    out[3] = S.n_reruns;
-    out[4] = S.first_bad;
-    return UMICLUST_OK;
-  });
-}
-
-int32_t umiclust_bam_times(umiclust_ctx* c, double* out) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
-    out[0] = S.t_inflate, out[1] = S.t_h2d, out[2] = S.t_dev;
-    return UMICLUST_OK;
-  });
-}
-
-int32_t umiclust_bam_columns(umiclust_ctx* c, int8_t* cls, int32_t* ref, int32_t* l_seq, int64_t* reference_length,
-                             int64_t* cols, int64_t* nm, uint8_t* nm_present, int32_t* cs_group) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    const size_t n = S.roff.size();
-    if (n) {
-      if (cls) memcpy(cls, S.cls.data(), n);
-      if (ref) memcpy(ref, S.ref.data(), n * 4);
-      if (l_seq) memcpy(l_seq, S.l_seq.data(), n * 4);
-      if (reference_length) memcpy(reference_length, S.reflen.data(), n * 8);
-      if (cols) memcpy(cols, S.cols.data(), n * 8);
-      if (nm) memcpy(nm, S.nm.data(), n * 8);
-      if (nm_present) memcpy(nm_present, S.nm_present.data(), n);
-      if (cs_group) memcpy(cs_group, S.cs_group.data(), n * 4);
-    }
-    return UMICLUST_OK;
-  });
-}
-
-int32_t umiclust_bam_refs(umiclust_ctx* c, char* buf, int64_t cap, int64_t* off, int64_t* len) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    int64_t need = 0;
-    for (const std::string& s : S.hdr.ref_name) need += (int64_t)s.size() + 1;
-    if (need > INT32_MAX) c->fail(UMICLUST_ERANGE, "reference names exceed 2 GiB");
-    if (cap == 0) return (int32_t)need;
-    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
-    int64_t o = 0;
-    for (size_t r = 0; r < S.hdr.ref_name.size(); r++) {
-      off[r] = o;
-      memcpy(buf + o, S.hdr.ref_name[r].c_str(), S.hdr.ref_name[r].size() + 1);
-      o += (int64_t)S.hdr.ref_name[r].size() + 1;
-      if (len) len[r] = S.hdr.ref_len[r];
-    }
-    off[S.hdr.ref_name.size()] = o;
-    return (int32_t)need;
-  });
-}
-
-int64_t umiclust_bam_strings(umiclust_ctx* c, int32_t kind, const int64_t* rec, int64_t m, char* buf, int64_t cap,
-                             int64_t* off) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    const int64_t n = (int64_t)S.roff.size();
-    if ((kind != 0 && kind != 1) || m < 0 || (m > 0 && !rec)) c->fail(UMICLUST_EINVAL, "bad argument");
-    auto span = [&](int64_t r, const uint8_t*& p) -> int64_t {
-      if (kind == 1) {
-        p = S.raw.data() + S.cs_off[r];
-        return std::max<int64_t>(0, S.cs_len[r]);
-      }
-      const uint8_t* f = S.raw.data() + S.roff[r] + 4;
-      p = f + 32;
-      const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(S.raw.data() + S.roff[r]) - 32);
-      return (int64_t)(lrn ? strnlen((const char*)p, lrn) : 0);
-    };
-    int64_t need = 0;
-    const uint8_t* p = nullptr;
-    for (int64_t x = 0; x < m; x++) {
-      if (rec[x] < 0 || rec[x] >= n) c->fail(UMICLUST_EINVAL, "record %lld out of range", (long long)rec[x]);
-      need += span(rec[x], p);
-    }
-    if (cap == 0) return need;
-    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
-    int64_t o = 0;
-    for (int64_t x = 0; x < m; x++) {
-      const int64_t ln = span(rec[x], p);
-      off[x] = o;
-      if (ln) memcpy(buf + o, p, (size_t)ln);
-      o += ln;
-    }
-    off[m] = o;
-    return need;
-  });
-}
-
-int32_t umiclust_bam_cs_groups(umiclust_ctx* c, int64_t* count, int64_t* rep) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    const size_t g = S.g_rep.size();
-    if (g && count) memcpy(count, S.g_count.data(), g * 8);
-    if (g && rep) memcpy(rep, S.g_rep.data(), g * 8);
-    return UMICLUST_OK;
-  });
-}
-
-int64_t umiclust_bam_write(umiclust_ctx* c, const uint8_t* keep, const char* out_bam) {
-  UC_GUARD(c, {
-    auto& S = *bam_session(c);
-    if (!out_bam || (!keep && !S.roff.empty())) c->fail(UMICLUST_EINVAL, "null argument");
-    std::string err;
-    const int64_t k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
-    if (k < 0) c->fail(UMICLUST_EIO, "%s", err.c_str());
-    return k;
-  });
-}
-
-int32_t umiclust_bam_close(umiclust_ctx* c) {
-  UC_GUARD(c, {
-    (void)bam_session(c);
-    c->bs = umiclust_ctx::BamSession();
-    return UMICLUST_OK;
-  });
-}
-
 int32_t umiclust_prep(umiclust_ctx* c, const umiclust_params* p, const char* seqs, const int64_t* offsets,
                       int64_t n, char* masked, uint16_t* kmers, int32_t kstride, int32_t* nk) {
   UC_GUARD(c, {
     if (!p || n < 0 || (n > 0 && (!seqs || !offsets))) c->fail(UMICLUST_EINVAL, "null argument");
     for (int64_t i = 0; i < n; i++)
       if (offsets[i + 1] - offsets[i] > kMaxLen) c->fail(UMICLUST_ERANGE, "sequence longer than %d", kMaxLen);
-    DevBuf<char> d_a, d_m;
-    DevBuf<int64_t> d_o;
-    DevBuf<uint32_t> d_codes;
-    DevBuf<uint8_t> d_lens, d_nk;
-    DevBuf<uint16_t> d_km;
-    const int64_t bytes = n > 0 ? offsets[n] - offsets[0] : 0;
-    std::vector<int64_t> rel((size_t)n + 1);
-    for (int64_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
-    c->hip(d_a.ensure((size_t)bytes + 1), "alloc");
-    c->hip(d_o.ensure((size_t)n + 1), "alloc");
-    c->hip(d_codes.ensure((size_t)n * 2 * kCodeWords + 1), "alloc");
-    c->hip(d_lens.ensure((size_t)n + 1), "alloc");
-    c->hip(d_nk.ensure((size_t)n * 2 + 1), "alloc");
-    c->hip(d_km.ensure((size_t)n * 2 * kKmerStride + 1), "alloc");
-    c->hip(d_m.ensure((size_t)n * kMaxLen + 1), "alloc");
-    if (bytes > 0) c->hip(hipMemcpy(d_a.p, seqs + offsets[0], (size_t)bytes, hipMemcpyHostToDevice), "h2d");
-    c->hip(hipMemcpy(d_o.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice), "h2d");
-    c->hip(launch_prep(d_a.p, d_o.p, nullptr, (int32_t)n, p->qmask_dust, d_codes.p, d_lens.p, d_km.p, d_nk.p, d_m.p,
-                       nullptr, c->st),
-           "prep");
+    ProbeSeqs S;
+    probe_prep(c, S, seqs, offsets, n, p->qmask_dust, true, false);
     std::vector<char> m((size_t)n * kMaxLen);
     std::vector<uint16_t> km((size_t)n * 2 * kKmerStride);
     std::vector<uint8_t> nkv((size_t)n * 2);
     if (n > 0) {
-      c->hip(hipMemcpyAsync(m.data(), d_m.p, m.size(), hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipMemcpyAsync(km.data(), d_km.p, km.size() * 2, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipMemcpyAsync(nkv.data(), d_nk.p, nkv.size(), hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(m.data(), S.d_m.p, m.size(), hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(km.data(), S.d_km.p, km.size() * 2, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(nkv.data(), S.d_nk.p, nkv.size(), hipMemcpyDeviceToHost, c->st), "d2h");
     }
     c->hip(hipStreamSynchronize(c->st), "sync");
     for (int64_t i = 0; i < n; i++) {

@@ -1,0 +1,403 @@
+// dropin_bam.cpp -- the two BAM readers: region binning (§8f f4, regionsplit.hip) and the BAM session with its scan,
+// cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip).  Their HIP-free halves are in bam_host.h.
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+#include <vector>
+
+#include "ctx.h"
+
+using namespace uc;
+using namespace uc::io;
+
+namespace {
+int32_t rd_i32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
+// the query name of record r: at most l_read_name bytes and never past the record, up to its NUL
+std::string_view record_name(const std::vector<uint8_t>& raw, const std::vector<int64_t>& roff, int64_t r) {
+  const uint8_t* f = raw.data() + roff[r] + 4;
+  const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(raw.data() + roff[r]) - 32);
+  return {(const char*)f + 32, lrn ? strnlen((const char*)f + 32, lrn) : 0};
+}
+BamSession* bam_session(Ctx* c) {
+  if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
+  return &c->bs;
+}
+}  // namespace
+
+int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t nregions, const char* const* region_names,
+                              const int64_t* region_lengths, const int32_t* region_clusters,
+                              double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                              const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int32_t ncluster_cap,
+                              uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    if (!bam_file || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
+        !counts || ncluster_cap < 0 || (ncluster_cap > 0 && !reads_per_cluster))
+      c->fail(UMICLUST_EINVAL, "bad argument");
+    std::vector<uint8_t> raw;
+    if (!io::inflate_bgzf(bam_file, raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    // header: text, then the reference names, matched to the regions of the reference FASTA
+    bam::Header hdr;
+    std::string herr;
+    if (!bam::parse_header(raw.data(), raw.size(), hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
+    std::unordered_map<std::string, int32_t> rid;
+    for (int32_t r = 0; r < nregions; r++) rid.emplace(region_names[r], r);
+    const int32_t nref = (int32_t)hdr.ref_name.size();
+    const std::vector<std::string>& refname = hdr.ref_name;
+    std::vector<int64_t> rlen(nref, -1);
+    std::vector<int32_t> rclu(nref, -1), rreg(nref, -1);
+    for (int32_t r = 0; r < nref; r++) {
+      auto it = rid.find(refname[r]);
+      if (it != rid.end()) {
+        rreg[r] = it->second;
+        rlen[r] = region_lengths[it->second];
+        rclu[r] = region_clusters[it->second];
+      }
+    }
+    std::vector<int64_t> roff;
+    if (!bam::record_offsets(raw.data(), raw.size(), hdr.end, roff, herr)) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
+    // the kernels index each record by its own l_read_name, n_cigar_op and l_seq
+    if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    const int64_t n = (int64_t)roff.size();
+    // device: classify every record
+    DevBuf<uint8_t> d_raw;
+    DevBuf<int64_t> d_roff, d_rlen, d_outlen, d_pos;
+    DevBuf<int32_t> d_rclu, d_clu;
+    DevBuf<int8_t> d_cls;
+    c->hip(d_raw.ensure(raw.size() + 1), "alloc");
+    alloc_each(c, (size_t)n + 1, d_roff, d_cls, d_clu, d_outlen, d_pos);
+    alloc_each(c, (size_t)nref + 1, d_rlen, d_rclu);
+    c->hip(hipMemcpyAsync(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
+    if (n) c->hip(hipMemcpyAsync(d_roff.p, roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
+    if (nref) {
+      c->hip(hipMemcpyAsync(d_rlen.p, rlen.data(), (size_t)nref * 8, hipMemcpyHostToDevice, c->st), "h2d");
+      c->hip(hipMemcpyAsync(d_rclu.p, rclu.data(), (size_t)nref * 4, hipMemcpyHostToDevice, c->st), "h2d");
+    }
+    c->hip(launch_bam_classify(d_raw.p, d_roff.p, n, nref, d_rlen.p, d_rclu.p, minimal_region_overlap,
+                               max_softclip_5_end, max_softclip_3_end, d_cls.p, d_clu.p, d_outlen.p, c->st),
+           "bam classify");
+    std::vector<int8_t> cls(n);
+    std::vector<int32_t> clu(n);
+    std::vector<int64_t> olen(n);
+    if (n) {
+      c->hip(hipMemcpyAsync(cls.data(), d_cls.p, (size_t)n, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(clu.data(), d_clu.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(olen.data(), d_outlen.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st), "d2h");
+    }
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    // the reference raises KeyError at the first record whose region is unknown, after the records before it
+    int64_t stop = n;
+    for (int64_t r = 0; r < n && stop == n; r++)
+      if (cls[r] == kBamNoRegion || cls[r] == kBamNoCluster) stop = r;
+    int32_t ncl = 0;
+    for (int64_t r = 0; r < stop; r++)
+      if (cls[r] == kBamKept) ncl = std::max(ncl, clu[r] + 1);
+    // output grouped by cluster, records in BAM order within a cluster
+    std::vector<int64_t> cbase((size_t)ncl + 1, 0), pos(n, -1);
+    for (int64_t r = 0; r < stop; r++)
+      if (cls[r] == kBamKept) cbase[clu[r] + 1] += olen[r];
+    for (int32_t k = 0; k < ncl; k++) cbase[k + 1] += cbase[k];
+    {
+      std::vector<int64_t> cur(cbase.begin(), cbase.end() - 1);
+      for (int64_t r = 0; r < stop; r++)
+        if (cls[r] == kBamKept) {
+          pos[r] = cur[clu[r]];
+          cur[clu[r]] += olen[r];
+        }
+    }
+    std::vector<char> outb((size_t)cbase[ncl] + 1);
+    DevBuf<char> d_out;
+    c->hip(d_out.ensure(outb.size()), "alloc");
+    if (stop) {
+      c->hip(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)stop * 8, hipMemcpyHostToDevice, c->st), "h2d");
+      c->hip(launch_bam_emit(d_raw.p, d_roff.p, stop, d_cls.p, d_pos.p, d_out.p, c->st), "bam emit");
+      c->hip(hipMemcpyAsync(outb.data(), d_out.p, (size_t)cbase[ncl], hipMemcpyDeviceToHost, c->st), "d2h");
+    }
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    // append per cluster (the reference opens region_cluster<k>.fasta with "a" for every record)
+    std::vector<int32_t> used;
+    for (int32_t k = 0; k < ncl; k++)
+      if (cbase[k + 1] > cbase[k]) used.push_back(k);
+    const int T = std::max(1, std::min<int>(io_threads(), (int)used.size()));
+    std::vector<int32_t> bad(T, -1);
+    parallel_for(T, [&](int t) {
+      for (size_t u = (size_t)t; u < used.size(); u += (size_t)T) {
+        const int32_t k = used[u];
+        const std::string fn = pjoin(out_dir, "region_cluster" + std::to_string(k) + ".fasta");
+        const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0666);
+        bool ok = fd >= 0 && io::write_all(fd, outb.data() + cbase[k], (size_t)(cbase[k + 1] - cbase[k]));
+        if (fd >= 0) ok = (close(fd) == 0) && ok;
+        if (!ok) bad[t] = k;
+      }
+    });
+    for (int32_t v : bad)
+      if (v >= 0) c->fail(UMICLUST_EIO, "cannot append region_cluster%d.fasta", v);
+    // counters of the records the reference reached
+    int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
+    if (reads_per_cluster) memset(reads_per_cluster, 0, sizeof(int64_t) * (size_t)ncluster_cap);
+    if (region_detected) memset(region_detected, 0, (size_t)nregions);
+    const int64_t last = stop < n ? stop + 1 : n;  // the failing record counts as a primary alignment too
+    for (int64_t r = 0; r < last; r++) {
+      const int8_t k = cls[r];
+      if (k == kBamUnmapped) cnt[0]++;
+      if (k >= kBamShort) cnt[1]++;
+      if (k == kBamShort) cnt[2]++;
+      if (k == kBamLong) cnt[3]++;
+      if (k == kBamKept && r < stop) {
+        if (clu[r] < ncluster_cap) reads_per_cluster[clu[r]]++;
+        const int32_t ref = rd_i32(raw.data() + roff[r] + 4);
+        if (region_detected && rreg[ref] >= 0) region_detected[rreg[ref]] = 1;
+      }
+    }
+    for (int x = 0; x < 4; x++) counts[x] = cnt[x];
+    if (stop < n) {
+      const int32_t ref = rd_i32(raw.data() + roff[stop] + 4);
+      const std::string nm = ref >= 0 && ref < nref ? refname[ref] : std::string("None");
+      if (missing_name && missing_cap > 0) snprintf(missing_name, (size_t)missing_cap, "%s", nm.c_str());
+      c->fail(UMICLUST_EFORMAT, "KeyError: '%s'", nm.c_str());
+    }
+    if (ncl > ncluster_cap) c->fail(UMICLUST_ERANGE, "cluster ids up to %d exceed the counter capacity", ncl - 1);
+    return (int64_t)used.size();
+  });
+}
+
+// ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
+int64_t umiclust_bam_open(umiclust_ctx* ctx, const char* bam_file, int32_t hash_bits) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    if (!bam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
+    c->bs = BamSession();
+    BamSession S;
+    const double t0 = now_s();
+    if (!io::inflate_bgzf(bam_file, S.raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    S.t_inflate = now_s() - t0;
+    std::string herr;
+    if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
+      c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    const int64_t n = (int64_t)S.roff.size();
+    uint64_t m = 1024;
+    while (m < 2 * (uint64_t)n) m <<= 1;
+    DevBuf<uint8_t> d_raw, d_nmp;
+    DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
+    DevBuf<int32_t> d_ref, d_lseq, d_cslen;
+    DevBuf<int8_t> d_cls, d_bad;
+    DevBuf<uint64_t> d_hash;
+    DevBuf<unsigned long long> d_keys, d_rep;
+    DevBuf<uint32_t> d_cnt, d_coll;
+    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
+    alloc_each(c, (size_t)n + 1, d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot, d_ref, d_lseq, d_cslen, d_cls, d_bad,
+               d_nmp, d_hash);
+    alloc_each(c, (size_t)m, d_keys, d_rep, d_cnt);
+    c->hip(d_coll.ensure(1), "alloc");
+    float ms = 0.f;
+    c->hip(hipEventRecord(c->ev0, c->st), "event");
+    c->hip(hipMemcpyAsync(d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
+    if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(hipEventRecord(c->ev1, c->st), "event");
+    c->hip(hipEventSynchronize(c->ev1), "sync");
+    c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+    S.t_h2d = ms * 1e-3;
+    const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
+                        d_bad.p};
+    // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
+    constexpr int kMaxSeeds = 8;
+    int pass = 0;
+    for (;; pass++) {
+      if (pass == kMaxSeeds) c->fail(UMICLUST_EDEVICE, "cs hash collisions under %d seeds", kMaxSeeds);
+      const uint64_t hmask = (pass == 0 && hash_bits < 64) ? ((1ull << hash_bits) - 1) : ~0ull;
+      uint32_t coll = 0;
+      c->hip(hipEventRecord(c->ev0, c->st), "event");
+      c->hip(launch_bam_scan(d_raw.p, (int64_t)S.raw.size(), d_roff.p, n, bam::cs_seed(pass), hmask, o, c->st), "bam scan");
+      c->hip(launch_cs_group(d_raw.p, o, n, m - 1, d_keys.p, d_rep.p, d_cnt.p, d_slot.p, d_coll.p, c->st), "cs group");
+      c->hip(hipEventRecord(c->ev1, c->st), "event");
+      c->hip(hipMemcpyAsync(&coll, d_coll.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipStreamSynchronize(c->st), "sync");
+      c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+      S.t_dev += ms * 1e-3;
+      if (!coll) break;
+    }
+    S.n_reruns = pass;
+    S.cls.resize(n), S.ref.resize(n), S.l_seq.resize(n), S.reflen.resize(n), S.cols.resize(n), S.nm.resize(n);
+    S.nm_present.resize(n), S.cs_off.resize(n), S.cs_len.resize(n), S.cs_group.assign(n, -1);
+    std::vector<int8_t> bad(n);
+    std::vector<int64_t> slot(n);
+    std::vector<unsigned long long> rep((size_t)m);
+    std::vector<uint32_t> cnt((size_t)m);
+    if (n) {
+      auto d2h = [&](void* dst, const void* src, size_t bytes) {
+        c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
+      };
+      d2h(S.cls.data(), d_cls.p, (size_t)n), d2h(S.ref.data(), d_ref.p, (size_t)n * 4);
+      d2h(S.l_seq.data(), d_lseq.p, (size_t)n * 4), d2h(S.reflen.data(), d_reflen.p, (size_t)n * 8);
+      d2h(S.cols.data(), d_cols.p, (size_t)n * 8), d2h(S.nm.data(), d_nm.p, (size_t)n * 8);
+      d2h(S.nm_present.data(), d_nmp.p, (size_t)n), d2h(S.cs_off.data(), d_csoff.p, (size_t)n * 8);
+      d2h(S.cs_len.data(), d_cslen.p, (size_t)n * 4), d2h(bad.data(), d_bad.p, (size_t)n);
+      d2h(slot.data(), d_slot.p, (size_t)n * 8), d2h(rep.data(), d_rep.p, (size_t)m * 8);
+      d2h(cnt.data(), d_cnt.p, (size_t)m * 4);
+      c->hip(hipStreamSynchronize(c->st), "sync");
+    }
+    for (int64_t r = 0; r < n; r++)
+      if (bad[r] && S.first_bad < 0) S.first_bad = r;  // a primary one fails below: what stays is a record never read
+    for (int64_t r = 0; r < n; r++)
+      if (S.cls[r] == bam::kScanPrimary && bad[r]) {
+        const std::string name(record_name(S.raw, S.roff, r));
+        c->fail(UMICLUST_EFORMAT, "malformed BAM record %lld (%s): a field or an aux tag does not fit the record",
+                (long long)r, name.c_str());
+      }
+    // dense group ids in order of the representative = first-seen order (a representative is its group's first record)
+    std::vector<int32_t> gid_of_slot;
+    gid_of_slot.assign((size_t)m, -1);
+    for (int64_t r = 0; r < n; r++) {
+      const int64_t s = slot[r];
+      if (s < 0) continue;
+      if ((int64_t)rep[s] == r) {
+        gid_of_slot[s] = (int32_t)S.g_rep.size();
+        S.g_rep.push_back(r);
+        S.g_count.push_back((int64_t)cnt[s]);
+      }
+      S.cs_group[r] = gid_of_slot[s];
+    }
+    S.open = true;
+    c->bs = std::move(S);
+    return n;
+  });
+}
+
+int32_t umiclust_bam_counts(umiclust_ctx* ctx, int64_t* out) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
+    out[0] = (int64_t)S.roff.size();
+    out[1] = (int64_t)S.hdr.ref_name.size();
+    out[2] = (int64_t)S.g_rep.size();
+    out[3] = S.n_reruns;
+    out[4] = S.first_bad;
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_times(umiclust_ctx* ctx, double* out) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
+    out[0] = S.t_inflate, out[1] = S.t_h2d, out[2] = S.t_dev;
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_columns(umiclust_ctx* ctx, int8_t* cls, int32_t* ref, int32_t* l_seq, int64_t* reference_length,
+                             int64_t* cols, int64_t* nm, uint8_t* nm_present, int32_t* cs_group) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const size_t n = S.roff.size();
+    if (n) {
+      if (cls) memcpy(cls, S.cls.data(), n);
+      if (ref) memcpy(ref, S.ref.data(), n * 4);
+      if (l_seq) memcpy(l_seq, S.l_seq.data(), n * 4);
+      if (reference_length) memcpy(reference_length, S.reflen.data(), n * 8);
+      if (cols) memcpy(cols, S.cols.data(), n * 8);
+      if (nm) memcpy(nm, S.nm.data(), n * 8);
+      if (nm_present) memcpy(nm_present, S.nm_present.data(), n);
+      if (cs_group) memcpy(cs_group, S.cs_group.data(), n * 4);
+    }
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_refs(umiclust_ctx* ctx, char* buf, int64_t cap, int64_t* off, int64_t* len) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    int64_t need = 0;
+    for (const std::string& s : S.hdr.ref_name) need += (int64_t)s.size() + 1;
+    if (need > INT32_MAX) c->fail(UMICLUST_ERANGE, "reference names exceed 2 GiB");
+    if (cap == 0) return (int32_t)need;
+    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
+    int64_t o = 0;
+    for (size_t r = 0; r < S.hdr.ref_name.size(); r++) {
+      off[r] = o;
+      memcpy(buf + o, S.hdr.ref_name[r].c_str(), S.hdr.ref_name[r].size() + 1);
+      o += (int64_t)S.hdr.ref_name[r].size() + 1;
+      if (len) len[r] = S.hdr.ref_len[r];
+    }
+    off[S.hdr.ref_name.size()] = o;
+    return (int32_t)need;
+  });
+}
+
+int64_t umiclust_bam_strings(umiclust_ctx* ctx, int32_t kind, const int64_t* rec, int64_t m, char* buf, int64_t cap,
+                             int64_t* off) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const int64_t n = (int64_t)S.roff.size();
+    if ((kind != 0 && kind != 1) || m < 0 || (m > 0 && !rec)) c->fail(UMICLUST_EINVAL, "bad argument");
+    auto span = [&](int64_t r, const uint8_t*& p) -> int64_t {
+      if (kind == 1) {
+        p = S.raw.data() + S.cs_off[r];
+        return std::max<int64_t>(0, S.cs_len[r]);
+      }
+      const std::string_view name = record_name(S.raw, S.roff, r);
+      p = (const uint8_t*)name.data();
+      return (int64_t)name.size();
+    };
+    int64_t need = 0;
+    const uint8_t* p = nullptr;
+    for (int64_t x = 0; x < m; x++) {
+      if (rec[x] < 0 || rec[x] >= n) c->fail(UMICLUST_EINVAL, "record %lld out of range", (long long)rec[x]);
+      need += span(rec[x], p);
+    }
+    if (cap == 0) return need;
+    if (!buf || !off || cap < need) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)need);
+    int64_t o = 0;
+    for (int64_t x = 0; x < m; x++) {
+      const int64_t ln = span(rec[x], p);
+      off[x] = o;
+      if (ln) memcpy(buf + o, p, (size_t)ln);
+      o += ln;
+    }
+    off[m] = o;
+    return need;
+  });
+}
+
+int32_t umiclust_bam_cs_groups(umiclust_ctx* ctx, int64_t* count, int64_t* rep) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const size_t g = S.g_rep.size();
+    if (g && count) memcpy(count, S.g_count.data(), g * 8);
+    if (g && rep) memcpy(rep, S.g_rep.data(), g * 8);
+    return UMICLUST_OK;
+  });
+}
+
+int64_t umiclust_bam_write(umiclust_ctx* ctx, const uint8_t* keep, const char* out_bam) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out_bam || (!keep && !S.roff.empty())) c->fail(UMICLUST_EINVAL, "null argument");
+    std::string err;
+    const int64_t k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
+    if (k < 0) c->fail(UMICLUST_EIO, "%s", err.c_str());
+    return k;
+  });
+}
+
+int32_t umiclust_bam_close(umiclust_ctx* ctx) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    (void)bam_session(c);
+    c->bs = BamSession();
+    return UMICLUST_OK;
+  });
+}

@@ -1,8 +1,9 @@
 // fastq_filter.h -- the HIP-free host side of the `vsearch --fastq_filter` drop-in (row f5): the
 // argv grammar, the streaming record indexer over the mapped input, the keep/discard decision (policy O7d) with its
 // guard band and host recheck, and the in-order writers.  The per-record fixed-point expected-error sums come from
-// a Backend: the device (driver.cpp, csrc/fastq_filter.hip) or the host restatement below (tools/fastq_check_main.cpp,
-// the CPU suite's ASan/UBSan program).  Compiled by g++ (no HIP); depends on no other translation unit.
+// a Backend: the device (dropin_fastq.cpp, csrc/fastq_filter.hip) or the host restatement below
+// (tools/fastq_check_main.cpp, the CPU suite's ASan/UBSan program).  Compiled by g++ (no HIP); depends on no other
+// translation unit.
 #pragma once
 #include <stdint.h>
 

@@ -1,5 +1,5 @@
-// Internal declarations shared by the HIP kernels (kernels.hip) and the host driver
-// (driver.cpp).  Not part of the C ABI (see include/umiclust.h).
+// Internal declarations shared by the HIP kernels (kernels.hip) and the host side (driver.cpp,
+// dropin_*.cpp through ctx.h).  Not part of the C ABI (see include/umiclust.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -7,7 +7,7 @@ import random
 import numpy as np
 import pytest
 from test_bam_filter_cpu import CASES, MALFORMED, RUNNING, check_against_fixture, check_census, report_of, run_drop_in
-from umiclust import _lib, minimap2_align
+from umiclust import _lib, minimap2_align, synth
 from umiclust import vsearch_umi_cluster as _v
 
 import bam_ref
@@ -166,3 +166,32 @@ def test_session_errors(tmp_path):
         with pytest.raises(_lib.UmiclustError) as e:
             call()
         assert e.value.code == ESTATE
+
+
+def test_context_closed_while_every_drop_in_holds_state(tmp_path):
+    """A context is torn down with the f5 events and staging slots, the f1 window buffers and an open BAM session
+    still in it; a second context on the same device then computes the same."""
+    name = min(RUNNING, key=lambda k: len(CASES[k]["records"]))
+    raw = bam_ref.write_bam(tmp_path / "in.bam", CASES[name]["refs"], CASES[name]["records"])
+    rng = random.Random(13)
+    quals = [b"", b"!", bytes(rng.randrange(33, 75) for _ in range(70))]
+    reads = ["".join(rng.choice("ACGT") for _ in range(200)) for _ in range(2)]
+    umis = [["".join(rng.choice("ACGT") for _ in range(64)) for _ in range(2)] for _ in range(2)]
+    umis[1][0] = umis[0][1]
+
+    def every_drop_in(ctx):
+        ee = ctx.fastq_ee(quals)
+        ex = ctx.extract_umis(reads, fwd=synth.UMI_FWD, rev=synth.UMI_REV)
+        ov = ctx.overlap_counts(umis[0], umis[1])
+        return [np.array(a) for a in (*ee, ex, ov)], ctx.bam_open(tmp_path / "in.bam")
+
+    ctx = _lib.Context(_v._device())
+    first, s = every_drop_in(ctx)
+    check_columns(s, bam_ref.Columns(raw))
+    ctx.close()  # the session is still open
+    with _lib.Context(_v._device()) as ctx:
+        again, s = every_drop_in(ctx)
+        assert len(first) == len(again) and all(np.array_equal(a, b) for a, b in zip(first, again))
+        assert list(first[0][:2]) == [0, 1 << 40] and list(first[4]) == [0, 1]  # "!" is Q0, p = 1
+        check_columns(s, bam_ref.Columns(raw))
+        s.close()
