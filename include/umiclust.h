@@ -393,6 +393,38 @@ int32_t umiclust_bam_cs_groups(umiclust_ctx *ctx, int64_t *count, int64_t *rep);
  * pysam.AlignmentFile(..., "wb", template=bam_in).write(entry) leaves, :207/:245, up to the compressed form);
  * returns the number written */
 int64_t umiclust_bam_write(umiclust_ctx *ctx, const uint8_t *keep, const char *out_bam);
+
+/* ---- round-2 region split and precision census on the session (rows f4b / f6b) ---- */
+/* Replaces the record loops of filter_and_split_reads_by_region (ont_tcr_consensus/region_split.py:336-435) and of
+ * estimate_precision_at_num_subreads (minimap2_align.py:362-435), which the reference runs on the filtered consensus
+ * BAM: the session that filtered it is split under the filter's keep mask, so one inflate and one scan serve the
+ * filter, the filtered BAM, the cs census and the split.
+ * Memory model: the session keeps the inflated file, the record offsets and the columns on the host only.  Each of
+ * the two calls uploads what its kernel reads (the raw bytes and offsets; for the split also class, refID, l_seq,
+ * reference_length and keep) and frees it on return. */
+/* Split the open session's records (keep == NULL: all; else those with keep[r] != 0, the others being "not in the
+ * file": skipped and counted nowhere) into FASTA buckets.  Region r of the reference FASTA goes to bucket
+ * region_buckets[r] (in [0, nbuckets), or -1: the lookup raises, as a region missing from the cluster JSON does);
+ * bucket b is appended to bucket_paths[b] as `>{query_name};strand={+|-}` + the forward sequence (`None` without
+ * one), in BAM order.  A record is classified from the session's columns with umiclust_region_split's comparisons
+ * (reference_length < L * overlap; l_seq > L * (2 - overlap) + (s5 + s3), the product rounded before the add).
+ * counts = {n_unmapped, n_primary_mapped, n_short, n_long}; reads_per_bucket[nbuckets]; region_detected[nregions]
+ * (may be NULL).  Returns the number of files appended to.
+ * A primary record whose reference is not among the regions, whose refID is -1 (name `None`) or whose bucket is -1
+ * stops the loop as umiclust_region_split's does: the records before it are written, the counters cover it as a
+ * primary alignment, and UMICLUST_EFORMAT is returned with the name in missing_name.  Only kept primary records are
+ * emitted and the open has checked their fields, so none is checked again (an empty name field: UMICLUST_EFORMAT).
+ * UMICLUST_ESTATE without an open session, UMICLUST_EIO for a bucket path that cannot be appended to. */
+int64_t umiclust_bam_split(umiclust_ctx *ctx, const uint8_t *keep, int32_t nregions, const char *const *region_names,
+                           const int64_t *region_lengths, const int32_t *region_buckets, int32_t nbuckets,
+                           const char *const *bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
+                           int32_t max_softclip_3_end, int64_t *counts, int64_t *reads_per_bucket,
+                           uint8_t *region_detected, char *missing_name, int32_t missing_cap);
+/* Per record (n-sized arrays, either may be NULL) the query name's tail: what follows its last "_", or the whole name
+ * without one.  A tail of 1 to 18 ASCII digits (leading zeros included): value[r] = its decimal value, status[r] = 1.
+ * Any other tail (empty, signed, a non-digit, 19 digits or more): status[r] = 0, value[r] = 0, and the caller applies
+ * int(name.split("_")[-1]) itself so that the value or the ValueError is Python's own. */
+int32_t umiclust_bam_name_suffix(umiclust_ctx *ctx, int64_t *value, uint8_t *status);
 int32_t umiclust_bam_close(umiclust_ctx *ctx);
 
 /* ---- kernel-level entry points (parity tests) ---- */

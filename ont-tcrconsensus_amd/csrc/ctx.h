@@ -89,7 +89,8 @@ struct FqState {
 };
 
 // BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
-// the columns of the device scan
+// the columns of the device scan.  Host memory only: umiclust_bam_split and umiclust_bam_name_suffix (f4b / f6b)
+// upload what their kernels read and free it on return
 struct BamSession {
   bool open = false;
   std::vector<uint8_t> raw;

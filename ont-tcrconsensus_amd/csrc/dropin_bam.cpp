@@ -1,5 +1,6 @@
 // dropin_bam.cpp -- the two BAM readers: region binning (§8f f4, regionsplit.hip) and the BAM session with its scan,
-// cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip).  Their HIP-free halves are in bam_host.h.
+// cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip), and on the session the round-2 region split and the
+// name suffix (§8f f4b / f6b, DESIGN.md §9c, bamsplit.hip).  Their HIP-free halves are in bam_host.h.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -26,6 +27,59 @@ std::string_view record_name(const std::vector<uint8_t>& raw, const std::vector<
 BamSession* bam_session(Ctx* c) {
   if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
   return &c->bs;
+}
+// The kept records among [0, stop) as FASTA text, grouped by bucket and in BAM order within a bucket: the slots are
+// laid out here, the bytes written by k_bam_emit, and every bucket's text is appended to path_of(bucket) (the
+// reference opens the file with "a" for every record).  d_pos: room for a slot per record.  Returns the buckets that
+// got a record; a file that cannot be appended to is UMICLUST_EIO.
+template <typename PathOf>
+std::vector<int32_t> emit_buckets(Ctx* c, const uint8_t* d_raw, const int64_t* d_roff, const int8_t* d_cls,
+                                  DevBuf<int64_t>& d_pos, const std::vector<int8_t>& cls,
+                                  const std::vector<int32_t>& bkt, const std::vector<int64_t>& olen, int64_t stop,
+                                  PathOf path_of) {
+  const int64_t n = (int64_t)cls.size();
+  int32_t nb = 0;
+  for (int64_t r = 0; r < stop; r++)
+    if (cls[r] == kBamKept) nb = std::max(nb, bkt[r] + 1);
+  std::vector<int64_t> cbase((size_t)nb + 1, 0), pos(n, -1);
+  for (int64_t r = 0; r < stop; r++)
+    if (cls[r] == kBamKept) cbase[bkt[r] + 1] += olen[r];
+  for (int32_t k = 0; k < nb; k++) cbase[k + 1] += cbase[k];
+  {
+    std::vector<int64_t> cur(cbase.begin(), cbase.end() - 1);
+    for (int64_t r = 0; r < stop; r++)
+      if (cls[r] == kBamKept) {
+        pos[r] = cur[bkt[r]];
+        cur[bkt[r]] += olen[r];
+      }
+  }
+  std::vector<char> outb((size_t)cbase[nb] + 1);
+  DevBuf<char> d_out;
+  c->hip(d_out.ensure(outb.size()), "alloc");
+  if (stop) {
+    c->hip(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)stop * 8, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(launch_bam_emit(d_raw, d_roff, stop, d_cls, d_pos.p, d_out.p, c->st), "bam emit");
+    c->hip(hipMemcpyAsync(outb.data(), d_out.p, (size_t)cbase[nb], hipMemcpyDeviceToHost, c->st), "d2h");
+  }
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  std::vector<int32_t> used;
+  for (int32_t k = 0; k < nb; k++)
+    if (cbase[k + 1] > cbase[k]) used.push_back(k);
+  const int T = std::max(1, std::min<int>(io_threads(), (int)used.size()));
+  std::vector<int32_t> bad(T, -1);
+  parallel_for(T, [&](int t) {
+    for (size_t u = (size_t)t; u < used.size(); u += (size_t)T) {
+      const int32_t k = used[u];
+      const std::string fn = path_of(k);
+      const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0666);
+      bool ok = fd >= 0 && io::write_all(fd, outb.data() + cbase[k], (size_t)(cbase[k + 1] - cbase[k]));
+      if (fd >= 0) ok = (close(fd) == 0) && ok;
+      if (!ok) bad[t] = k;
+    }
+  });
+  for (int32_t v : bad)
+    if (v >= 0) c->fail(UMICLUST_EIO, "cannot append %s", path_of(v).c_str());
+  return used;
 }
 }  // namespace
 
@@ -98,45 +152,8 @@ int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t n
     for (int64_t r = 0; r < stop; r++)
       if (cls[r] == kBamKept) ncl = std::max(ncl, clu[r] + 1);
     // output grouped by cluster, records in BAM order within a cluster
-    std::vector<int64_t> cbase((size_t)ncl + 1, 0), pos(n, -1);
-    for (int64_t r = 0; r < stop; r++)
-      if (cls[r] == kBamKept) cbase[clu[r] + 1] += olen[r];
-    for (int32_t k = 0; k < ncl; k++) cbase[k + 1] += cbase[k];
-    {
-      std::vector<int64_t> cur(cbase.begin(), cbase.end() - 1);
-      for (int64_t r = 0; r < stop; r++)
-        if (cls[r] == kBamKept) {
-          pos[r] = cur[clu[r]];
-          cur[clu[r]] += olen[r];
-        }
-    }
-    std::vector<char> outb((size_t)cbase[ncl] + 1);
-    DevBuf<char> d_out;
-    c->hip(d_out.ensure(outb.size()), "alloc");
-    if (stop) {
-      c->hip(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)stop * 8, hipMemcpyHostToDevice, c->st), "h2d");
-      c->hip(launch_bam_emit(d_raw.p, d_roff.p, stop, d_cls.p, d_pos.p, d_out.p, c->st), "bam emit");
-      c->hip(hipMemcpyAsync(outb.data(), d_out.p, (size_t)cbase[ncl], hipMemcpyDeviceToHost, c->st), "d2h");
-    }
-    c->hip(hipStreamSynchronize(c->st), "sync");
-    // append per cluster (the reference opens region_cluster<k>.fasta with "a" for every record)
-    std::vector<int32_t> used;
-    for (int32_t k = 0; k < ncl; k++)
-      if (cbase[k + 1] > cbase[k]) used.push_back(k);
-    const int T = std::max(1, std::min<int>(io_threads(), (int)used.size()));
-    std::vector<int32_t> bad(T, -1);
-    parallel_for(T, [&](int t) {
-      for (size_t u = (size_t)t; u < used.size(); u += (size_t)T) {
-        const int32_t k = used[u];
-        const std::string fn = pjoin(out_dir, "region_cluster" + std::to_string(k) + ".fasta");
-        const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0666);
-        bool ok = fd >= 0 && io::write_all(fd, outb.data() + cbase[k], (size_t)(cbase[k + 1] - cbase[k]));
-        if (fd >= 0) ok = (close(fd) == 0) && ok;
-        if (!ok) bad[t] = k;
-      }
-    });
-    for (int32_t v : bad)
-      if (v >= 0) c->fail(UMICLUST_EIO, "cannot append region_cluster%d.fasta", v);
+    const auto cluster_fasta = [&](int32_t k) { return pjoin(out_dir, "region_cluster" + std::to_string(k) + ".fasta"); };
+    const std::vector<int32_t> used = emit_buckets(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, olen, stop, cluster_fasta);
     // counters of the records the reference reached
     int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
     if (reads_per_cluster) memset(reads_per_cluster, 0, sizeof(int64_t) * (size_t)ncluster_cap);
@@ -390,6 +407,126 @@ int64_t umiclust_bam_write(umiclust_ctx* ctx, const uint8_t* keep, const char* o
     const int64_t k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
     if (k < 0) c->fail(UMICLUST_EIO, "%s", err.c_str());
     return k;
+  });
+}
+
+// ---------------------------------------------------------------- region split and name suffix on the session (§8f f4b / f6b)
+// The session holds the inflated file and its columns on the host only (ctx.h BamSession), so each of the two calls
+// below uploads what its kernel reads -- the raw bytes and record offsets, and for the split the four columns and the
+// keep mask -- and frees it on return: no device memory outlives a call.
+int64_t umiclust_bam_split(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregions, const char* const* region_names,
+                           const int64_t* region_lengths, const int32_t* region_buckets, int32_t nbuckets,
+                           const char* const* bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
+                           int32_t max_softclip_3_end, int64_t* counts, int64_t* reads_per_bucket,
+                           uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_buckets)) || nbuckets < 0 ||
+        (nbuckets > 0 && (!bucket_paths || !reads_per_bucket)) || !counts)
+      c->fail(UMICLUST_EINVAL, "bad argument");
+    for (int32_t r = 0; r < nregions; r++)
+      if (region_buckets[r] >= nbuckets) c->fail(UMICLUST_EINVAL, "region %d: bucket %d of %d", r, region_buckets[r], nbuckets);
+    std::unordered_map<std::string, int32_t> rid;
+    for (int32_t r = 0; r < nregions; r++) rid.emplace(region_names[r], r);
+    const int32_t nref = (int32_t)S.hdr.ref_name.size();
+    std::vector<int64_t> rlen(nref, -1);
+    std::vector<int32_t> rbkt(nref, -1), rreg(nref, -1);
+    for (int32_t r = 0; r < nref; r++) {
+      auto it = rid.find(S.hdr.ref_name[r]);
+      if (it != rid.end()) {
+        rreg[r] = it->second;
+        rlen[r] = region_lengths[it->second];
+        rbkt[r] = region_buckets[it->second];
+      }
+    }
+    const int64_t n = (int64_t)S.roff.size();
+    DevBuf<uint8_t> d_raw, d_keep;
+    DevBuf<int64_t> d_roff, d_reflen, d_rlen, d_outlen, d_pos;
+    DevBuf<int32_t> d_ref, d_lseq, d_rbkt, d_bkt;
+    DevBuf<int8_t> d_scan, d_cls;
+    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
+    alloc_each(c, (size_t)n + 1, d_keep, d_roff, d_reflen, d_outlen, d_pos, d_ref, d_lseq, d_bkt, d_scan, d_cls);
+    alloc_each(c, (size_t)nref + 1, d_rlen, d_rbkt);
+    auto h2d = [&](void* dst, const void* src, size_t bytes) {
+      if (bytes) c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->st), "h2d");
+    };
+    h2d(d_raw.p, S.raw.data(), S.raw.size()), h2d(d_roff.p, S.roff.data(), (size_t)n * 8);
+    h2d(d_scan.p, S.cls.data(), (size_t)n), h2d(d_ref.p, S.ref.data(), (size_t)n * 4);
+    h2d(d_lseq.p, S.l_seq.data(), (size_t)n * 4), h2d(d_reflen.p, S.reflen.data(), (size_t)n * 8);
+    if (keep) h2d(d_keep.p, keep, (size_t)n);
+    h2d(d_rlen.p, rlen.data(), (size_t)nref * 8), h2d(d_rbkt.p, rbkt.data(), (size_t)nref * 4);
+    BamScanCols o{};
+    o.cls = d_scan.p, o.ref = d_ref.p, o.l_seq = d_lseq.p, o.reflen = d_reflen.p;
+    c->hip(launch_split_cols(o, d_raw.p, d_roff.p, keep ? d_keep.p : nullptr, n, nref, d_rlen.p, d_rbkt.p,
+                             minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, d_cls.p, d_bkt.p,
+                             d_outlen.p, c->st),
+           "split cols");
+    std::vector<int8_t> cls(n);
+    std::vector<int32_t> bkt(n);
+    std::vector<int64_t> olen(n);
+    if (n) {
+      c->hip(hipMemcpyAsync(cls.data(), d_cls.p, (size_t)n, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(bkt.data(), d_bkt.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->st), "d2h");
+      c->hip(hipMemcpyAsync(olen.data(), d_outlen.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st), "d2h");
+    }
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    // the reference raises KeyError at the first primary record whose region is unknown, after the records before it
+    int64_t stop = n;
+    for (int64_t r = 0; r < n && stop == n; r++)
+      if (cls[r] == kBamNoRegion || cls[r] == kBamNoCluster) stop = r;
+    // k_bam_emit indexes the name, the CIGAR and the sequence of a kept record by its own fields.  Kept records are
+    // primary, and the open has refused every primary record whose l_seq is negative or whose fields overrun its
+    // block_size, so no second field check is made here; what the open does not look at is an empty name field.
+    for (int64_t r = 0; r < stop; r++)
+      if (cls[r] == kBamKept && S.raw[(size_t)S.roff[r] + 12] == 0)
+        c->fail(UMICLUST_EFORMAT, "BAM record %lld: l_read_name 0", (long long)r);
+    const std::vector<int32_t> used = emit_buckets(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, bkt, olen, stop,
+                                                   [&](int32_t b) { return std::string(bucket_paths[b]); });
+    // counters of the records the reference reached
+    int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
+    if (nbuckets) memset(reads_per_bucket, 0, sizeof(int64_t) * (size_t)nbuckets);
+    if (region_detected && nregions) memset(region_detected, 0, (size_t)nregions);
+    const int64_t last = stop < n ? stop + 1 : n;  // the failing record counts as a primary alignment too
+    for (int64_t r = 0; r < last; r++) {
+      const int8_t k = cls[r];
+      if (k == kBamUnmapped) cnt[0]++;
+      if (k >= kBamShort && k != kBamAbsent) cnt[1]++;
+      if (k == kBamShort) cnt[2]++;
+      if (k == kBamLong) cnt[3]++;
+      if (k == kBamKept && r < stop) {
+        reads_per_bucket[bkt[r]]++;
+        if (region_detected) region_detected[rreg[S.ref[r]]] = 1;
+      }
+    }
+    for (int x = 0; x < 4; x++) counts[x] = cnt[x];
+    if (stop < n) {
+      const int32_t ref = S.ref[stop];
+      const std::string nm = ref >= 0 && ref < nref ? S.hdr.ref_name[ref] : std::string("None");
+      if (missing_name && missing_cap > 0) snprintf(missing_name, (size_t)missing_cap, "%s", nm.c_str());
+      c->fail(UMICLUST_EFORMAT, "KeyError: '%s'", nm.c_str());
+    }
+    return (int64_t)used.size();
+  });
+}
+
+int32_t umiclust_bam_name_suffix(umiclust_ctx* ctx, int64_t* value, uint8_t* status) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    const int64_t n = (int64_t)S.roff.size();
+    if (!n) return UMICLUST_OK;
+    DevBuf<uint8_t> d_raw, d_status;
+    DevBuf<int64_t> d_roff, d_value;
+    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
+    alloc_each(c, (size_t)n, d_roff, d_value, d_status);
+    c->hip(hipMemcpyAsync(d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
+    c->hip(launch_name_suffix(d_raw.p, d_roff.p, n, d_value.p, d_status.p, c->st), "name suffix");
+    if (value) c->hip(hipMemcpyAsync(value, d_value.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st), "d2h");
+    if (status) c->hip(hipMemcpyAsync(status, d_status.p, (size_t)n, hipMemcpyDeviceToHost, c->st), "d2h");
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    return UMICLUST_OK;
   });
 }
 

@@ -14,6 +14,7 @@
 
 #include <stdint.h>
 
+#include "bam_bounds.h"
 #include "umiclust_internal.h"
 
 namespace uc {
@@ -23,15 +24,7 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
 }
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
-// region_length * (2 - minimal_region_overlap) + (max_softclip_5_end + max_softclip_3_end) as the reference evaluates
-// it (:264-267): the product rounded to a double, then the add.  Contracted into one fma (the compiler's default, and
-// __dmul_rn / __dadd_rn do not prevent it) the bound can land one ulp lower, and a read exactly at it drops as long:
-// region 400, overlap 0.93, slack 141 gives 569.0 rounded and 568.9999999999999 fused.
-__device__ __forceinline__ double long_bound(double L, double minov, int32_t slack) {
-#pragma clang fp contract(off)
-  const double prod = L * (2.0 - minov);
-  return prod + (double)slack;
-}
+// long_bound, the `too long` bound as the reference rounds it (:264-267): bam_bounds.h
 
 // per record: class (kBamUnmapped ... kBamNoCluster), cluster, output bytes
 __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* __restrict__ roff, int64_t n,

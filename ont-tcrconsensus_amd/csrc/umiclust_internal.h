@@ -298,4 +298,15 @@ hipError_t launch_cs_group(const uint8_t* raw, const BamScanCols& o, int64_t n, 
                            unsigned long long* rep, uint32_t* cnt, int64_t* slot, uint32_t* collision,
                            hipStream_t st);
 
+// ---- region split and name suffix on the session's columns (bamsplit.hip; rows f4b / f6b) ----
+constexpr int8_t kBamAbsent = 7;  // keep[r] == 0: the record is not in the file that is being split
+// classes of launch_bam_classify (+ kBamAbsent) from o.cls / o.ref / o.l_seq / o.reflen alone (the other columns are
+// not read); keep may be null; ref_len / ref_bucket per BAM reference (-1: not a region / no bucket)
+hipError_t launch_split_cols(const BamScanCols& o, const uint8_t* raw, const int64_t* roff, const uint8_t* keep,
+                             int64_t n, int32_t nref, const int64_t* ref_len, const int32_t* ref_bucket, double minov,
+                             int32_t s5, int32_t s3, int8_t* cls, int32_t* bucket, int64_t* outlen, hipStream_t st);
+// value / status of the query name's last "_" field: status 1 = 1..18 ASCII digits, 0 = anything else
+hipError_t launch_name_suffix(const uint8_t* raw, const int64_t* roff, int64_t n, int64_t* value, uint8_t* status,
+                              hipStream_t st);
+
 }  // namespace uc

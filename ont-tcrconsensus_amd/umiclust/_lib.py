@@ -132,7 +132,8 @@ EXPORTS = [
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
-    "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_close",
+    "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
+    "umiclust_bam_name_suffix", "umiclust_bam_close",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -271,6 +272,12 @@ def lib() -> C.CDLL:
     L.umiclust_bam_cs_groups.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.umiclust_bam_write.restype = C.c_int64
     L.umiclust_bam_write.argtypes = [C.c_void_p, P(C.c_uint8), C.c_char_p]
+    L.umiclust_bam_split.restype = C.c_int64
+    L.umiclust_bam_split.argtypes = [C.c_void_p, P(C.c_uint8), C.c_int32, P(C.c_char_p), P(C.c_int64), P(C.c_int32),
+                                     C.c_int32, P(C.c_char_p), C.c_double, C.c_int32, C.c_int32, P(C.c_int64),
+                                     P(C.c_int64), P(C.c_uint8), C.c_char_p, C.c_int32]
+    L.umiclust_bam_name_suffix.restype = C.c_int32
+    L.umiclust_bam_name_suffix.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_uint8)]
     L.umiclust_bam_close.restype = C.c_int32
     L.umiclust_bam_close.argtypes = [C.c_void_p]
     _lib = L
@@ -740,7 +747,8 @@ class BamSession:
     """The columns of an open BAM session (umiclust_bam_*), read once; names and cs strings are gathered in bulk on
     request.  The attributes are what umiclust.minimap2_align's formatting half takes from any source: n, cls, ref,
     l_seq, reference_length, cols, nm, nm_present, cs_group, ref_names, ref_lengths, query_names(idx),
-    cs_strings(idx), write(keep, path)."""
+    cs_strings(idx), write(keep, path), and -- for the round-2 split and the precision census --
+    split(...) and name_suffix()."""
 
     def __init__(self, ctx: Context):
         self._ctx = ctx
@@ -795,6 +803,42 @@ class BamSession:
             raise ValueError("keep needs one entry per record")
         return int(self._ctx._check(lib().umiclust_bam_write(
             self._ctx._h, keep.ctypes.data_as(C.POINTER(C.c_uint8)), os.fspath(path).encode()), "bam_write"))
+
+    def split(self, keep, names, lengths, buckets, bucket_paths, overlap: float, s5: int, s3: int):
+        """umiclust_bam_split: the records (keep None: all, else those with keep[r] != 0) appended as FASTA to
+        bucket_paths[buckets[region]]; (counts[4], reads_per_bucket, region_detected).  KeyError(name) as
+        Context.region_split raises it."""
+        R, B = len(names), len(bucket_paths)
+        P = C.POINTER
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            if len(keep) != self.n:
+                raise ValueError("keep needs one entry per record")
+            kp = keep.ctypes.data_as(P(C.c_uint8))
+        nm = (C.c_char_p * max(R, 1))(*[x.encode() for x in names])
+        paths = (C.c_char_p * max(B, 1))(*[os.fspath(x).encode() for x in bucket_paths])
+        ln = np.ascontiguousarray(lengths, np.int64)
+        bk = np.ascontiguousarray(buckets, np.int32)
+        counts = np.zeros(4, np.int64)
+        per_bucket = np.zeros(max(B, 1), np.int64)
+        det = np.zeros(max(R, 1), np.uint8)
+        miss = C.create_string_buffer(4096)
+        rc = lib().umiclust_bam_split(self._ctx._h, kp, R, nm, _i64(ln), bk.ctypes.data_as(P(C.c_int32)), B, paths,
+                                      overlap, s5, s3, _i64(counts), _i64(per_bucket), det.ctypes.data_as(P(C.c_uint8)),
+                                      miss, 4096)
+        if rc == -74 and miss.value:
+            raise KeyError(miss.value.decode())
+        self._ctx._check(rc, "bam_split")
+        return counts, per_bucket[:B], det[:R]
+
+    def name_suffix(self) -> tuple[np.ndarray, np.ndarray]:
+        """umiclust_bam_name_suffix: per record (value, status) of the query name's last "_" field; status 0 where the
+        field is not 1..18 ASCII digits and int() has to decide."""
+        value, status = np.zeros(self.n, np.int64), np.zeros(self.n, np.uint8)
+        self._ctx._check(lib().umiclust_bam_name_suffix(self._ctx._h, _i64(value),
+                                                        status.ctypes.data_as(C.POINTER(C.c_uint8))), "bam_name_suffix")
+        return value, status
 
     def close(self) -> None:
         if self._ctx is not None:

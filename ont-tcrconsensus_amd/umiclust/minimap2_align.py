@@ -1,6 +1,8 @@
 """Drop-ins for the per-record loops of ont_tcr_consensus/minimap2_align.py:
-count_cs_tags (:21-37), the cs-tag log blocks of minimap2_ont_align (:141-150) and filter_consensus_alignments
-(:158-359).
+count_cs_tags (:21-37), the cs-tag log blocks of minimap2_ont_align (:141-150), filter_consensus_alignments
+(:158-359) and estimate_precision_at_num_subreads (:362-435, row f6b); and
+filter_consensus_alignments_and_split, which runs the filter and the round-2 split of region_split.py:336-435 on one
+session.
 
 The BAM is read once by a session of the library (umiclust_bam_open: BGZF inflated on the host threads, every
 record scanned and the cs:Z strings grouped exactly on the GPU); this module only forms the reference's floats and
@@ -19,7 +21,7 @@ from typing import Union
 import numpy as np
 
 from . import vsearch_umi_cluster as _v
-from .region_split import generate_region_length_dict_from_ref_fa
+from .region_split import filter_and_split_reads_by_region_from, generate_region_length_dict_from_ref_fa
 
 PRIMARY = 2  # the cls column: 0 unmapped, 1 secondary or supplementary, 2 primary mapped
 
@@ -150,6 +152,13 @@ def filter_consensus_alignments_from(src, consensus_bam_file, reference, logs_di
     """filter_consensus_alignments (:158-359) over the columns of `src` (a _lib.BamSession, or any object with its
     attributes): the decisions, the seven CSVs, the log and -- through src.write -- the filtered BAM.  Values and
     texts are pinned by tests/golden/bam_filter, which the reference's own function produced."""
+    return _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
+                                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)[0]
+
+
+def _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
+                                 minimal_region_overlap, max_softclip_5_end, max_softclip_3_end):
+    """filter_consensus_alignments_from, returning (filtered BAM path, keep): keep[r] != 0 for the records written"""
     stem = os.path.basename(consensus_bam_file).split(".")[0]
     filtered = os.path.splitext(consensus_bam_file)[0] + "_filtered.bam"
     lengths = generate_region_length_dict_from_ref_fa(reference=reference)
@@ -247,7 +256,7 @@ def filter_consensus_alignments_from(src, consensus_bam_file, reference, logs_di
         _write_lines(fh, lines)
         # :341-357 re-reads the file it just wrote; its records are the kept ones of this session
         fh.write(cs_tag_report(src, keep=keep))
-    return filtered
+    return filtered, keep
 
 
 def filter_consensus_alignments(consensus_bam_file: Union[str, os.PathLike[str]],
@@ -258,3 +267,78 @@ def filter_consensus_alignments(consensus_bam_file: Union[str, os.PathLike[str]]
     with _Opened(consensus_bam_file) as src:
         return filter_consensus_alignments_from(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
                                                 minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+
+
+def filter_consensus_alignments_and_split(consensus_bam_file: Union[str, os.PathLike[str]],
+                                          reference: Union[str, os.PathLike[str]],
+                                          logs_dir: Union[str, os.PathLike[str]], blast_id_threshold: float,
+                                          region_fasta_out_dir: Union[str, os.PathLike[str]],
+                                          minimal_region_overlap: float = 0.9975, max_softclip_5_end: int = 73,
+                                          max_softclip_3_end: int = 68):
+    """tcr_consensus.py's filter_consensus_alignments (:366-374) and filter_and_split_reads_by_region (:376-384) on one
+    session: the filter runs as above (it still writes and indexes the filtered BAM), then the session's records are
+    split under the filter's keep mask instead of the filtered BAM being read back.  The split takes the filter's
+    overlap and softclip arguments, as :376-384 passes them, and names its log after the filtered BAM, as the two-step
+    call does.  Returns (filtered BAM path, list of region_<name>.fasta paths)."""
+    with _Opened(consensus_bam_file) as src:
+        filtered, keep = _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
+                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+        fastas = filter_and_split_reads_by_region_from(src, keep, filtered, reference, logs_dir, region_fasta_out_dir,
+                                                       minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+    return filtered, fastas
+
+
+def estimate_precision_at_num_subreads_from(src, consensus_bam_file, reference, logs_dir, minimal_region_overlap=1.0,
+                                            blast_id_threshold=1.0, max_softclip_5_end=73, max_softclip_3_end=68,
+                                            num_subreads_threshold=6):
+    """estimate_precision_at_num_subreads (:362-435) over the columns and name_suffix() of `src`: the CSV and the five
+    printed lines.  Pinned by tests/golden/precision, which the reference's own function produced."""
+    path = os.path.join(logs_dir, os.path.basename(consensus_bam_file).split(".")[0]
+                        + "_precision_at_different_num_subreads.csv")
+    lengths = generate_region_length_dict_from_ref_fa(reference=reference)
+    overlap, clip = minimal_region_overlap, max_softclip_5_end + max_softclip_3_end
+    primary = np.flatnonzero(np.asarray(src.cls) == PRIMARY)
+    value, status = src.name_suffix()
+    # a tail the device does not read as 1..18 digits goes through int() itself: its value or its ValueError
+    odd = primary[np.asarray(status)[primary] == 0]
+    odd_name = dict(zip(odd.tolist(), src.query_names(odd)))
+    spans = np.asarray(src.reference_length)[primary].tolist()  # Python ints, as in the filter above
+    reads = np.asarray(src.l_seq)[primary].tolist()
+    mapped, written = collections.defaultdict(int), collections.defaultdict(int)
+    n_primary = n_mapped_above = n_written_above = 0
+    for j, r in enumerate(primary.tolist()):
+        n_primary += 1
+        num_subreads = int(odd_name[r].split("_")[-1]) if r in odd_name else int(value[r])
+        mapped[num_subreads] += 1
+        if num_subreads >= num_subreads_threshold:
+            n_mapped_above += 1
+        region = _reference_name(src, r)
+        if spans[j] < lengths[region] * overlap:  # KeyError(region): a reference that the FASTA does not hold
+            continue
+        if reads[j] > lengths[region] * (2 - overlap) + clip:
+            continue
+        if _blast_id(src, r) >= blast_id_threshold:
+            written[num_subreads] += 1
+            if num_subreads >= num_subreads_threshold:
+                n_written_above += 1
+    # (Series(written) / Series(mapped)).fillna(0).sort_index().to_csv(header=True, index_label="num_subreads")
+    _to_csv(path, ["num_subreads", "precision"], [(k, written[k] / mapped[k] if k in written else 0.0)
+                                                  for k in sorted(mapped)])
+    expanded = [k for k, count in mapped.items() for _ in range(count)]
+    print(n_written_above, n_mapped_above)
+    print("median # of subreads:", np.median(expanded))
+    print("mean # of subreads:", np.mean(expanded))
+    print("n primary mapped:", n_primary)
+    print("Overall precision above " + str(num_subreads_threshold) + " is:", n_written_above / n_mapped_above)
+
+
+def estimate_precision_at_num_subreads(consensus_bam_file: Union[str, os.PathLike[str]],
+                                       reference: Union[str, os.PathLike[str]], logs_dir: Union[str, os.PathLike[str]],
+                                       minimal_region_overlap: float = 1.0, blast_id_threshold: float = 1.0,
+                                       max_softclip_5_end: int = 73, max_softclip_3_end: int = 68,
+                                       num_subreads_threshold: int = 6):
+    """:362-435 -- same signature, defaults, CSV and printed lines; no pandas."""
+    with _Opened(consensus_bam_file) as src:
+        return estimate_precision_at_num_subreads_from(src, consensus_bam_file, reference, logs_dir,
+                                                       minimal_region_overlap, blast_id_threshold, max_softclip_5_end,
+                                                       max_softclip_3_end, num_subreads_threshold)

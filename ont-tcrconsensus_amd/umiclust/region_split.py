@@ -6,6 +6,11 @@ Same signature, defaults, files (append-mode region_cluster<k>.fasta, the
 set's order).  The BAM record loop runs in the library (umiclust_region_split: BGZF inflated on the host
 threads, records classified and FASTA records built on the GPU); the log is formatted here with the same
 Python expressions as the reference.  No CPU fallback.
+
+Also the round-2 function of the same file, filter_and_split_reads_by_region (:336-435, row f4b): one
+append-mode region_<name>.fasta per reference name, no cluster lookup, the
+<bam>_filter_and_split_reads_by_region.err log.  It runs on a BAM session (umiclust_bam_open + umiclust_bam_split),
+so that minimap2_align.filter_consensus_alignments_and_split can split the session that filtered the consensus BAM.
 """
 from __future__ import annotations
 
@@ -101,3 +106,71 @@ def filter_and_split_reads_by_region_cluster(bam_file: Union[str, os.PathLike[st
         ferr.write(logging_str)
     del n_unmapped
     return list(region_cluster_fasta_set)
+
+
+def filter_and_split_reads_by_region_from(src, keep, bam_file, reference, logs_dir, region_fasta_out_dir,
+                                          minimal_region_overlap=0.95, max_softclip_5_end=73, max_softclip_3_end=68):
+    """filter_and_split_reads_by_region (region_split.py:336-435) over an open BAM session `src` (a _lib.BamSession, or
+    any object with its attributes and split()): the records with keep[r] != 0 (keep None: all) are the file.  One
+    append-mode region_<name>.fasta per reference name, the <bam>_filter_and_split_reads_by_region.err log named after
+    `bam_file`, and the list of the FASTA paths written, in a set's order.  Pinned by tests/golden/by_region, which
+    the reference's own function produced."""
+    log_file = os.path.join(logs_dir, os.path.basename(bam_file).split(".")[0] + "_filter_and_split_reads_by_region.err")
+    region_length_dict = generate_region_length_dict_from_ref_fa(reference=reference)
+    names = list(region_length_dict)
+    paths = [os.path.join(region_fasta_out_dir, "region_{}.fasta".format(n)) for n in names]
+    try:
+        counts, per_region, detected = src.split(keep, names, [region_length_dict[n] for n in names],
+                                                 list(range(len(names))), paths, minimal_region_overlap,
+                                                 max_softclip_5_end, max_softclip_3_end)
+    except KeyError:
+        # the reference looks the region up for every primary record, before either filter (:374): the first one
+        # whose reference name the FASTA lacks raises, and a refID of -1 is the name None, not the string 'None'
+        ref = np.asarray(src.ref)
+        primary = np.asarray(src.cls) == 2
+        if keep is not None:
+            primary &= np.asarray(keep) != 0
+        for r in np.flatnonzero(primary).tolist():
+            name = src.ref_names[ref[r]] if 0 <= ref[r] < len(src.ref_names) else None
+            if name not in region_length_dict:
+                raise KeyError(name) from None
+        raise
+    n_unmapped, n_primary_mapped, n_short, n_long = (int(x) for x in counts)
+    n_reads_region_counter = {names[r]: int(v) for r, v in enumerate(per_region) if v}
+    region_fasta_set = {paths[r] for r, v in enumerate(per_region) if v}
+    detected_regions_set = {names[r] for r, d in enumerate(detected) if d}
+
+    # the log, as region_split.py:397-430 builds it
+    logging_str = "Total # primary alignments in bam file: " + str(n_primary_mapped) + "\n"
+    logging_str += ("median # of primary alignments in regions that have minimal region overlap and are not too long: "
+                    + str(round(np.median(list(n_reads_region_counter.values())), 3)) + "\n")
+    logging_str += ("% of primary alignments that have shorter overlap than minimal region overlap: "
+                    + str(round(100 * n_short / n_primary_mapped, 2)) + "\n")
+    logging_str += "% of primary alignments that have too long reads: " + str(round(100 * n_long / n_primary_mapped, 2)) + "\n"
+    regions_set = generate_regions_set_from_ref_fa(reference=reference, remove_negative_control_regions=True,
+                                                   negative_control_regions_suffix_str_tuple=NEGATIVE_CONTROL_SUFFIXES)
+    detected_regions_set = set([r for r in detected_regions_set if not r.endswith(NEGATIVE_CONTROL_SUFFIXES)])
+    fraction_regions_detected = len(regions_set.intersection(detected_regions_set)) / len(regions_set)
+    number_missing_regions = len(regions_set.difference(detected_regions_set))
+    missing_regions = regions_set.difference(detected_regions_set)
+    logging_str += "fraction detected regions of total regions in reference: " + str(round(fraction_regions_detected, 4)) + "\n"
+    logging_str += "# of missing regions from reference: " + str(number_missing_regions) + "\n"
+    logging_str += "missing/non-detected regions from reference: " + str(missing_regions) + "\n"
+    with open(log_file, "w") as ferr:
+        ferr.write(logging_str)
+    del n_unmapped
+    return list(region_fasta_set)
+
+
+def filter_and_split_reads_by_region(bam_file: Union[str, os.PathLike[str]], reference: Union[str, os.PathLike[str]],
+                                     logs_dir: Union[str, os.PathLike[str]],
+                                     region_fasta_out_dir: Union[str, os.PathLike[str]],
+                                     minimal_region_overlap: float = 0.95, max_softclip_5_end: int = 73,
+                                     max_softclip_3_end: int = 68):
+    """region_split.py:336-435 -- same signature, defaults, files and return value.  The file is read by a BAM session
+    (umiclust_bam_open), which also walks the aux tags of its primary records and groups their cs strings; the split
+    needs neither, but the reference calls this function on the filtered consensus BAM alone, a small file, and
+    minimap2_align.filter_consensus_alignments_and_split splits the filter's own session without reading it again."""
+    with _v.context().bam_open(os.fspath(bam_file)) as src:
+        return filter_and_split_reads_by_region_from(src, None, bam_file, reference, logs_dir, region_fasta_out_dir,
+                                                     minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
