@@ -305,7 +305,8 @@ int64_t umiclust_region_split(umiclust_ctx *ctx, const char *bam_file, int32_t n
  * expected error in fixed point (ee_fx = sum of llrint(10^(-q/10) * 2^40), order-independent), and the host decides,
  * recomputing in double exactly as vsearch states it whatever falls within a guard band of a threshold.  Policies
  * O7a-O7f (record form, quality range, expected error, decision order, options, log) are in DESIGN.md §9a.
- * The reference's own seqkit calls (:126-127, :156-157) are not part of this. */
+ * The reference's own seqkit calls (:126-127, :156-157) are served by the same pass when it is asked for them:
+ * umiclust_fastq_filter_stats below (row f5b). */
 typedef struct umiclust_fastq_filter_params {
   int32_t fastq_ascii;      /* --fastq_ascii: 33 (default) or 64 */
   int32_t fastq_qmin;       /* --fastq_qmin (0) */
@@ -346,6 +347,41 @@ int64_t umiclust_fastq_filter(umiclust_ctx *ctx, const umiclust_fastq_filter_par
 /* same, from the exact argv the reference builds */
 int64_t umiclust_fastq_filter_argv(umiclust_ctx *ctx, int32_t argc, const char *const *argv,
                                    umiclust_fastq_filter_result *result);
+
+/* ---- seqkit's `stat -a` tables from the same pass (row f5b; DESIGN.md §9a, policy O8) ---- */
+/* vsearch_fastq_filtering also runs `seqkit stat -a` on the raw FASTQ before the filter
+ * (ont_tcr_consensus/preprocessing.py:126-127) and on the filtered FASTQ after it (:156-157);
+ * analysis.py:76-81 reads the AvgQual column of the text.  The numbers of one table: integers counted exactly, and
+ * the doubles O8c-O8e derive from them alone, so they do not depend on chunk size, thread count or backend. */
+typedef struct umiclust_fastq_stats {
+  int64_t num_seqs, sum_len, min_len, max_len;
+  int64_t n50, n50_num;          /* O8c: the length at which the descending cumulative sum reaches half, and L50 */
+  int64_t n_q20, n_q30;          /* quality bytes with byte - fastq_ascii >= 20 / >= 30 */
+  int64_t n_gc, sum_n, sum_gap;  /* sequence bytes in "GCgc", in "Nn", in "-. " */
+  uint64_t ee_fx_lo, ee_fx_hi;   /* the 128-bit sum of the records' ee_fx (2^-40 units) */
+  int32_t type;                  /* O8f: 0 DNA, 1 RNA, 2 Protein */
+  int32_t pad;
+  double avg_len, q1, q2, q3;    /* O8c */
+  double q20_pct, q30_pct, avg_qual, gc_pct; /* O8d, O8e */
+} umiclust_fastq_stats;
+
+/* umiclust_fastq_filter, and the two tables of preprocessing.py:126-127,156-157 (read by analysis.py:76-81) from
+ * the same pass: stats_before_txt describes every record the filter read (its `file` column is in_fastq),
+ * stats_after_txt every record it kept (`file` is fastqout, "-" without one); the text is policy O8.  before / after
+ * receive the tables' numbers.  Any of the last five arguments may be NULL; with fastqout, fastqout_discarded and
+ * log_path all NULL it is a statistics-only pass.  The two texts are written only when the whole call succeeds: on an
+ * error the filter outputs are what umiclust_fastq_filter leaves and no statistics file is written. */
+int64_t umiclust_fastq_filter_stats(umiclust_ctx *ctx, const umiclust_fastq_filter_params *p, const char *in_fastq,
+                                    const char *fastqout, const char *fastqout_discarded, const char *log_path,
+                                    const char *stats_before_txt, const char *stats_after_txt,
+                                    umiclust_fastq_filter_result *result, umiclust_fastq_stats *before,
+                                    umiclust_fastq_stats *after);
+/* same, from the exact argv the reference builds (:129-148) beside its two seqkit calls (:126-127, :156-157; the
+ * AvgQual column is what analysis.py:76-81 reads) */
+int64_t umiclust_fastq_filter_stats_argv(umiclust_ctx *ctx, int32_t argc, const char *const *argv,
+                                         const char *stats_before_txt, const char *stats_after_txt,
+                                         umiclust_fastq_filter_result *result, umiclust_fastq_stats *before,
+                                         umiclust_fastq_stats *after);
 
 /* ---- consensus alignment filter and cs-tag census (row f6) ---- */
 /* Replaces the per-record loops of ont_tcr_consensus/minimap2_align.py: count_cs_tags (:21-37, called on every
@@ -433,6 +469,14 @@ int32_t umiclust_bam_close(umiclust_ctx *ctx);
  * smallest / largest raw byte (255 / 0 for an empty record).  Records of more than 2^22 bytes: UMICLUST_ERANGE. */
 int32_t umiclust_fastq_ee(umiclust_ctx *ctx, const uint8_t *quals, const int64_t *offsets, int64_t n,
                           int32_t fastq_ascii, int64_t *ee_fx, uint8_t *qlo, uint8_t *qhi);
+/* The statistics kernel alone (row f5b: what the tables of preprocessing.py:126-127,156-157, read by
+ * analysis.py:76-81, are summed from): record i's sequence is seqs[offsets[i] .. offsets[i+1]) and its quality the
+ * same range of quals.  ee_fx, qlo, qhi as umiclust_fastq_ee's; counts[5 i ..] = the record's quality bytes with
+ * b - fastq_ascii >= 20, those with b - fastq_ascii >= 30, its sequence bytes in "GCgc", in "Nn" and in "-. ".
+ * Records of more than 2^22 bytes: UMICLUST_ERANGE. */
+int32_t umiclust_fastq_record_stats(umiclust_ctx *ctx, const uint8_t *seqs, const uint8_t *quals,
+                                    const int64_t *offsets, int64_t n, int32_t fastq_ascii, int64_t *ee_fx,
+                                    uint8_t *qlo, uint8_t *qhi, uint32_t *counts);
 /* Align npairs (query, target) pairs with the production alignment kernel.  Sequences are
  * ASCII; q/t record k at [q_off[k], q_off[k+1]).  Outputs per pair: score, matches,
  * internal alignment length (columns minus the terminal gap runs, vsearch align_trim) and,

@@ -72,14 +72,17 @@ struct ExtractState {
 };
 
 // quality filtering (f5): two pinned staging slots (one being gathered while the other is on the device), one set
-// of device buffers, kept across calls
+// of device buffers, kept across calls.  seq / cnt and dseq / dcnt (the sequence bytes and the five counts per record
+// of row f5b) are allocated by the first call that asks for the statistics tables.
 struct FqState {
   struct Slot {
-    PinBuf<uint8_t> q, lo, hi;
+    PinBuf<uint8_t> q, lo, hi, seq;
     PinBuf<int64_t> offs, ee;
+    PinBuf<uint32_t> cnt;
   } slot[2];
-  DevBuf<uint8_t> dq, dlo, dhi;
+  DevBuf<uint8_t> dq, dlo, dhi, dseq;
   DevBuf<int64_t> doffs, dee;
+  DevBuf<uint32_t> dcnt;
   DevBuf<uint64_t> dtab;
   hipEvent_t ev[3] = {};  // copy begin, kernel begin, kernel end
   ~FqState() {

@@ -258,14 +258,59 @@ int index_window(const char* d, int64_t size, int64_t pos, int64_t want_end, int
 }
 
 // ------------------------------------------------------------------ the host backend
-bool HostBackend::reserve(int slot, size_t qual_bytes, size_t nrec, Slot& s, std::string&) {
+bool HostBackend::reserve(int slot, size_t qual_bytes, size_t nrec, bool stats, Slot& s, std::string&) {
   q[slot].assign(qual_bytes + 2 * kPad, 0);
   offs[slot].assign(nrec + 1, 0);
   ee[slot].assign(nrec + 1, 0);
   lo[slot].assign(nrec + 1, 0);
   hi[slot].assign(nrec + 1, 0);
   slots[slot] = Slot{q[slot].data(), offs[slot].data(), ee[slot].data(), lo[slot].data(), hi[slot].data()};
+  if (stats) {
+    sq[slot].assign(qual_bytes + 2 * kPad, 0);
+    cnt[slot].assign(kCounts * (nrec + 1), 0);
+    slots[slot].seq = sq[slot].data();
+    slots[slot].cnt = cnt[slot].data();
+  }
   s = slots[slot];
+  return true;
+}
+
+void record_stats(const uint8_t* seq, const uint8_t* qual, int64_t len, const uint64_t* table, int ascii,
+                  unsigned __int128* ee, uint8_t* qlo, uint8_t* qhi, uint64_t cnt[kCounts]) {
+  unsigned __int128 acc = 0;
+  uint8_t mn = 255, mx = 0;
+  uint64_t c[kCounts] = {0, 0, 0, 0, 0};
+  for (int64_t k = 0; k < len; k++) {
+    const uint8_t b = qual[k];
+    acc += table[b];
+    mn = std::min(mn, b);
+    mx = std::max(mx, b);
+    c[0] += (int)b - ascii >= 20;
+    c[1] += (int)b - ascii >= 30;
+    const uint8_t x = seq[k];
+    c[2] += x == 'G' || x == 'C' || x == 'g' || x == 'c';
+    c[3] += x == 'N' || x == 'n';
+    c[4] += x == '-' || x == '.' || x == ' ';
+  }
+  *ee = acc;
+  *qlo = mn;
+  *qhi = mx;
+  for (int j = 0; j < kCounts; j++) cnt[j] = c[j];
+}
+
+bool HostBackend::run_stats(int slot, size_t, int64_t nrec, const uint64_t* table, int ascii, double* t_h2d_s,
+                            double* t_kernel_s, std::string&) {
+  const Slot& s = slots[slot];
+  for (int64_t i = 0; i < nrec; i++) {
+    unsigned __int128 acc;
+    uint64_t c[kCounts];
+    record_stats(s.seq + kPad + s.offs[i], s.qual + kPad + s.offs[i], s.offs[i + 1] - s.offs[i], table, ascii, &acc,
+                 &s.qlo[i], &s.qhi[i], c);
+    s.ee[i] = (int64_t)acc;
+    for (int j = 0; j < kCounts; j++) s.cnt[kCounts * i + j] = (uint32_t)c[j];
+  }
+  *t_h2d_s = 0.0;
+  *t_kernel_s = 0.0;
   return true;
 }
 
@@ -332,6 +377,180 @@ int decide_fx(const umiclust_fastq_filter_params& p, int64_t len, int64_t ee_fx,
   return 0;
 }
 
+// ------------------------------------------------------------------ the statistics tables (row f5b, policy O8)
+int seq_type(const uint8_t* seq, int64_t len) {
+  bool dna = true, has_u = false, has_t = false;
+  for (int64_t i = 0; i < len; i++) {
+    const int c = seq[i] & ~0x20;  // upper case of a letter
+    if (c < 'A' || c > 'Z') continue;
+    has_u |= c == 'U';
+    has_t |= c == 'T';
+    dna &= strchr("ACGTRYSWKMBDHVN", c) != nullptr;
+  }
+  return dna ? 0 : (has_u && !has_t) ? 1 : 2;
+}
+
+void StatAcc::add(const uint8_t* seq, int64_t len, unsigned __int128 ee_fx, const uint64_t c[kCounts]) {
+  if (num_seqs == 0) type = seq_type(seq, len);
+  num_seqs++;
+  sum_len += len;
+  ee += ee_fx;
+  for (int j = 0; j < kCounts; j++) cnt[j] += c[j];
+  if (len <= kDevMaxLen) {
+    if ((int64_t)hist.size() <= len)
+      hist.resize((size_t)std::min<int64_t>(kDevMaxLen + 1, std::max<int64_t>(len + 1, 2 * (int64_t)hist.size())), 0);
+    hist[(size_t)len]++;
+  } else {
+    longer[len]++;
+  }
+}
+
+namespace {
+
+// the distinct lengths of a histogram in ascending order with their counts
+template <typename F>
+void walk_up(const StatAcc& a, F f) {
+  for (size_t l = 0; l < a.hist.size(); l++)
+    if (a.hist[l]) f((int64_t)l, a.hist[l]);
+  for (const auto& kv : a.longer) f(kv.first, kv.second);
+}
+
+// an integer with thousands commas
+std::string commas(uint64_t v) {
+  std::string d = std::to_string(v), out;
+  for (size_t i = 0; i < d.size(); i++) {
+    if (i && (d.size() - i) % 3 == 0) out += ',';
+    out += d[i];
+  }
+  return out;
+}
+
+// %.<prec>f of a non-negative number, the integer part with thousands commas
+std::string fixed(double v, int prec, bool with_commas) {
+  char buf[400];
+  snprintf(buf, sizeof(buf), "%.*f", prec, v);
+  std::string s = buf;
+  if (!with_commas) return s;
+  const size_t dot = s.find('.');
+  const size_t first = s[0] == '-' ? 1 : 0;
+  std::string ip = s.substr(first, dot - first), out = s.substr(0, first);
+  for (size_t i = 0; i < ip.size(); i++) {
+    if (i && (ip.size() - i) % 3 == 0) out += ',';
+    out += ip[i];
+  }
+  return out + s.substr(dot);
+}
+
+}  // namespace
+
+void finish_stats(const StatAcc& a, umiclust_fastq_stats* o) {
+  memset(o, 0, sizeof(*o));
+  o->type = a.type;
+  const int64_t n = a.num_seqs;
+  if (n == 0) return;  // O8c: every number is 0
+  o->num_seqs = n;
+  o->sum_len = a.sum_len;
+  o->n_q20 = (int64_t)a.cnt[0];
+  o->n_q30 = (int64_t)a.cnt[1];
+  o->n_gc = (int64_t)a.cnt[2];
+  o->sum_n = (int64_t)a.cnt[3];
+  o->sum_gap = (int64_t)a.cnt[4];
+  o->ee_fx_lo = (uint64_t)a.ee;
+  o->ee_fx_hi = (uint64_t)(a.ee >> 64);
+  // O8c: the order statistics the three quartiles need (0-based ranks in the ascending lengths), from one walk.
+  // The lower half is the first h lengths, the upper half the last h: the middle one of an odd n is in neither.
+  const int64_t h = n / 2;
+  int64_t want[6] = {(n - 1) / 2, n / 2, 0, 0, 0, 0}, got[6] = {0, 0, 0, 0, 0, 0};
+  if (h > 0) {
+    want[2] = (h - 1) / 2;
+    want[3] = h / 2;
+    want[4] = n - h + (h - 1) / 2;
+    want[5] = n - h + h / 2;
+  }  // n = 1: all three are the one length
+  int64_t seen = 0, mn = -1, mx = 0;
+  walk_up(a, [&](int64_t len, int64_t count) {
+    if (mn < 0) mn = len;
+    mx = len;
+    for (int k = 0; k < 6; k++)
+      if (want[k] >= seen && want[k] < seen + count) got[k] = len;
+    seen += count;
+  });
+  o->min_len = mn;
+  o->max_len = mx;
+  o->avg_len = (double)a.sum_len / (double)n;
+  o->q2 = (double)(got[0] + got[1]) / 2.0;
+  o->q1 = (double)(got[2] + got[3]) / 2.0;
+  o->q3 = (double)(got[4] + got[5]) / 2.0;
+  // N50: down the lengths, the first record at which twice the cumulative sum reaches sum_len; within a run of
+  // `count` records of one length that is the j-th of them, j = ceil((sum_len - 2 cum) / (2 len))
+  {
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    walk_up(a, [&](int64_t len, int64_t count) { runs.emplace_back(len, count); });
+    int64_t cum = 0, num = 0;
+    for (size_t i = runs.size(); i-- > 0;) {
+      const int64_t len = runs[i].first, count = runs[i].second;
+      if (2 * (cum + len * count) >= a.sum_len) {
+        const int64_t need = a.sum_len - 2 * cum;  // > 0 unless sum_len is 0
+        const int64_t j = len > 0 ? std::max<int64_t>(1, (need + 2 * len - 1) / (2 * len)) : 1;
+        o->n50 = len;
+        o->n50_num = num + j;
+        break;
+      }
+      cum += len * count;
+      num += count;
+    }
+  }
+  if (a.sum_len > 0) {  // a file of empty records: the ratios are 0
+    const double s = (double)a.sum_len;
+    o->q20_pct = 100.0 * (double)a.cnt[0] / s;
+    o->q30_pct = 100.0 * (double)a.cnt[1] / s;
+    o->gc_pct = 100.0 * (double)a.cnt[2] / s;
+    if (a.ee > 0) o->avg_qual = 0.0 - 10.0 * log10(ldexp((double)a.ee, -kFxShift) / s);  // 0.0 - x: no "-0.00"
+  }
+}
+
+std::string format_stat_table(const char* path, const StatAcc& a) {
+  umiclust_fastq_stats t;
+  finish_stats(a, &t);
+  static const char* kNames[19] = {"file",    "format",  "type",   "num_seqs", "sum_len", "min_len", "avg_len",
+                                   "max_len", "Q1",      "Q2",     "Q3",       "sum_gap", "N50",     "N50_num",
+                                   "Q20(%)",  "Q30(%)",  "AvgQual", "GC(%)",   "sum_n"};
+  static const char* kTypes[3] = {"DNA", "RNA", "Protein"};
+  const std::string v[19] = {path ? path : "-",
+                             "FASTQ",
+                             kTypes[t.type],
+                             commas((uint64_t)t.num_seqs),
+                             commas((uint64_t)t.sum_len),
+                             commas((uint64_t)t.min_len),
+                             fixed(t.avg_len, 1, true),
+                             commas((uint64_t)t.max_len),
+                             fixed(t.q1, 1, true),
+                             fixed(t.q2, 1, true),
+                             fixed(t.q3, 1, true),
+                             commas((uint64_t)t.sum_gap),
+                             commas((uint64_t)t.n50),
+                             commas((uint64_t)t.n50_num),
+                             fixed(t.q20_pct, 2, false),
+                             fixed(t.q30_pct, 2, false),
+                             fixed(t.avg_qual, 2, false),
+                             fixed(t.gc_pct, 2, false),
+                             commas((uint64_t)t.sum_n)};
+  std::string head, data;
+  for (int k = 0; k < 19; k++) {
+    const size_t w = std::max(strlen(kNames[k]), v[k].size());
+    const std::string hp(w - strlen(kNames[k]), ' '), vp(w - v[k].size(), ' ');
+    if (k) head += "  ", data += "  ";
+    if (k < 3) {  // left-aligned
+      head += kNames[k] + hp;
+      data += v[k] + vp;
+    } else {
+      head += hp + kNames[k];
+      data += vp + v[k];
+    }
+  }
+  return head + "\n" + data + "\n";
+}
+
 // ------------------------------------------------------------------ the writers
 namespace {
 
@@ -387,11 +606,15 @@ struct Chunk {
 }  // namespace
 
 int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, int threads, int64_t chunk_bytes,
-                   Backend& be, umiclust_fastq_filter_result* res, std::string& err) {
+                   Backend& be, umiclust_fastq_filter_result* res, std::string& err, const StatsReq* stats) {
   const double t_begin = now_s();
   umiclust_fastq_filter_result R;
   memset(&R, 0, sizeof(R));
   if (res) *res = R;
+  const bool st = stats != nullptr;
+  StatAcc acc_in, acc_kept;  // every record read, every record kept
+  if (st && stats->before) memset(stats->before, 0, sizeof(*stats->before));
+  if (st && stats->after) memset(stats->after, 0, sizeof(*stats->after));
   if (!paths.in) return err = "null input path", UMICLUST_EINVAL;
   if ((p.fastq_ascii != 33 && p.fastq_ascii != 64) || p.fastq_qmin < 0 || p.fastq_qmax < p.fastq_qmin ||
       p.fastq_minlen < 0 || std::isnan(p.fastq_maxee) || std::isnan(p.fastq_maxee_rate))
@@ -467,7 +690,7 @@ int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, in
         int64_t total = 0;
         for (const Rec& r : c.recs) total += r.len <= kDevMaxLen ? r.len : 0;
         c.qual_bytes = total;
-        if (!be.reserve(s, (size_t)total, (size_t)n, c.slot, c.err)) {
+        if (!be.reserve(s, (size_t)total, (size_t)n, st, c.slot, c.err)) {
           c.rc = UMICLUST_ENOMEM;
           c.recs.clear();
         } else {
@@ -479,12 +702,18 @@ int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, in
           c.slot.offs[n] = at;
           memset(c.slot.qual, 0, (size_t)kPad);
           memset(c.slot.qual + kPad + total, 0, (size_t)kPad);
+          if (st) {
+            memset(c.slot.seq, 0, (size_t)kPad);
+            memset(c.slot.seq + kPad + total, 0, (size_t)kPad);
+          }
           const int T = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n / 64));
           parallel_for(T, [&](int t) {
             for (int64_t i = n * t / T; i < n * (t + 1) / T; i++) {
               const Rec& r = c.recs[i];
               if (r.len > kDevMaxLen) continue;
-              memcpy(c.slot.qual + kPad + c.slot.offs[i], (r.arena ? c.arena.data() : data) + r.qual, (size_t)r.len);
+              const char* from = r.arena ? c.arena.data() : data;
+              memcpy(c.slot.qual + kPad + c.slot.offs[i], from + r.qual, (size_t)r.len);
+              if (st) memcpy(c.slot.seq + kPad + c.slot.offs[i], from + r.seq, (size_t)r.len);
             }
           });
         }
@@ -526,7 +755,8 @@ int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, in
       }
       if (n > 0 || c.rc == UMICLUST_OK) R.n_chunks++;
       double t_h2d = 0.0, t_k = 0.0;
-      if (n > 0 && !be.run(s, (size_t)c.qual_bytes, n, tab.fx, &t_h2d, &t_k, err)) {
+      if (n > 0 && !(st ? be.run_stats(s, (size_t)c.qual_bytes, n, tab.fx, p.fastq_ascii, &t_h2d, &t_k, err)
+                        : be.run(s, (size_t)c.qual_bytes, n, tab.fx, &t_h2d, &t_k, err))) {
         rc = UMICLUST_EDEVICE;
         break;
       }
@@ -574,6 +804,19 @@ int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, in
             why = decide_exact(p, tab, q, r.len);
             R.n_host_rechecked++;
           }
+        }
+        if (st) {  // the record's integers: the device's, or for a host-only record the same restatement's
+          unsigned __int128 e128 = 0;
+          uint64_t cnt[kCounts];
+          if (host_only) {
+            uint8_t l8, h8;
+            record_stats((const uint8_t*)base + r.seq, q, r.len, tab.fx, p.fastq_ascii, &e128, &l8, &h8, cnt);
+          } else {
+            e128 = (unsigned __int128)(uint64_t)c.slot.ee[i];
+            for (int j = 0; j < kCounts; j++) cnt[j] = c.slot.cnt[kCounts * i + j];
+          }
+          acc_in.add((const uint8_t*)base + r.seq, r.len, e128, cnt);
+          if (why == 0) acc_kept.add((const uint8_t*)base + r.seq, r.len, e128, cnt);
         }
         R.n_input++;
         R.bases_in += r.len;
@@ -680,6 +923,25 @@ int64_t run_filter(const umiclust_fastq_filter_params& p, const Paths& paths, in
       ok = close(lf) == 0 && ok;
     }
     if (!ok) return err = std::string("cannot write ") + paths.log, UMICLUST_EIO;
+  }
+  if (st) {  // everything else succeeded: the two tables
+    const char* txt[2] = {stats->before_txt, stats->after_txt};
+    const char* file[2] = {paths.in, paths.out};
+    const StatAcc* acc[2] = {&acc_in, &acc_kept};
+    umiclust_fastq_stats* sout[2] = {stats->before, stats->after};
+    for (int k = 0; k < 2; k++) {
+      if (sout[k]) finish_stats(*acc[k], sout[k]);
+      if (!txt[k]) continue;
+      std::string table = format_stat_table(file[k], *acc[k]);
+      const int tf = open(txt[k], O_WRONLY | O_CREAT | O_TRUNC, 0666);
+      bool ok = tf >= 0;
+      if (ok) {
+        std::vector<iovec> v{{(void*)table.data(), table.size()}};
+        ok = writev_all(tf, v);
+        ok = close(tf) == 0 && ok;
+      }
+      if (!ok) return err = std::string("cannot write ") + txt[k], UMICLUST_EIO;
+    }
   }
   return R.n_kept;
 }

@@ -264,6 +264,12 @@ hipError_t launch_extract_win(const char* win, const uint8_t* wlen, int64_t n, i
 // (255 / 0 for an empty record).
 hipError_t launch_fastq_ee(const uint8_t* qual, const int64_t* offs, int64_t n, const uint64_t* table, int64_t* ee,
                            uint8_t* qlo, uint8_t* qhi, hipStream_t st);
+// The same with the counts of seqkit's `stat -a` table (row f5b): seq = the concatenated sequence bytes, laid out as
+// qual is (the same offs, the same padding).  ee / qlo / qhi as above; counts[5 i ..] = record i's quality bytes with
+// b - ascii >= 20, with b - ascii >= 30, its sequence bytes in "GCgc", in "Nn" and in "-. ".
+hipError_t launch_fastq_stats(const uint8_t* qual, const uint8_t* seq, const int64_t* offs, int64_t n,
+                              const uint64_t* table, int ascii, int64_t* ee, uint8_t* qlo, uint8_t* qhi,
+                              uint32_t* counts, hipStream_t st);
 
 // ---- region binning of BAM records (regionsplit.hip) ----
 enum : int8_t { kBamUnmapped = 0, kBamSecondary = 1, kBamShort = 2, kBamLong = 3, kBamKept = 4, kBamNoRegion = 5,

@@ -122,6 +122,20 @@ class FastqFilterResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FastqStats(C.Structure):
+    """umiclust_fastq_stats: the numbers of one `seqkit stat -a` table (policy O8)"""
+    _fields_ = [(k, C.c_int64) for k in ("num_seqs", "sum_len", "min_len", "max_len", "n50", "n50_num", "n_q20",
+                                         "n_q30", "n_gc", "sum_n", "sum_gap")] + \
+               [("ee_fx_lo", C.c_uint64), ("ee_fx_hi", C.c_uint64), ("type", C.c_int32), ("pad", C.c_int32)] + \
+               [(k, C.c_double) for k in ("avg_len", "q1", "q2", "q3", "q20_pct", "q30_pct", "avg_qual", "gc_pct")]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("pad", "ee_fx_lo", "ee_fx_hi", "type")}
+        d["ee_fx"] = (self.ee_fx_hi << 64) | self.ee_fx_lo
+        d["type"] = ("DNA", "RNA", "Protein")[self.type]
+        return d
+
+
 # every symbol include/umiclust.h declares
 EXPORTS = [
     "umiclust_abi_version", "umiclust_params_init", "umiclust_params_from_argv", "umiclust_create",
@@ -130,7 +144,8 @@ EXPORTS = [
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
-    "umiclust_fastq_filter_argv", "umiclust_fastq_ee", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
+    "umiclust_fastq_filter_argv", "umiclust_fastq_filter_stats", "umiclust_fastq_filter_stats_argv",
+    "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close",
@@ -245,6 +260,16 @@ def lib() -> C.CDLL:
     L.umiclust_fastq_ee.restype = C.c_int32
     L.umiclust_fastq_ee.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int64, C.c_int32, P(C.c_int64),
                                     P(C.c_uint8), P(C.c_uint8)]
+    L.umiclust_fastq_filter_stats.restype = C.c_int64
+    L.umiclust_fastq_filter_stats.argtypes = [C.c_void_p, P(FastqFilterParams), C.c_char_p, C.c_char_p, C.c_char_p,
+                                              C.c_char_p, C.c_char_p, C.c_char_p, P(FastqFilterResult), P(FastqStats),
+                                              P(FastqStats)]
+    L.umiclust_fastq_filter_stats_argv.restype = C.c_int64
+    L.umiclust_fastq_filter_stats_argv.argtypes = [C.c_void_p, C.c_int32, P(C.c_char_p), C.c_char_p, C.c_char_p,
+                                                   P(FastqFilterResult), P(FastqStats), P(FastqStats)]
+    L.umiclust_fastq_record_stats.restype = C.c_int32
+    L.umiclust_fastq_record_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int64, C.c_int32,
+                                              P(C.c_int64), P(C.c_uint8), P(C.c_uint8), P(C.c_uint32)]
     L.umiclust_prefilter.restype = C.c_int32
     L.umiclust_prefilter.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
@@ -548,6 +573,51 @@ class Context:
         k = lib().umiclust_fastq_filter_argv(self._h, len(argv), arr, C.byref(r))
         self._check(k, "fastq_filter_argv")
         return r.as_dict()
+
+    def fastq_filter_stats(self, p: FastqFilterParams, in_fastq: str, fastqout: str | None = None,
+                           fastqout_discarded: str | None = None, log: str | None = None,
+                           stats_before_txt: str | None = None, stats_after_txt: str | None = None) -> dict:
+        """umiclust_fastq_filter_stats: the filter and, from the same pass, the two `seqkit stat -a` tables of the
+        records read and of the records kept (policy O8).  Returns the result counters and phase times plus
+        "before" / "after", the tables' numbers.  Without any filter output it is a statistics-only pass."""
+        r, b, a = FastqFilterResult(), FastqStats(), FastqStats()
+        enc = lambda x: os.fspath(x).encode() if x else None  # noqa: E731
+        k = lib().umiclust_fastq_filter_stats(self._h, C.byref(p), enc(in_fastq), enc(fastqout),
+                                              enc(fastqout_discarded), enc(log), enc(stats_before_txt),
+                                              enc(stats_after_txt), C.byref(r), C.byref(b), C.byref(a))
+        self._check(k, "fastq_filter_stats")
+        return dict(r.as_dict(), before=b.as_dict(), after=a.as_dict())
+
+    def fastq_filter_stats_argv(self, argv: list[str], stats_before_txt: str | None = None,
+                                stats_after_txt: str | None = None) -> dict:
+        """The same from the argv the reference builds (preprocessing.py:129-148)."""
+        r, b, a = FastqFilterResult(), FastqStats(), FastqStats()
+        enc = lambda x: os.fspath(x).encode() if x else None  # noqa: E731
+        arr = (C.c_char_p * len(argv))(*[str(x).encode() for x in argv])
+        k = lib().umiclust_fastq_filter_stats_argv(self._h, len(argv), arr, enc(stats_before_txt),
+                                                   enc(stats_after_txt), C.byref(r), C.byref(b), C.byref(a))
+        self._check(k, "fastq_filter_stats_argv")
+        return dict(r.as_dict(), before=b.as_dict(), after=a.as_dict())
+
+    def fastq_record_stats(self, seqs, quals, fastq_ascii: int = 33):
+        """umiclust_fastq_record_stats: per record (`seqs[i]` and `quals[i]` are bytes objects of one length) the
+        fixed-point expected error, the smallest / largest quality byte, and counts[i] = (n_q20, n_q30, n_gc, n_n,
+        n_gap) as a uint32 array of shape (n, 5)."""
+        if [len(x) for x in seqs] != [len(x) for x in quals]:
+            raise ValueError("a record's sequence and quality differ in length")
+        sbuf, off = _pack(seqs)
+        qbuf, _ = _pack(quals)
+        n = len(off) - 1
+        ee = np.zeros(max(n, 1), np.int64)
+        lo = np.zeros(max(n, 1), np.uint8)
+        hi = np.zeros(max(n, 1), np.uint8)
+        cnt = np.zeros((max(n, 1), 5), np.uint32)
+        P = C.POINTER
+        self._check(lib().umiclust_fastq_record_stats(self._h, sbuf.ctypes.data, qbuf.ctypes.data, _i64(off), n,
+                                                      fastq_ascii, _i64(ee), lo.ctypes.data_as(P(C.c_uint8)),
+                                                      hi.ctypes.data_as(P(C.c_uint8)),
+                                                      cnt.ctypes.data_as(P(C.c_uint32))), "fastq_record_stats")
+        return ee[:n], lo[:n], hi[:n], cnt[:n]
 
     def fastq_ee(self, quals, fastq_ascii: int = 33) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """umiclust_fastq_ee: per record of `quals` (bytes objects) the fixed-point expected error (int64, 2^-40

@@ -1,11 +1,17 @@
 // fastq_check_main.cpp -- drives the HIP-free side of the fastq_filter drop-in (ont-tcrconsensus_amd/csrc/
 // fastq_filter.cpp) under ASan + UBSan, without a GPU (make fastq_check; tests/test_fastq_filter_cpu.py).  The device
-// is replaced by fq::HostBackend, the host restatement of the kernel: per record the sum of the fixed-point table and
-// the smallest / largest byte.
+// is replaced by fq::HostBackend, the host restatement of the kernels: per record the sum of the fixed-point table and
+// the smallest / largest byte, and in stats mode the five counts of the statistics tables.
 //
 //   fastq_check filter <in> <out|-> <discarded|-> <log|-> <threads> <chunk> <ascii> <qmin> <qmax> <minlen> <maxlen>
 //                      <maxee> <maxee_rate>
 //       runs the whole step; prints `rc=<n_kept or error code>`, one `name=value` line per result counter and `err=<message>`
+//   fastq_check stats <in> <out|-> <discarded|-> <log|-> <before_txt|-> <after_txt|-> <threads> <chunk> <ascii> <qmin>
+//                     <qmax> <minlen> <maxlen> <maxee> <maxee_rate>
+//       the same step in stats mode (row f5b): the gathered sequence bytes, the host restatement of k_fastq_stats,
+//       the two accumulators, the histogram walk and the formatter; writes the two `seqkit stat -a` tables and prints,
+//       after the lines above, `before.<name>=<value>` and `after.<name>=<value>` for every integer of the two
+//       umiclust_fastq_stats and the doubles in hexadecimal
 //   fastq_check seams <in>
 //       indexes the file in windows of every length from 1 byte to the whole file, on 1, 2, 3 and 7 threads (so a
 //       slice boundary falls on every byte), and compares each pass with the one-window, one-thread index; prints
@@ -90,13 +96,28 @@ int seams(const char* path) {
   return 0;
 }
 
+void print_stats(const char* which, const umiclust_fastq_stats& t) {
+  const long long v[11] = {t.num_seqs, t.sum_len, t.min_len, t.max_len, t.n50,    t.n50_num,
+                           t.n_q20,    t.n_q30,   t.n_gc,    t.sum_n,   t.sum_gap};
+  static const char* names[11] = {"num_seqs", "sum_len", "min_len", "max_len", "n50",    "n50_num",
+                                  "n_q20",    "n_q30",   "n_gc",    "sum_n",   "sum_gap"};
+  for (int k = 0; k < 11; k++) printf("%s.%s=%lld\n", which, names[k], v[k]);
+  printf("%s.ee_fx_lo=%llu\n%s.ee_fx_hi=%llu\n%s.type=%d\n", which, (unsigned long long)t.ee_fx_lo, which,
+         (unsigned long long)t.ee_fx_hi, which, t.type);
+  printf("%s.avg_len=%a\n%s.q1=%a\n%s.q2=%a\n%s.q3=%a\n", which, t.avg_len, which, t.q1, which, t.q2, which, t.q3);
+  printf("%s.q20_pct=%a\n%s.q30_pct=%a\n%s.avg_qual=%a\n%s.gc_pct=%a\n", which, t.q20_pct, which, t.q30_pct, which,
+         t.avg_qual, which, t.gc_pct);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc == 3 && strcmp(argv[1], "seams") == 0) return seams(argv[2]);
-  if (argc != 15 || strcmp(argv[1], "filter") != 0) {
+  const bool stats = argc == 17 && strcmp(argv[1], "stats") == 0;
+  if (!stats && (argc != 15 || strcmp(argv[1], "filter") != 0)) {
     fprintf(stderr, "usage: fastq_check filter <in> <out|-> <discarded|-> <log|-> <threads> <chunk> <ascii> <qmin> "
-                    "<qmax> <minlen> <maxlen> <maxee> <maxee_rate> | fastq_check seams <in>\n");
+                    "<qmax> <minlen> <maxlen> <maxee> <maxee_rate> | fastq_check stats <in> <out|-> <discarded|-> "
+                    "<log|-> <before_txt|-> <after_txt|-> <threads> ... <maxee_rate> | fastq_check seams <in>\n");
     return 1;
   }
   fq::Paths paths;
@@ -104,6 +125,15 @@ int main(int argc, char** argv) {
   paths.out = opt_path(argv[3]);
   paths.discarded = opt_path(argv[4]);
   paths.log = opt_path(argv[5]);
+  umiclust_fastq_stats before, after;
+  fq::StatsReq req;
+  if (stats) {
+    req.before_txt = opt_path(argv[6]);
+    req.after_txt = opt_path(argv[7]);
+    req.before = &before;
+    req.after = &after;
+    argv += 2;  // the filter's own arguments follow
+  }
   const int threads = atoi(argv[6]);
   const int64_t chunk = atoll(argv[7]);
   umiclust_fastq_filter_params p;
@@ -118,7 +148,7 @@ int main(int argc, char** argv) {
   fq::HostBackend be;
   umiclust_fastq_filter_result r;
   std::string err;
-  const int64_t rc = fq::run_filter(p, paths, threads, chunk, be, &r, err);
+  const int64_t rc = fq::run_filter(p, paths, threads, chunk, be, &r, err, stats ? &req : nullptr);
   printf("rc=%lld\n", (long long)rc);
   printf("n_input=%lld\nn_kept=%lld\nn_discarded=%lld\nbases_in=%lld\nbases_kept=%lld\n", (long long)r.n_input,
          (long long)r.n_kept, (long long)r.n_discarded, (long long)r.bases_in, (long long)r.bases_kept);
@@ -127,5 +157,9 @@ int main(int argc, char** argv) {
          (long long)r.n_host_rechecked, (long long)r.n_chunks);
   printf("ee_in=%a\nee_kept=%a\n", r.ee_in, r.ee_kept);
   printf("err=%s\n", err.c_str());
+  if (stats) {
+    print_stats("before", before);
+    print_stats("after", after);
+  }
   return 0;
 }

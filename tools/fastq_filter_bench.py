@@ -9,7 +9,13 @@ the wall time, input GB/s and the result struct (counters and phase times), and 
 time stayed below the summed host-to-device copy time of the same chunks.  If a `vsearch` binary is on PATH the same
 argv is timed with it once; otherwise the JSON says it is absent.  Needs a GPU: there is no CPU fallback.
 
-    python tools/fastq_filter_bench.py [--gb 2.0] [--runs 3] [--out FILE]
+With --stats (row f5b) the same process then runs the same argv on the same file through
+umiclust_fastq_filter_stats_argv, which also writes the two `seqkit stat -a` tables: the JSON (default
+profiles/fastq_filter/bench_stats.json) holds the plain runs as above and, under "stats", the runs with the tables,
+their phase sums, the added host-to-device time, and whether k_fastq_stats's summed HIP-event time stayed below the
+summed host-to-device copy time of the same chunks.  seqkit, like vsearch, is only timed if a binary is on PATH.
+
+    python tools/fastq_filter_bench.py [--gb 2.0] [--runs 3] [--stats] [--out FILE]
 """
 import argparse
 import json
@@ -57,9 +63,12 @@ def main():
     ap.add_argument("--len", type=int, default=1500)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--dir", default="/dev/shm")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fastq_filter", "bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--stats", action="store_true", help="also time the pass that writes the seqkit tables")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fastq_filter", "bench_stats.json" if args.stats else "bench.json")
     work = os.path.join(args.dir, f"umiclust_fq_bench_{os.getpid()}")
     os.makedirs(work, exist_ok=True)
     try:
@@ -80,12 +89,44 @@ def main():
                       f"{r['t_kernel_s'] * 1e3:.2f} ms, h2d {r['t_h2d_s'] * 1e3:.2f} ms", flush=True)
                 if i > 0:
                     out["runs"].append(dict(wall_s=dt, input_gb_per_s=size / dt / 1e9, result=r))
+            if args.stats:
+                txt = [os.path.join(work, "stats_before.txt"), os.path.join(work, "stats_after.txt")]
+                st = out["stats"] = dict(runs=[])
+                for i in range(args.runs + 1):
+                    t0 = time.perf_counter()
+                    r = ctx.fastq_filter_stats_argv(argv, *txt)
+                    dt = time.perf_counter() - t0
+                    print(f"stats run {i}{' (warm-up)' if i == 0 else ''}: {dt:.3f} s, {size / dt / 1e9:.2f} GB/s, "
+                          f"kernel {r['t_kernel_s'] * 1e3:.2f} ms, h2d {r['t_h2d_s'] * 1e3:.2f} ms", flush=True)
+                    if i > 0:
+                        r["before"]["ee_fx"] = str(r["before"]["ee_fx"])  # beyond a JSON reader's integers
+                        r["after"]["ee_fx"] = str(r["after"]["ee_fx"])
+                        st["runs"].append(dict(wall_s=dt, input_gb_per_s=size / dt / 1e9, result=r))
+                st["tables"] = [open(t).read() for t in txt]
         out["input_gb_per_s_median"] = float(np.median([x["input_gb_per_s"] for x in out["runs"]]))
         k = sum(x["result"]["t_kernel_s"] for x in out["runs"])
         h = sum(x["result"]["t_h2d_s"] for x in out["runs"])
         out.update(kernel_s_sum=k, h2d_s_sum=h, kernel_below_h2d=bool(k < h),
                    kernel_qual_gb_per_s=sum(x["result"]["bases_in"] for x in out["runs"]) / k / 1e9,
                    h2d_gb_per_s=sum(x["result"]["bases_in"] for x in out["runs"]) / h / 1e9)
+        if args.stats:
+            st = out["stats"]
+            sk = sum(x["result"]["t_kernel_s"] for x in st["runs"])
+            sh = sum(x["result"]["t_h2d_s"] for x in st["runs"])
+            phases = ("t_read_s", "t_h2d_s", "t_kernel_s", "t_write_s")
+            st.update(input_gb_per_s_median=float(np.median([x["input_gb_per_s"] for x in st["runs"]])),
+                      wall_s_median=float(np.median([x["wall_s"] for x in st["runs"]])),
+                      kernel_s_sum=sk, h2d_s_sum=sh, kernel_below_h2d=bool(sk < sh), h2d_s_added=sh - h,
+                      phase_s_per_run={k: sum(x["result"][k] for x in st["runs"]) / len(st["runs"]) for k in phases})
+            out["wall_s_median"] = float(np.median([x["wall_s"] for x in out["runs"]]))
+            out["phase_s_per_run"] = {k: sum(x["result"][k] for x in out["runs"]) / len(out["runs"]) for k in phases}
+            out["seqkit"] = shutil.which("seqkit")
+            if out["seqkit"]:
+                t0 = time.perf_counter()
+                rc = subprocess.run([out["seqkit"], "stat", "-a", src], stdout=subprocess.DEVNULL).returncode
+                out["seqkit_run"] = dict(returncode=rc, wall_s=time.perf_counter() - t0)
+            else:
+                print("no seqkit binary on PATH: the reference's two passes are not measured")
         vs = shutil.which("vsearch")
         out["vsearch"] = vs
         if vs:
@@ -100,7 +141,10 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
             json.dump(out, fh, indent=1)
-        print(json.dumps({k: v for k, v in out.items() if k != "runs"}))
+        brief = {k: v for k, v in out.items() if k != "runs"}
+        if args.stats:
+            brief["stats"] = {k: v for k, v in out["stats"].items() if k != "runs"}
+        print(json.dumps(brief))
     finally:
         shutil.rmtree(work, ignore_errors=True)
 
