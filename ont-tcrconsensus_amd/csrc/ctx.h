@@ -1,12 +1,13 @@
 // ctx.h -- the context core: what every entry point of the C ABI (include/umiclust.h) needs of a context, and the
-// state of the drop-ins (dropin_*.cpp), which share nothing else with clustering.  driver.cpp derives umiclust_ctx from
-// uc::Ctx; the drop-ins see umiclust_ctx only as the ABI's incomplete type and reach this base through uc::core.
+// state of the drop-ins (dropin_*.cpp), which share nothing else with clustering.  cluster_ctx.h derives umiclust_ctx
+// from uc::Ctx; the drop-ins see umiclust_ctx only as the ABI's incomplete type and reach this base through uc::core.
 #pragma once
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/umiclust.h"
@@ -57,6 +58,45 @@ void alloc_each(C* c, size_t count, B&... b) {
   (c->hip(b.ensure(count), "alloc"), ...);
 }
 
+// An owned HIP event (Event) or stream (Stream): move-only, destroyed with its owner, read as the raw handle.
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  operator hipEvent_t() const { return e; }
+  // creates the event unless it exists
+  hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+  // the handle, created on first use (a failure is the context's)
+  template <typename C>
+  hipEvent_t get(C* c, unsigned flags = hipEventDefault) {
+    c->hip(create(flags), "event");
+    return e;
+  }
+};
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+  // (a replaced stream -- umiclust_set_priority -- leaves in `o` and is destroyed with it)
+  Stream& operator=(Stream&& o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+  hipError_t create(unsigned flags) { return hipStreamCreateWithFlags(&s, flags); }
+  hipError_t create(unsigned flags, int priority) { return hipStreamCreateWithPriority(&s, flags, priority); }
+};
+
 struct Fail {
   int code;
 };
@@ -84,11 +124,7 @@ struct FqState {
   DevBuf<int64_t> doffs, dee;
   DevBuf<uint32_t> dcnt;
   DevBuf<uint64_t> dtab;
-  hipEvent_t ev[3] = {};  // copy begin, kernel begin, kernel end
-  ~FqState() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  Event ev[3];  // copy begin, kernel begin, kernel end
 };
 
 // BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
@@ -108,20 +144,15 @@ struct BamSession {
 
 struct Ctx {
   int dev = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Stream st;
+  Event ev0, ev1;
   std::string err;
   Tunables tun;  // the UMICLUST_* switches, as umiclust_create read them (tunables.h)
   umiclust_stats stats{};
   ExtractState ex;
   FqState fq;
   BamSession bs;
-  // runs after the derived context's destructor (which selects the device) and before the members above are freed
-  ~Ctx() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  // (the members go after the derived context's destructor, which selects the device)
 
   void fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -139,6 +170,13 @@ struct Ctx {
 
 // the core of a context (driver.cpp: the upcast); null for null
 Ctx* core(umiclust_ctx* c);
+
+// seconds between two recorded events that have completed
+inline double elapsed_s(Ctx* c, hipEvent_t a, hipEvent_t b) {
+  float ms = 0;
+  c->hip(hipEventElapsedTime(&ms, a, b), "elapsed");
+  return ms * 1e-3;
+}
 
 // A packed sequence set on the device: the bytes of records [0, n) into d_seq and their offsets, relative to offs[0],
 // into d_off, both copies queued on st.  `rel` is what the offset copy reads: it must live until st has run it.

@@ -48,8 +48,7 @@ struct FqDevice : fq::Backend {
     const size_t n = (size_t)nrec;
     hipError_t e = hipSuccess;
     auto ok = [&](hipError_t x) { return e == hipSuccess && (e = x) == hipSuccess; };
-    for (hipEvent_t& ev : c->fq.ev)
-      if (!ev) ok(hipEventCreate(&ev));
+    for (uc::Event& ev : c->fq.ev) ok(ev.create());
     if (e == hipSuccess && !(grow(c->fq.dq, qual_bytes + 2 * fq::kPad) && grow(c->fq.doffs, n + 1) &&
                              grow(c->fq.dee, n + 1) && grow(c->fq.dlo, n + 1) && grow(c->fq.dhi, n + 1) &&
                              grow(c->fq.dtab, 256) &&

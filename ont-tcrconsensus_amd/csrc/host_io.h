@@ -1,6 +1,6 @@
 // host_io.h -- the HIP-free host side of the drop-in boundary: FASTA/FASTQ input, the vsearch output
 // writers (--consout, --clusters), the in-process parse_umi_clusters, the vsearch argv
-// grammar, BGZF inflation (f4) and the detected-UMI writer (f1).  Compiled by g++ (no HIP), so the CPU
+// grammar, BGZF inflation (f4), the detected-UMI writer (f1) and prepare's length sort.  Compiled by g++ (no HIP), so the CPU
 // suite builds it with ASan/UBSan (tests/test_sanitizers_cpu.py, tools/host_asan_main.cpp).  Not part of the
 // C ABI except umiclust_params_init / umiclust_params_from_argv, which it defines.
 #pragma once
@@ -17,7 +17,7 @@
 namespace uc {
 namespace io {
 
-// A failure of an I/O-side step: an UMICLUST_E* code and a message (driver.cpp turns it into the context's
+// A failure of an I/O-side step: an UMICLUST_E* code and a message (UC_GUARD turns it into the context's
 // error; nothing is thrown across the C ABI).
 struct IoError {
   int code;
@@ -130,6 +130,18 @@ void parse_clusters(const Fasta& f, const ClusterView& cv, const umiclust_parse_
 // write_fasta of extract_umis (/root/reference/ont_tcr_consensus/extract_umis.py:154-186) for records [0, ngood):
 // res[i*6 ..] = (dist, start, end) of the 5' and 3' UMI in their windows; returns the reads with both UMIs
 int64_t write_detected_umis(const char* path, const Fasta& f, const int32_t* res, int64_t ngood, int32_t a3);
+
+// vsearch's length filter and db_sortbylength over the records of a load (umiclust_prepare): within every bin
+// [bin_in[b], bin_in[b + 1]) the records of minlen <= length <= min(maxseq, kMaxLen), longest first, ties in input
+// order (O1), the bins laid out one after another.  perm (sorted -> input index) and hlen (sorted lengths) have room
+// for every record; bin_s[0 .. nbins] are the bins' first sorted positions.  A bin of >= 256k records is sorted on T
+// threads.  `bad` is the first input record the load cannot take -- longer than kMaxLen inside the caller's window,
+// or kept and shorter than kMinTplLen -- in the first bin that holds one (the sort stops there), or -1.
+struct LenSort {
+  int64_t kept, bad;
+};
+LenSort sort_by_length(const uint32_t* rec_len, const int64_t* bin_in, int32_t nbins, int64_t minlen, int64_t maxseq,
+                       int T, int32_t* perm, uint8_t* hlen, int32_t* bin_s);
 
 // BGZF (SAM/BAM specification §4.1) inflated on the host threads
 bool inflate_bgzf(const char* path, std::vector<uint8_t>& raw);

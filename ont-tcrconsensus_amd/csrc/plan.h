@@ -1,7 +1,7 @@
 // plan.h -- the integer policy of one clustering call, host-only C++ (no HIP): how a bin's sorted queries are cut
 // into greedy blocks and re-cut after peer overflows and clean stretches (BlockPlan), and how the finished clusters
 // are numbered for the output (number_clusters), and which member traceback goes to which launch and slot
-// (plan_traceback).  driver.cpp's cluster_all drives them (umiclust_consensus the last); tools/plan_check_main.cpp
+// (plan_traceback).  driver.cpp's cluster_all drives them through ClusterRun (umiclust_consensus the last); tools/plan_check_main.cpp
 // (tests/test_plan_cpu.py) exercises them under ASan + UBSan without a GPU.
 #pragma once
 #include <cstdint>

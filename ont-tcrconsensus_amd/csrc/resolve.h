@@ -1,7 +1,7 @@
 // resolve.h -- the host's in-order resolution of one greedy block (vsearch's sequential assignment,
 // cluster.cc cluster_core_serial / cluster_core_parallel, behind vsearch_umi_cluster.py:21-54), host-only C++:
 // no HIP, so the ThreadSanitizer harness (tools/resolve_tsan_main.cpp, tests/test_sanitizers_cpu.py) builds it
-// with g++ and replays recorded passes through it.  driver.cpp's resolve_pass waits for a pass on the device and
+// with g++ and replays recorded passes through it.  pass.cpp's resolve_pass waits for a pass on the device and
 // calls resolve_block with the pass's per-query-strand outcomes (HostQs) and records; round B (alignments the
 // device did not compute) is a callback.
 #pragma once

@@ -1,5 +1,6 @@
-// Internal declarations shared by the HIP kernels (kernels.hip) and the host side (driver.cpp,
-// dropin_*.cpp through ctx.h).  Not part of the C ABI (see include/umiclust.h).
+// Internal declarations shared by the HIP kernels (kernels.hip) and the host side (clustering: driver.cpp,
+// index.cpp, pass.cpp, load.cpp, probes.cpp through cluster_ctx.h; dropin_*.cpp through ctx.h).  Not part of the C
+// ABI (see include/umiclust.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

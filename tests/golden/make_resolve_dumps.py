@@ -1,4 +1,4 @@
-"""Record resolve_block calls of real clustering runs on the GPU (UMICLUST_RESOLVE_DUMP, driver.cpp
+"""Record resolve_block calls of real clustering runs on the GPU (UMICLUST_RESOLVE_DUMP, pass.cpp
 write_resolve_dump) for the host-only ThreadSanitizer replay (tools/resolve_tsan_main.cpp,
 tests/test_sanitizers_cpu.py).  Run on the GPU box; the dumps (gzip) are committed under tests/golden/resolve/.
 

@@ -11,7 +11,7 @@ from umiclust import _lib, synth
 pytestmark = pytest.mark.gpu
 
 PF1 = ["0", str(1 << 30)]
-K_TILE, K_DELTA = 65536, 8192  # sealed tile size, delta tile fold threshold (driver.cpp)
+K_TILE, K_DELTA = 65536, 8192  # sealed tile size, delta tile fold threshold (cluster_ctx.h)
 
 
 @pytest.fixture(scope="module")

@@ -28,7 +28,8 @@ def test_oracle_under_asan_ubsan(tmp_path):
 # ---- the drop-in's HIP-free host code (ont-tcrconsensus_amd/csrc/host_io.cpp) under ASan + UBSan ----
 # tools/host_asan_main.cpp drives FASTA/FASTQ reading (threaded slicing past 1 MiB), the vsearch writers, the
 # in-process parse_umi_clusters (against the fixtures the reference itself produced, tests/golden/parse), the
-# detected-UMI writer, BGZF inflation and the argv grammar.  A sanitizer report fails the test.
+# detected-UMI writer, BGZF inflation, the argv grammar, prepare's length sort and the timeline's interval union.  A
+# sanitizer report fails the test.
 import glob
 import gzip
 import json
@@ -268,6 +269,99 @@ def test_host_argv_under_asan(host_asan):
     assert host_asan("argv", "vsearch", "--gapopen", "4X", "--cluster_fast", "a").strip() == "rc -22"
     assert host_asan("argv", "vsearch", "--cluster_fast").strip() == "rc -22"
     assert host_asan("argv", "vsearch", "--cluster_fast", "x" * 300).strip() == "rc -22"  # longer than the buffer
+
+
+# ---- the length filter and sort of umiclust_prepare (host_io.cpp sort_by_length) ----
+K_MAX_LEN, K_MIN_TPL_LEN = 112, 32  # umiclust_consts.h kMaxLen, kMinTplLen
+
+
+def _sortlen(host_asan, tmp_path, lens, bin_in, minlen, maxseq, T):
+    import numpy as np
+    with open(tmp_path / "in.bin", "wb") as f:
+        f.write(struct.pack("<q", len(bin_in) - 1))
+        f.write(np.asarray(bin_in, dtype="<i8").tobytes())
+        f.write(np.asarray(lens, dtype="<u4").tobytes())
+    kept, bad = map(int, host_asan("sortlen", tmp_path / "in.bin", minlen, maxseq, T, tmp_path / "out.bin").split())
+    raw = (tmp_path / "out.bin").read_bytes()
+    nb = len(bin_in)
+    assert len(raw) == 4 * nb + 5 * kept
+    bin_s = np.frombuffer(raw, "<i4", nb)
+    perm = np.frombuffer(raw, "<i4", kept, 4 * nb)
+    hlen = np.frombuffer(raw, "u1", kept, 4 * nb + 4 * kept)
+    return kept, bad, bin_s, perm, hlen
+
+
+def _first_bad(lens, minlen, maxseq):
+    """The first record the load cannot take: longer than kMaxLen inside the window, or kept and too short to align."""
+    import numpy as np
+    kept = (lens >= minlen) & (lens <= min(maxseq, K_MAX_LEN))
+    bad = ((lens > K_MAX_LEN) & (lens <= maxseq)) | (kept & (lens < K_MIN_TPL_LEN))
+    return int(np.flatnonzero(bad)[0]) if bad.any() else -1
+
+
+@pytest.mark.parametrize("T", [1, 5])
+def test_host_sort_by_length_under_asan(host_asan, tmp_path, T):
+    """Against a stable argsort on key kMaxLen - L per bin: bins of 0, 1 and 1,000 records and one on either side of
+    the threaded path's 2^18 threshold; lengths 20..130, so records fall off both ends of the window.  Then both kinds
+    of bad record, and a load whose bad record is in its second bin.  Every comparison is exact."""
+    import numpy as np
+    rng = np.random.default_rng(11)
+    sizes = [0, 1, 1000, (1 << 18) - 1, (1 << 18) + 1]
+    bin_in = np.concatenate([[0], np.cumsum(sizes)])
+    lens = rng.integers(20, 131, size=int(bin_in[-1]), dtype=np.int64)
+    minlen, maxseq = K_MIN_TPL_LEN, K_MAX_LEN  # the window no record of which is bad
+    kept, bad, bin_s, perm, hlen = _sortlen(host_asan, tmp_path, lens, bin_in, minlen, maxseq, T)
+    want_perm, want_bin_s = [], [0]
+    for b in range(len(sizes)):
+        i = np.arange(bin_in[b], bin_in[b + 1])
+        i = i[(lens[i] >= minlen) & (lens[i] <= maxseq)]
+        want_perm.append(i[np.argsort(K_MAX_LEN - lens[i], kind="stable")])
+        want_bin_s.append(want_bin_s[-1] + len(i))
+    want_perm = np.concatenate(want_perm)
+    assert bad == -1 and kept == len(want_perm)
+    assert 0 < kept < len(lens) and lens.min() < minlen and lens.max() > maxseq
+    assert bin_s.tolist() == want_bin_s
+    assert np.array_equal(perm, want_perm)
+    assert np.array_equal(hlen, lens[want_perm])
+    # bad records: too long inside the caller's window, kept but too short, both (the first in input order wins)
+    for lo, hi in [(K_MIN_TPL_LEN, 130), (20, K_MAX_LEN), (20, 130)]:
+        want = _first_bad(lens, lo, hi)
+        assert want >= 0
+        assert _sortlen(host_asan, tmp_path, lens, bin_in, lo, hi, T)[1] == want
+    # the bad record in the second bin, behind a first bin that sorts (on the threaded path when T > 1)
+    n0 = (1 << 18) + 3
+    two = np.concatenate([rng.integers(K_MIN_TPL_LEN, K_MAX_LEN + 1, size=n0), rng.integers(20, 131, size=5000)])
+    want = _first_bad(two, 20, 130)
+    assert want >= n0
+    kept, bad, bin_s, _perm, _hlen = _sortlen(host_asan, tmp_path, two, [0, n0, len(two)], 20, 130, T)
+    assert bad == want and bin_s[0] == 0 and bin_s[1] == n0
+
+
+# ---- the timeline's interval union (interval_union.h IntervalUnion) ----
+def test_host_interval_union_under_asan(host_asan, tmp_path):
+    """Against a brute-force union over the integer grid: a few hundred intervals arriving roughly in order (neighbours
+    overlap and swap), cap 64 and keep 8, so the held intervals are folded several times; late arrivals start below
+    fold_hi, inside the last folded interval (every interval is at least 16 long), where the clipping loses nothing the
+    union does not already hold.  Integer endpoints below 2^20 are exact in float."""
+    import numpy as np
+    rng = random.Random(17)
+    lines = []
+    for k in range(400):
+        a = max(0, 100 * k + rng.randint(-150, 150))
+        lines.append(f"{a} {a + rng.randint(16, 90)}")
+        if k % 9 == 8:
+            lines.append(f"late {rng.randint(1, 16)} {rng.choice([0, 0, rng.randint(1, 400)])}")
+    (tmp_path / "iv.txt").write_text("\n".join(lines) + "\n")
+    out = host_asan("union", 64, 8, tmp_path / "iv.txt").splitlines()
+    added = [tuple(int(float(x)) for x in line.split()) for line in out[:-2]]
+    folds, measure = int(out[-2].split()[1]), float(out[-1].split()[1])
+    nlate = sum(line.startswith("late") for line in lines)
+    assert folds >= 5 and len(added) > len(lines) - nlate + 30  # folded several times; late arrivals were added
+    assert max(b for _, b in added) < (1 << 20)
+    grid = np.zeros(1 << 20, dtype=bool)
+    for a, b in added:
+        grid[a:b] = True
+    assert abs(measure - int(grid.sum())) <= 1e-3
 
 
 # ---- the host resolve (ont-tcrconsensus_amd/csrc/resolve.cpp) under ThreadSanitizer ----

@@ -12,6 +12,12 @@
 //   host_asan umis <in.fa> <res.txt> <out.fa> <a3>  write_detected_umis (res: 6 ints per record)
 //   host_asan bgzf <in.bgzf> <out.raw>         inflate_bgzf
 //   host_asan argv <args...>                   umiclust_params_from_argv: the decoded fields
+//   host_asan sortlen <in.bin> <minlen> <maxseq> <T> <out.bin>   sort_by_length.  in: int64 nbins, int64
+//        bin_in[nbins + 1], uint32 rec_len[n]; prints "kept bad"; out: int32 bin_s[nbins + 1], int32 perm[kept],
+//        uint8 hlen[kept]
+//   host_asan union <cap> <keep> <in.txt>      IntervalUnion (interval_union.h).  in: "a b" adds [a, b); "late d x"
+//        adds [fold_hi - d, fold_hi + x), a late arrival (skipped until something has been folded).  Prints every
+//        interval as added, then "folds <count>" and "measure <value>"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +25,7 @@
 #include <vector>
 
 #include "../ont-tcrconsensus_amd/csrc/host_io.h"
+#include "../ont-tcrconsensus_amd/csrc/interval_union.h"
 
 using namespace uc::io;
 
@@ -142,6 +149,59 @@ int main(int argc, char** argv) {
       if (!fo) return 2;
       if (!raw.empty()) fwrite(raw.data(), 1, raw.size(), fo);
       fclose(fo);
+      return 0;
+    }
+    if (cmd == "sortlen" && argc == 7) {
+      FILE* fi = fopen(argv[2], "rb");
+      if (!fi) return 3;
+      int64_t nbins = 0;
+      if (fread(&nbins, 8, 1, fi) != 1 || nbins < 1 || nbins > (1 << 20)) return 4;
+      std::vector<int64_t> bin_in((size_t)nbins + 1);
+      if (fread(bin_in.data(), 8, bin_in.size(), fi) != bin_in.size() || bin_in[0] != 0) return 4;
+      for (int64_t b = 0; b < nbins; b++)
+        if (bin_in[b + 1] < bin_in[b]) return 4;
+      const int64_t n = bin_in[nbins];
+      std::vector<uint32_t> rec_len((size_t)n);
+      if (n && fread(rec_len.data(), 4, (size_t)n, fi) != (size_t)n) return 4;
+      fclose(fi);
+      // exactly what the caller must provide: room for every record, nbins + 1 boundaries
+      std::vector<int32_t> perm((size_t)n), bin_s((size_t)nbins + 1, 0);
+      std::vector<uint8_t> hlen((size_t)n);
+      const LenSort ls = sort_by_length(rec_len.data(), bin_in.data(), (int32_t)nbins, atoll(argv[3]), atoll(argv[4]),
+                                        atoi(argv[5]), perm.data(), hlen.data(), bin_s.data());
+      printf("%lld %lld\n", (long long)ls.kept, (long long)ls.bad);
+      FILE* fo = fopen(argv[6], "wb");
+      if (!fo) return 2;
+      fwrite(bin_s.data(), 4, bin_s.size(), fo);
+      if (ls.kept) {
+        fwrite(perm.data(), 4, (size_t)ls.kept, fo);
+        fwrite(hlen.data(), 1, (size_t)ls.kept, fo);
+      }
+      fclose(fo);
+      return 0;
+    }
+    if (cmd == "union" && argc == 5) {
+      uc::IntervalUnion u((size_t)atoll(argv[2]), (size_t)atoll(argv[3]));
+      FILE* fi = fopen(argv[4], "r");
+      if (!fi) return 3;
+      char line[128];
+      int folds = 0;
+      while (fgets(line, sizeof line, fi)) {
+        float a = 0, b = 0;
+        if (sscanf(line, "late %f %f", &a, &b) == 2) {
+          if (u.fold_hi < 0) continue;  // nothing folded yet
+          a = u.fold_hi - a;
+          b = u.fold_hi + b;
+        } else if (sscanf(line, "%f %f", &a, &b) != 2) {
+          return 4;
+        }
+        const float hi = u.fold_hi;
+        u.add(a, b);
+        folds += u.fold_hi != hi;
+        printf("%.1f %.1f\n", a, b);
+      }
+      fclose(fi);
+      printf("folds %d\nmeasure %.6f\n", folds, u.measure());
       return 0;
     }
     if (cmd == "argv") {

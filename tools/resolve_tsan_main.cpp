@@ -1,6 +1,6 @@
 // resolve_tsan_main.cpp -- host-only replay of recorded resolve_block calls (test infrastructure, no GPU).
 //
-// driver.cpp writes a pass's inputs, round-B pairs and results, and outputs with UMICLUST_RESOLVE_DUMP
+// pass.cpp writes a pass's inputs, round-B pairs and results, and outputs with UMICLUST_RESOLVE_DUMP
 // (write_resolve_dump); this replays each dump through resolve.cpp's resolve_block with a worker pool of 1, 3 and
 // 8 threads -- the classify phase on the pool, the in-order phase and round B on the caller, as in a clustering
 // run -- and checks every output against the recorded one (states, targets, strands of the block, the new
