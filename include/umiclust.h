@@ -297,6 +297,35 @@ int64_t umiclust_region_split(umiclust_ctx *ctx, const char *bam_file, int32_t n
                               int64_t *counts, int64_t *reads_per_cluster, int32_t ncluster_cap,
                               uint8_t *region_detected, char *missing_name, int32_t missing_cap);
 
+/* ---- region binning fused with UMI extraction (row f4+f1) ---- */
+/* umiclust_region_split followed by umiclust_extract_umis_file on every file it wrote, in one pass over the BAM and
+ * without the region FASTA files: for every cluster k with a kept record, <umi_out_dir>/region_cluster<k>_detected_umis.fasta
+ * is created (truncated, as the reference opens it with "w") and holds, in BAM order, one write_fasta record
+ * (extract_umis.py:154-186) per kept record in whose two windows both UMIs were found -- the bytes the two calls
+ * produce one after the other; a cluster whose reads yield no UMI gets an empty file.  The UMI search runs on the
+ * device on the record's 4-bit sequence: the read is the text umiclust_region_split would have written (the forward
+ * sequence, `None` for a record without one), the windows are seq[:adapter_length_5_end] and
+ * seq[-adapter_length_3_end:] (any lengths >= 0), the patterns umiclust_extract_umis' (1..64 symbols).  The header
+ * fields are those of the text `{query_name};strand={+|-}`: read name = that text up to its first ';', strand = what
+ * follows its first "strand=" up to the next one, so a query name holding ';' or "strand=" comes out as from the
+ * two calls.  counts, reads_per_cluster, region_detected, missing_name and the refusal of malformed records are
+ * umiclust_region_split's; umis_per_cluster[k] (ncluster_cap entries) = records written for cluster k (the
+ * reference's n_both_umi).  Returns the number of clusters with a kept record = files created.
+ * The reference's KeyError (see umiclust_region_split): counts and missing_name are filled, UMICLUST_EFORMAT is
+ * returned and no file is created, since the exception ends the pipeline before extract_umis starts.
+ * Differences: a kept record whose query name holds a byte in "\t\n\v\f\r " (SAM forbids them) is refused with
+ * UMICLUST_EFORMAT naming the record, nothing written; and the read keeps a '=' base code, which the FASTA parser of
+ * umiclust_extract_umis_file drops (it keeps letters only) and the reference's reader keeps. */
+int64_t umiclust_region_split_extract(umiclust_ctx *ctx, const char *bam_file, int32_t nregions,
+                                      const char *const *region_names, const int64_t *region_lengths,
+                                      const int32_t *region_clusters, double minimal_region_overlap,
+                                      int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                      int32_t adapter_length_5_end, int32_t adapter_length_3_end,
+                                      int32_t max_pattern_dist, const char *umi_fwd, const char *umi_rev,
+                                      const char *umi_out_dir, int64_t *counts, int64_t *reads_per_cluster,
+                                      int64_t *umis_per_cluster, int32_t ncluster_cap, uint8_t *region_detected,
+                                      char *missing_name, int32_t missing_cap);
+
 /* ---- quality filtering (row f5) ---- */
 /* Replaces the `vsearch --fastq_filter` subprocess of vsearch_fastq_filtering
  * (/root/reference/ont_tcr_consensus/preprocessing.py:104-159, argv :129-148; run once per library between
@@ -456,6 +485,20 @@ int64_t umiclust_bam_split(umiclust_ctx *ctx, const uint8_t *keep, int32_t nregi
                            const char *const *bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
                            int32_t max_softclip_3_end, int64_t *counts, int64_t *reads_per_bucket,
                            uint8_t *region_detected, char *missing_name, int32_t missing_cap);
+/* umiclust_bam_split fused with the UMI extraction, as umiclust_region_split_extract fuses umiclust_region_split
+ * (row f4+f1): the same arguments, classes, counters and KeyError, but bucket b's kept records go to
+ * bucket_umi_paths[b] as detected-UMI records (the file is truncated; one is created for every bucket with a kept
+ * record, empty if none of them holds both UMIs) and no region FASTA is written.  umis_per_bucket[nbuckets] = records
+ * written.  On the KeyError no file is created.  Returns the number of buckets with a kept record. */
+int64_t umiclust_bam_split_extract(umiclust_ctx *ctx, const uint8_t *keep, int32_t nregions,
+                                   const char *const *region_names, const int64_t *region_lengths,
+                                   const int32_t *region_buckets, int32_t nbuckets,
+                                   const char *const *bucket_umi_paths, double minimal_region_overlap,
+                                   int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                   int32_t adapter_length_5_end, int32_t adapter_length_3_end,
+                                   int32_t max_pattern_dist, const char *umi_fwd, const char *umi_rev,
+                                   int64_t *counts, int64_t *reads_per_bucket, int64_t *umis_per_bucket,
+                                   uint8_t *region_detected, char *missing_name, int32_t missing_cap);
 /* Per record (n-sized arrays, either may be NULL) the query name's tail: what follows its last "_", or the whole name
  * without one.  A tail of 1 to 18 ASCII digits (leading zeros included): value[r] = its decimal value, status[r] = 1.
  * Any other tail (empty, signed, a non-digit, 19 digits or more): status[r] = 0, value[r] = 0, and the caller applies

@@ -187,6 +187,50 @@ void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask
   }
 }
 
+// ---------------------------------------------------------------- detected-UMI record (row f4+f1)
+std::string forward_text(const uint8_t* rec) {
+  const uint8_t* f = rec + 4;
+  const uint32_t lrn = f[8], ncig = ld_u16(f + 12), flag = ld_u16(f + 14);
+  const int32_t lseq = (int32_t)ld_u32(f + 16);
+  if (lseq <= 0) return "None";
+  const uint8_t* sq = f + 32 + lrn + 4 * (size_t)ncig;
+  const bool rev = (flag & 0x10u) != 0;
+  std::string out((size_t)lseq, '\0');
+  for (int32_t x = 0; x < lseq; x++) {
+    const int32_t y = rev ? lseq - 1 - x : x;
+    char ch = "=ACMGRSVTWYHKDBN"[(sq[y >> 1] >> (((y & 1) ^ 1) * 4)) & 15u];
+    if (rev) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+    out[(size_t)x] = ch;
+  }
+  return out;
+}
+
+std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3) {
+  const uint8_t* f = rec + 4;
+  const std::string read = forward_text(rec);
+  std::string hdr((const char*)f + 32, (size_t)f[8] - 1);
+  hdr += (ld_u16(f + 14) & 0x10u) ? ";strand=-" : ";strand=+";
+  const std::string rid = hdr.substr(0, hdr.find(';'));
+  const size_t s0 = hdr.find("strand=") + 7, s1 = hdr.find("strand=", s0);
+  const std::string strand = hdr.substr(s0, s1 == std::string::npos ? s1 : s1 - s0);
+  const size_t L = read.size(), w3 = (a3 == 0 || (size_t)a3 > L) ? L : (size_t)a3;
+  const std::string u5 = read.substr((size_t)res[1], (size_t)(res[2] - res[1] + 1));
+  const std::string u3 = read.substr(L - w3 + (size_t)res[4], (size_t)(res[5] - res[4] + 1));
+  std::string out = ">" + rid + ";strand=" + strand + ";umi_fwd_dist=" + std::to_string(res[0]) + ";umi_rev_dist=" +
+                    std::to_string(res[3]) + ";umi_fwd_seq=" + u5 + ";umi_rev_seq=" + u3 + ";seq=" + read + "\n";
+  if (strand == "+") {
+    out += u5 + u3;
+  } else {
+    for (const std::string* u : {&u3, &u5})
+      for (size_t x = u->size(); x-- > 0;) {
+        const char ch = (*u)[x];
+        out.push_back(ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'T' ? 'A' : ch == 'G' ? 'C' : ch);
+      }
+  }
+  out.push_back('\n');
+  return out;
+}
+
 // ---------------------------------------------------------------- BGZF writer
 namespace {
 

@@ -64,6 +64,16 @@ inline uint64_t cs_seed(int k) { return 0x243f6a8885a308d3ull + (uint64_t)k * 0x
 // one record, exactly as the kernel computes it (roff = offset of its block_size field)
 void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask, ScanRow& out);
 
+// ---- the detected-UMI record of one BAM record (row f4+f1) ----
+// The read as k_bam_emit (regionsplit.hip) writes it: the forward sequence (reverse strand: reversed, A/C/G/T
+// complemented), "None" for a record without one.  rec = the record's block_size field; its fields have been checked.
+std::string forward_text(const uint8_t* rec);
+// What extract_umis.py prints for the FASTA entry ">{name};strand={+|-}" + forward_text, given the six values of
+// umiclust_extract_umis (both UMIs found) and the 3' window length a3: read name = header up to its first ';', strand
+// = header.split("strand=")[1], combined UMI = u5 + u3 on "+", their reverse complements swapped on anything else.
+// The host restatement of k_bam_emit_umi, and the formatter of the records whose name holds "strand=".
+std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3);
+
 // ---- BGZF writer ----
 // The file at `path` inflates to raw[0, header_end) followed by the records r with keep[r] != 0 (record r =
 // raw[roff[r], roff[r] + 4 + block_size)), in input order: blocks of at most 0xff00 payload bytes, raw deflate, the BC

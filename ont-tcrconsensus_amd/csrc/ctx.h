@@ -171,6 +171,9 @@ struct Ctx {
 // the core of a context (driver.cpp: the upcast); null for null
 Ctx* core(umiclust_ctx* c);
 
+// the match masks of the two UMI patterns (dropin_extract.cpp): 1..64 symbols each, the reference's IUPAC equalities
+void build_patterns(Ctx* c, const char* fwd, const char* rev, ExtractPatterns& P);
+
 // seconds between two recorded events that have completed
 inline double elapsed_s(Ctx* c, hipEvent_t a, hipEvent_t b) {
   float ms = 0;

@@ -1,6 +1,7 @@
 // dropin_bam.cpp -- the two BAM readers: region binning (§8f f4, regionsplit.hip) and the BAM session with its scan,
 // cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip), and on the session the round-2 region split and the
-// name suffix (§8f f4b / f6b, DESIGN.md §9c, bamsplit.hip).  Their HIP-free halves are in bam_host.h.
+// name suffix (§8f f4b / f6b, DESIGN.md §9c, bamsplit.hip), and on both readers the region split fused with the UMI
+// extraction (§8f f4+f1, DESIGN.md §9d, bamextract.hip).  Their HIP-free halves are in bam_host.h.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -28,22 +29,24 @@ BamSession* bam_session(Ctx* c) {
   if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
   return &c->bs;
 }
-// The kept records among [0, stop) as FASTA text, grouped by bucket and in BAM order within a bucket: the slots are
-// laid out here, the bytes written by k_bam_emit, and every bucket's text is appended to path_of(bucket) (the
-// reference opens the file with "a" for every record).  d_pos: room for a slot per record.  Returns the buckets that
-// got a record; a file that cannot be appended to is UMICLUST_EIO.
-template <typename PathOf>
-std::vector<int32_t> emit_buckets(Ctx* c, const uint8_t* d_raw, const int64_t* d_roff, const int8_t* d_cls,
-                                  DevBuf<int64_t>& d_pos, const std::vector<int8_t>& cls,
+// The text of the kept records among [0, stop), grouped by bucket and in BAM order within a bucket: the slots are laid
+// out here from olen (a kept record may have none), the bytes written by `launch(d_pos, d_out)` (k_bam_emit or
+// k_bam_emit_umi) and then by `patch(pos, out)` on the host, and every bucket's text goes to path_of(bucket), opened
+// with O_WRONLY | O_CREAT | mode: O_APPEND for the region FASTA (the reference opens it with "a" for every record),
+// O_TRUNC for the detected-UMI FASTA (opened with "w").  d_pos: room for a slot per record.  Returns the buckets that
+// hold a kept record, each of which got its file; a file that cannot be written is UMICLUST_EIO.
+template <typename PathOf, typename Launch, typename Patch>
+std::vector<int32_t> emit_buckets(Ctx* c, DevBuf<int64_t>& d_pos, const std::vector<int8_t>& cls,
                                   const std::vector<int32_t>& bkt, const std::vector<int64_t>& olen, int64_t stop,
-                                  PathOf path_of) {
+                                  PathOf path_of, int mode, Launch launch, Patch patch) {
   const int64_t n = (int64_t)cls.size();
   int32_t nb = 0;
   for (int64_t r = 0; r < stop; r++)
     if (cls[r] == kBamKept) nb = std::max(nb, bkt[r] + 1);
   std::vector<int64_t> cbase((size_t)nb + 1, 0), pos(n, -1);
+  std::vector<uint8_t> has((size_t)nb, 0);
   for (int64_t r = 0; r < stop; r++)
-    if (cls[r] == kBamKept) cbase[bkt[r] + 1] += olen[r];
+    if (cls[r] == kBamKept) cbase[bkt[r] + 1] += olen[r], has[bkt[r]] = 1;
   for (int32_t k = 0; k < nb; k++) cbase[k + 1] += cbase[k];
   {
     std::vector<int64_t> cur(cbase.begin(), cbase.end() - 1);
@@ -58,38 +61,118 @@ std::vector<int32_t> emit_buckets(Ctx* c, const uint8_t* d_raw, const int64_t* d
   c->hip(d_out.ensure(outb.size()), "alloc");
   if (stop) {
     c->hip(hipMemcpyAsync(d_pos.p, pos.data(), (size_t)stop * 8, hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(launch_bam_emit(d_raw, d_roff, stop, d_cls, d_pos.p, d_out.p, c->st), "bam emit");
+    c->hip(launch(d_pos.p, d_out.p), "bam emit");
     c->hip(hipMemcpyAsync(outb.data(), d_out.p, (size_t)cbase[nb], hipMemcpyDeviceToHost, c->st), "d2h");
   }
   c->hip(hipStreamSynchronize(c->st), "sync");
+  patch(pos, outb.data());
   std::vector<int32_t> used;
   for (int32_t k = 0; k < nb; k++)
-    if (cbase[k + 1] > cbase[k]) used.push_back(k);
+    if (has[k]) used.push_back(k);
   const int T = std::max(1, std::min<int>(io_threads(), (int)used.size()));
   std::vector<int32_t> bad(T, -1);
   parallel_for(T, [&](int t) {
     for (size_t u = (size_t)t; u < used.size(); u += (size_t)T) {
       const int32_t k = used[u];
       const std::string fn = path_of(k);
-      const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0666);
+      const int fd = open(fn.c_str(), O_WRONLY | O_CREAT | mode, 0666);
       bool ok = fd >= 0 && io::write_all(fd, outb.data() + cbase[k], (size_t)(cbase[k + 1] - cbase[k]));
       if (fd >= 0) ok = (close(fd) == 0) && ok;
       if (!ok) bad[t] = k;
     }
   });
   for (int32_t v : bad)
-    if (v >= 0) c->fail(UMICLUST_EIO, "cannot append %s", path_of(v).c_str());
+    if (v >= 0) c->fail(UMICLUST_EIO, "cannot write %s", path_of(v).c_str());
   return used;
 }
-}  // namespace
 
-int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t nregions, const char* const* region_names,
-                              const int64_t* region_lengths, const int32_t* region_clusters,
-                              double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
-                              const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int32_t ncluster_cap,
-                              uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+// the region FASTA of the kept records (rows f4 / f4b): k_bam_emit, appended
+template <typename PathOf>
+std::vector<int32_t> emit_fasta(Ctx* c, const uint8_t* d_raw, const int64_t* d_roff, const int8_t* d_cls,
+                                DevBuf<int64_t>& d_pos, const std::vector<int8_t>& cls, const std::vector<int32_t>& bkt,
+                                const std::vector<int64_t>& olen, int64_t stop, PathOf path_of) {
+  return emit_buckets(
+      c, d_pos, cls, bkt, olen, stop, path_of, O_APPEND,
+      [&](const int64_t* pos, char* out) { return launch_bam_emit(d_raw, d_roff, stop, d_cls, pos, out, c->st); },
+      [](const std::vector<int64_t>&, char*) {});
+}
+
+// The five extraction parameters of umiclust_region_split_extract / umiclust_bam_split_extract.
+struct UmiArgs {
+  int32_t a5, a3, k;
+  const char* fwd;
+  const char* rev;
+};
+void check_umi_args(Ctx* c, const UmiArgs& u, ExtractPatterns& P) {
+  if (u.a5 < 0 || u.a3 < 0 || u.k < 0) c->fail(UMICLUST_EINVAL, "bad argument");
+  build_patterns(c, u.fwd, u.rev, P);
+}
+
+// The detected-UMI FASTA of the kept records among [0, stop) (row f4+f1): the UMI search on the records
+// in place (k_bam_umi_search), the slots from its sizes, the text by k_bam_emit_umi -- by bam::format_umi_record for a
+// record whose name holds "strand=" -- and one truncated file per bucket that holds a kept record.  A kept record
+// whose name holds white space is refused before any file is opened.  per_bucket[b] (b < cap) = records written.
+template <typename PathOf>
+std::vector<int32_t> emit_umis(Ctx* c, const std::vector<uint8_t>& raw, const std::vector<int64_t>& roff,
+                               const uint8_t* d_raw, const int64_t* d_roff, const int8_t* d_cls, DevBuf<int64_t>& d_pos,
+                               const std::vector<int8_t>& cls, const std::vector<int32_t>& bkt, int64_t stop,
+                               const UmiArgs& u, const ExtractPatterns& P, PathOf path_of, int64_t* per_bucket,
+                               int32_t cap) {
+  const int64_t n = (int64_t)cls.size();
+  DevBuf<ExtractPatterns> d_pat;
+  DevBuf<int32_t> d_res;
+  DevBuf<int64_t> d_len;
+  c->hip(d_pat.ensure(1), "alloc");
+  c->hip(d_res.ensure((size_t)stop * 6 + 1), "alloc");
+  c->hip(d_len.ensure((size_t)stop + 1), "alloc");
+  std::vector<int64_t> olen((size_t)n, 0);
+  c->hip(hipMemcpyAsync(d_pat.p, &P, sizeof(P), hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(launch_bam_umi_search(d_raw, d_roff, stop, d_cls, u.a5, u.a3, u.k, d_pat.p, d_res.p, d_len.p, c->st),
+         "bam umi search");
+  if (stop) c->hip(hipMemcpyAsync(olen.data(), d_len.p, (size_t)stop * 8, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  std::vector<std::pair<int64_t, std::string>> host_text;  // the records the host formats, in BAM order
+  for (int64_t r = 0; r < stop; r++) {
+    if (olen[r] == kUmiBadName) {
+      const std::string name(record_name(raw, roff, r));
+      c->fail(UMICLUST_EFORMAT, "BAM record %lld: white space in the query name '%s'", (long long)r, name.c_str());
+    }
+    if (olen[r] == kUmiHostName) host_text.emplace_back(r, std::string());
+  }
+  if (!host_text.empty()) {
+    std::vector<int32_t> res((size_t)stop * 6);
+    c->hip(hipMemcpyAsync(res.data(), d_res.p, res.size() * 4, hipMemcpyDeviceToHost, c->st), "d2h");
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    for (auto& [r, text] : host_text) {
+      text = bam::format_umi_record(raw.data() + roff[r], res.data() + r * 6, u.a3);
+      olen[r] = (int64_t)text.size();
+    }
+  }
+  if (cap > 0) memset(per_bucket, 0, sizeof(int64_t) * (size_t)cap);
+  for (int64_t r = 0; r < stop; r++)
+    if (cls[r] == kBamKept && olen[r] > 0 && bkt[r] < cap) per_bucket[bkt[r]]++;
+  return emit_buckets(
+      c, d_pos, cls, bkt, olen, stop, path_of, O_TRUNC,
+      [&](const int64_t* pos, char* out) {
+        return launch_bam_emit_umi(d_raw, d_roff, stop, d_len.p, d_res.p, pos, u.a3, out, c->st);
+      },
+      [&](const std::vector<int64_t>& pos, char* out) {
+        for (const auto& [r, text] : host_text) memcpy(out + pos[r], text.data(), text.size());
+      });
+}
+
+// umiclust_region_split (umi null: region_cluster<k>.fasta in out_dir) and umiclust_region_split_extract (umi set:
+// region_cluster<k>_detected_umis.fasta in out_dir, their record counts in umis_per_cluster)
+int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregions, const char* const* region_names,
+                          const int64_t* region_lengths, const int32_t* region_clusters, double minimal_region_overlap,
+                          int32_t max_softclip_5_end, int32_t max_softclip_3_end, const UmiArgs* umi,
+                          const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int64_t* umis_per_cluster,
+                          int32_t ncluster_cap, uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
   uc::Ctx* c = uc::core(ctx);
   UC_GUARD(c, {
+    if (umi && ncluster_cap > 0 && !umis_per_cluster) c->fail(UMICLUST_EINVAL, "bad argument");
+    ExtractPatterns pat;
+    if (umi) check_umi_args(c, *umi, pat);
     if (!bam_file || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
         !counts || ncluster_cap < 0 || (ncluster_cap > 0 && !reads_per_cluster))
       c->fail(UMICLUST_EINVAL, "bad argument");
@@ -153,7 +236,16 @@ int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t n
       if (cls[r] == kBamKept) ncl = std::max(ncl, clu[r] + 1);
     // output grouped by cluster, records in BAM order within a cluster
     const auto cluster_fasta = [&](int32_t k) { return pjoin(out_dir, "region_cluster" + std::to_string(k) + ".fasta"); };
-    const std::vector<int32_t> used = emit_buckets(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, olen, stop, cluster_fasta);
+    const auto cluster_umis = [&](int32_t k) {
+      return pjoin(out_dir, "region_cluster" + std::to_string(k) + "_detected_umis.fasta");
+    };
+    // (the reference's KeyError ends the pipeline before extract_umis starts: no UMI file then)
+    std::vector<int32_t> used;
+    if (!umi)
+      used = emit_fasta(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, olen, stop, cluster_fasta);
+    else if (stop == n)
+      used = emit_umis(c, raw, roff, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, stop, *umi, pat, cluster_umis,
+                       umis_per_cluster, ncluster_cap);
     // counters of the records the reference reached
     int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
     if (reads_per_cluster) memset(reads_per_cluster, 0, sizeof(int64_t) * (size_t)ncluster_cap);
@@ -181,6 +273,31 @@ int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t n
     if (ncl > ncluster_cap) c->fail(UMICLUST_ERANGE, "cluster ids up to %d exceed the counter capacity", ncl - 1);
     return (int64_t)used.size();
   });
+}
+}  // namespace
+
+int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t nregions, const char* const* region_names,
+                              const int64_t* region_lengths, const int32_t* region_clusters,
+                              double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                              const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int32_t ncluster_cap,
+                              uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  return region_split_impl(ctx, bam_file, nregions, region_names, region_lengths, region_clusters, minimal_region_overlap,
+                           max_softclip_5_end, max_softclip_3_end, nullptr, out_dir, counts, reads_per_cluster, nullptr,
+                           ncluster_cap, region_detected, missing_name, missing_cap);
+}
+
+int64_t umiclust_region_split_extract(umiclust_ctx* ctx, const char* bam_file, int32_t nregions,
+                                      const char* const* region_names, const int64_t* region_lengths,
+                                      const int32_t* region_clusters, double minimal_region_overlap,
+                                      int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                      int32_t adapter_length_5_end, int32_t adapter_length_3_end, int32_t max_pattern_dist,
+                                      const char* umi_fwd, const char* umi_rev, const char* umi_out_dir, int64_t* counts,
+                                      int64_t* reads_per_cluster, int64_t* umis_per_cluster, int32_t ncluster_cap,
+                                      uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  const UmiArgs umi{adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev};
+  return region_split_impl(ctx, bam_file, nregions, region_names, region_lengths, region_clusters, minimal_region_overlap,
+                           max_softclip_5_end, max_softclip_3_end, &umi, umi_out_dir, counts, reads_per_cluster,
+                           umis_per_cluster, ncluster_cap, region_detected, missing_name, missing_cap);
 }
 
 // ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
@@ -414,14 +531,20 @@ int64_t umiclust_bam_write(umiclust_ctx* ctx, const uint8_t* keep, const char* o
 // The session holds the inflated file and its columns on the host only (ctx.h BamSession), so each of the two calls
 // below uploads what its kernel reads -- the raw bytes and record offsets, and for the split the four columns and the
 // keep mask -- and frees it on return: no device memory outlives a call.
-int64_t umiclust_bam_split(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregions, const char* const* region_names,
-                           const int64_t* region_lengths, const int32_t* region_buckets, int32_t nbuckets,
-                           const char* const* bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
-                           int32_t max_softclip_3_end, int64_t* counts, int64_t* reads_per_bucket,
-                           uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+namespace {
+// umiclust_bam_split (umi null: bucket_paths are region FASTA files, appended to) and umiclust_bam_split_extract (umi
+// set: bucket_paths are detected-UMI FASTA files, truncated, their record counts in umis_per_bucket)
+int64_t bam_split_impl(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregions, const char* const* region_names,
+                       const int64_t* region_lengths, const int32_t* region_buckets, int32_t nbuckets,
+                       const char* const* bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
+                       int32_t max_softclip_3_end, const UmiArgs* umi, int64_t* counts, int64_t* reads_per_bucket,
+                       int64_t* umis_per_bucket, uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
   uc::Ctx* c = uc::core(ctx);
   UC_GUARD(c, {
     auto& S = *bam_session(c);
+    if (umi && nbuckets > 0 && !umis_per_bucket) c->fail(UMICLUST_EINVAL, "bad argument");
+    ExtractPatterns pat;
+    if (umi) check_umi_args(c, *umi, pat);
     if (nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_buckets)) || nbuckets < 0 ||
         (nbuckets > 0 && (!bucket_paths || !reads_per_bucket)) || !counts)
       c->fail(UMICLUST_EINVAL, "bad argument");
@@ -481,8 +604,13 @@ int64_t umiclust_bam_split(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregi
     for (int64_t r = 0; r < stop; r++)
       if (cls[r] == kBamKept && S.raw[(size_t)S.roff[r] + 12] == 0)
         c->fail(UMICLUST_EFORMAT, "BAM record %lld: l_read_name 0", (long long)r);
-    const std::vector<int32_t> used = emit_buckets(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, bkt, olen, stop,
-                                                   [&](int32_t b) { return std::string(bucket_paths[b]); });
+    const auto bucket_path = [&](int32_t b) { return std::string(bucket_paths[b]); };
+    std::vector<int32_t> used;
+    if (!umi)
+      used = emit_fasta(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, bkt, olen, stop, bucket_path);
+    else if (stop == n)
+      used = emit_umis(c, S.raw, S.roff, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, bkt, stop, *umi, pat, bucket_path,
+                       umis_per_bucket, nbuckets);
     // counters of the records the reference reached
     int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
     if (nbuckets) memset(reads_per_bucket, 0, sizeof(int64_t) * (size_t)nbuckets);
@@ -508,6 +636,31 @@ int64_t umiclust_bam_split(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregi
     }
     return (int64_t)used.size();
   });
+}
+}  // namespace
+
+int64_t umiclust_bam_split(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregions, const char* const* region_names,
+                           const int64_t* region_lengths, const int32_t* region_buckets, int32_t nbuckets,
+                           const char* const* bucket_paths, double minimal_region_overlap, int32_t max_softclip_5_end,
+                           int32_t max_softclip_3_end, int64_t* counts, int64_t* reads_per_bucket,
+                           uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  return bam_split_impl(ctx, keep, nregions, region_names, region_lengths, region_buckets, nbuckets, bucket_paths,
+                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, nullptr, counts,
+                        reads_per_bucket, nullptr, region_detected, missing_name, missing_cap);
+}
+
+int64_t umiclust_bam_split_extract(umiclust_ctx* ctx, const uint8_t* keep, int32_t nregions,
+                                   const char* const* region_names, const int64_t* region_lengths,
+                                   const int32_t* region_buckets, int32_t nbuckets, const char* const* bucket_umi_paths,
+                                   double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                   int32_t adapter_length_5_end, int32_t adapter_length_3_end, int32_t max_pattern_dist,
+                                   const char* umi_fwd, const char* umi_rev, int64_t* counts, int64_t* reads_per_bucket,
+                                   int64_t* umis_per_bucket, uint8_t* region_detected, char* missing_name,
+                                   int32_t missing_cap) {
+  const UmiArgs umi{adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev};
+  return bam_split_impl(ctx, keep, nregions, region_names, region_lengths, region_buckets, nbuckets, bucket_umi_paths,
+                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, &umi, counts, reads_per_bucket,
+                        umis_per_bucket, region_detected, missing_name, missing_cap);
 }
 
 int32_t umiclust_bam_name_suffix(umiclust_ctx* ctx, int64_t* value, uint8_t* status) {

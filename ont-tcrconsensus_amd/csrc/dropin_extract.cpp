@@ -32,8 +32,9 @@ constexpr EqTable make_eq_table() {
   return t;
 }
 constexpr EqTable kEqTable = make_eq_table();
+}  // namespace
 
-void build_patterns(Ctx* c, const char* fwd, const char* rev, ExtractPatterns& P) {
+void uc::build_patterns(Ctx* c, const char* fwd, const char* rev, ExtractPatterns& P) {
   const auto& eqt = kEqTable.eq;
   memset(&P, 0, sizeof(P));
   const char* pats[2] = {fwd, rev};
@@ -50,6 +51,7 @@ void build_patterns(Ctx* c, const char* fwd, const char* rev, ExtractPatterns& P
   }
 }
 
+namespace {
 void extract_device(Ctx* c, const char* seqs, const int64_t* offs, int64_t n, int32_t a5, int32_t a3,
                     int32_t k, const char* fwd, const char* rev, int32_t* out) {
   if (n < 0 || (n > 0 && (!seqs || !offs || !out)) || a5 < 0 || a3 < 0 || k < 0)

@@ -283,6 +283,19 @@ hipError_t launch_bam_classify(const uint8_t* raw, const int64_t* roff, int64_t 
 hipError_t launch_bam_emit(const uint8_t* raw, const int64_t* roff, int64_t n, const int8_t* cls, const int64_t* pos,
                            char* out, hipStream_t st);
 
+// ---- UMI extraction from the kept BAM records (bamextract.hip; row f4+f1) ----
+// res[r * 6 ...] = umiclust_extract_umis' six values for every record r < n with cls[r] == kBamKept, found in the two
+// windows of the read as launch_bam_emit would write it; len[r] = bytes of the record's detected-UMI text (0: a UMI
+// is missing, or the record is not kept), or one of the two marks below
+constexpr int64_t kUmiHostName = -1;  // both UMIs found, the name holds "strand=": the host formats the record
+constexpr int64_t kUmiBadName = -2;   // the name holds white space: the call refuses the file
+hipError_t launch_bam_umi_search(const uint8_t* raw, const int64_t* roff, int64_t n, const int8_t* cls, int32_t a5,
+                                 int32_t a3, int32_t k, const ExtractPatterns* P, int32_t* res, int64_t* len,
+                                 hipStream_t st);
+// the text of every record with len[r] > 0 at out + pos[r]
+hipError_t launch_bam_emit_umi(const uint8_t* raw, const int64_t* roff, int64_t n, const int64_t* len,
+                               const int32_t* res, const int64_t* pos, int32_t a3, char* out, hipStream_t st);
+
 // ---- BAM record scan with tags and the cs:Z group-by (bamscan.hip) ----
 struct BamScanCols {  // one entry per record
   int8_t* cls;        // bam::kScanUnmapped / kScanSecondary / kScanPrimary

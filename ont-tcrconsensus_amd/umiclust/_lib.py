@@ -148,7 +148,7 @@ EXPORTS = [
     "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
-    "umiclust_bam_name_suffix", "umiclust_bam_close",
+    "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -235,6 +235,12 @@ def lib() -> C.CDLL:
     L.umiclust_region_split.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, P(C.c_char_p), P(C.c_int64), P(C.c_int32),
                                         C.c_double, C.c_int32, C.c_int32, C.c_char_p, P(C.c_int64), P(C.c_int64),
                                         C.c_int32, P(C.c_uint8), C.c_char_p, C.c_int32]
+    L.umiclust_region_split_extract.restype = C.c_int64
+    L.umiclust_region_split_extract.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, P(C.c_char_p), P(C.c_int64),
+                                                P(C.c_int32), C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, P(C.c_int64),
+                                                P(C.c_int64), P(C.c_int64), C.c_int32, P(C.c_uint8), C.c_char_p,
+                                                C.c_int32]
     L.umiclust_align_pairs.restype = C.c_int32
     L.umiclust_align_pairs.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_void_p, P(C.c_int64),
                                        C.c_int64, P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_int32,
@@ -301,6 +307,11 @@ def lib() -> C.CDLL:
     L.umiclust_bam_split.argtypes = [C.c_void_p, P(C.c_uint8), C.c_int32, P(C.c_char_p), P(C.c_int64), P(C.c_int32),
                                      C.c_int32, P(C.c_char_p), C.c_double, C.c_int32, C.c_int32, P(C.c_int64),
                                      P(C.c_int64), P(C.c_uint8), C.c_char_p, C.c_int32]
+    L.umiclust_bam_split_extract.restype = C.c_int64
+    L.umiclust_bam_split_extract.argtypes = [C.c_void_p, P(C.c_uint8), C.c_int32, P(C.c_char_p), P(C.c_int64),
+                                             P(C.c_int32), C.c_int32, P(C.c_char_p), C.c_double, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, P(C.c_int64),
+                                             P(C.c_int64), P(C.c_int64), P(C.c_uint8), C.c_char_p, C.c_int32]
     L.umiclust_bam_name_suffix.restype = C.c_int32
     L.umiclust_bam_name_suffix.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_uint8)]
     L.umiclust_bam_close.restype = C.c_int32
@@ -656,6 +667,30 @@ class Context:
         self._check(rc, "region_split")
         return counts, rpc[:cap], det[:R]
 
+    def region_split_extract(self, bam_file: str, names, lengths, clusters, minov: float, s5: int, s3: int, a5: int,
+                             a3: int, k: int, fwd: str, rev: str, umi_out_dir: str):
+        """umiclust_region_split_extract (row f4+f1): region_split and extract_umis_file in one pass,
+        region_cluster<k>_detected_umis.fasta in umi_out_dir and no region FASTA.  (counts[4], reads_per_cluster,
+        umis_per_cluster, region_detected); KeyError(name) as region_split raises it, with no file written."""
+        R = len(names)
+        nm = (C.c_char_p * max(R, 1))(*[x.encode() for x in names])
+        ln = np.asarray(lengths, np.int64)
+        cl = np.asarray(clusters, np.int32)
+        cap = int(max([0] + [k_ + 1 for k_ in clusters]))
+        counts = np.zeros(4, np.int64)
+        rpc, upc = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int64)
+        det = np.zeros(max(R, 1), np.uint8)
+        miss = C.create_string_buffer(4096)
+        P = C.POINTER
+        rc = lib().umiclust_region_split_extract(
+            self._h, os.fspath(bam_file).encode(), R, nm, _i64(ln), cl.ctypes.data_as(P(C.c_int32)), minov, s5, s3, a5,
+            a3, k, fwd.encode(), rev.encode(), os.fspath(umi_out_dir).encode(), _i64(counts), _i64(rpc), _i64(upc), cap,
+            det.ctypes.data_as(P(C.c_uint8)), miss, 4096)
+        if rc == -74 and miss.value:
+            raise KeyError(miss.value.decode())
+        self._check(rc, "region_split_extract")
+        return counts, rpc[:cap], upc[:cap], det[:R]
+
     def bam_open(self, bam_file: str, hash_bits: int = 64) -> "BamSession":
         """umiclust_bam_open: the BAM session of this context (one at a time; row f6)."""
         self._check(lib().umiclust_bam_open(self._h, os.fspath(bam_file).encode(), hash_bits), "bam_open")
@@ -901,6 +936,36 @@ class BamSession:
             raise KeyError(miss.value.decode())
         self._ctx._check(rc, "bam_split")
         return counts, per_bucket[:B], det[:R]
+
+    def split_extract(self, keep, names, lengths, buckets, bucket_umi_paths, overlap: float, s5: int, s3: int, a5: int,
+                      a3: int, k: int, fwd: str, rev: str):
+        """umiclust_bam_split_extract (row f4+f1): split() and extract_umis_file in one pass, the
+        detected-UMI records of bucket b in bucket_umi_paths[b] (truncated) and no region FASTA.  (counts[4],
+        reads_per_bucket, umis_per_bucket, region_detected); KeyError(name) as split() raises it, no file written."""
+        R, B = len(names), len(bucket_umi_paths)
+        P = C.POINTER
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+            if len(keep) != self.n:
+                raise ValueError("keep needs one entry per record")
+            kp = keep.ctypes.data_as(P(C.c_uint8))
+        nm = (C.c_char_p * max(R, 1))(*[x.encode() for x in names])
+        paths = (C.c_char_p * max(B, 1))(*[os.fspath(x).encode() for x in bucket_umi_paths])
+        ln = np.ascontiguousarray(lengths, np.int64)
+        bk = np.ascontiguousarray(buckets, np.int32)
+        counts = np.zeros(4, np.int64)
+        per_bucket, umis = np.zeros(max(B, 1), np.int64), np.zeros(max(B, 1), np.int64)
+        det = np.zeros(max(R, 1), np.uint8)
+        miss = C.create_string_buffer(4096)
+        rc = lib().umiclust_bam_split_extract(
+            self._ctx._h, kp, R, nm, _i64(ln), bk.ctypes.data_as(P(C.c_int32)), B, paths, overlap, s5, s3, a5, a3, k,
+            fwd.encode(), rev.encode(), _i64(counts), _i64(per_bucket), _i64(umis), det.ctypes.data_as(P(C.c_uint8)),
+            miss, 4096)
+        if rc == -74 and miss.value:
+            raise KeyError(miss.value.decode())
+        self._ctx._check(rc, "bam_split_extract")
+        return counts, per_bucket[:B], umis[:B], det[:R]
 
     def name_suffix(self) -> tuple[np.ndarray, np.ndarray]:
         """umiclust_bam_name_suffix: per record (value, status) of the query name's last "_" field; status 0 where the

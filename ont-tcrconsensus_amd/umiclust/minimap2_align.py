@@ -21,7 +21,9 @@ from typing import Union
 import numpy as np
 
 from . import vsearch_umi_cluster as _v
-from .region_split import filter_and_split_reads_by_region_from, generate_region_length_dict_from_ref_fa
+from .extract_umis import UMI_FWD_DEFAULT, UMI_REV_DEFAULT
+from .region_split import (filter_and_split_reads_by_region_from, filter_split_and_extract_umis_by_region_from,
+                           generate_region_length_dict_from_ref_fa)
 
 PRIMARY = 2  # the cls column: 0 unmapped, 1 secondary or supplementary, 2 primary mapped
 
@@ -286,6 +288,28 @@ def filter_consensus_alignments_and_split(consensus_bam_file: Union[str, os.Path
         fastas = filter_and_split_reads_by_region_from(src, keep, filtered, reference, logs_dir, region_fasta_out_dir,
                                                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
     return filtered, fastas
+
+
+def filter_consensus_alignments_split_and_extract(consensus_bam_file: Union[str, os.PathLike[str]],
+                                                  reference: Union[str, os.PathLike[str]],
+                                                  logs_dir: Union[str, os.PathLike[str]], blast_id_threshold: float,
+                                                  umi_fasta_out_dir: Union[str, os.PathLike[str]],
+                                                  minimal_region_overlap: float = 0.9975, max_softclip_5_end: int = 73,
+                                                  max_softclip_3_end: int = 68, adapter_length_5_end: int = None,
+                                                  adapter_length_3_end: int = None, max_pattern_dist: int = 3,
+                                                  umi_fwd: str = UMI_FWD_DEFAULT, umi_rev: str = UMI_REV_DEFAULT):
+    """filter_consensus_alignments_and_split with the UMI extraction of tcr_consensus.py:386-403 fused into the split
+    (row f4+f1): the filter runs as above, then the session's records are split under its keep mask and
+    searched for their UMIs in one pass, so that region_<name>_detected_umis.fasta is written and no region FASTA is.
+    The adapter lengths default to the soft-clip lengths, as the pipeline passes them.  Returns (filtered BAM path, list
+    of the detected-UMI FASTA paths that hold a record)."""
+    with _Opened(consensus_bam_file) as src:
+        filtered, keep = _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
+                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+        umi_fastas = filter_split_and_extract_umis_by_region_from(
+            src, keep, filtered, reference, logs_dir, umi_fasta_out_dir, minimal_region_overlap, max_softclip_5_end,
+            max_softclip_3_end, adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev)
+    return filtered, umi_fastas
 
 
 def estimate_precision_at_num_subreads_from(src, consensus_bam_file, reference, logs_dir, minimal_region_overlap=1.0,

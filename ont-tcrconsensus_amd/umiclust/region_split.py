@@ -22,6 +22,7 @@ from typing import Union
 import numpy as np
 
 from . import vsearch_umi_cluster as _v
+from .extract_umis import UMI_FWD_DEFAULT, UMI_REV_DEFAULT
 
 NEGATIVE_CONTROL_SUFFIXES = ("_v_n", "cdr3j_n", "full_n")  # region_split.py:305
 
@@ -73,16 +74,20 @@ def filter_and_split_reads_by_region_cluster(bam_file: Union[str, os.PathLike[st
         os.fspath(bam_file), names, [region_length_dict[n] for n in names],
         [int(region_cluster_dict[n]) if n in region_cluster_dict else -1 for n in names], minimal_region_overlap,
         max_softclip_5_end, max_softclip_3_end, os.fspath(region_fasta_out_dir))
+    clusters = _write_region_cluster_log(log_file, reference, names, counts, per_cluster, detected)
+    return list({os.path.join(region_fasta_out_dir, "region_cluster{}.fasta".format(k)) for k in clusters})
+
+
+def _write_region_cluster_log(log_file, reference, names, counts, per_cluster, detected):
+    """The <bam>_filter_and_split_reads_by_region_cluster.err log, as region_split.py:285-331 builds it from the loop's
+    counters; returns the clusters that got a read, in the order of the reference's counter."""
     n_unmapped, n_primary_mapped, n_short, n_long = (int(x) for x in counts)
     n_reads_region_cluster_counter = collections.defaultdict(int)
     for k, v in enumerate(per_cluster):
         if v:
             n_reads_region_cluster_counter[k] = int(v)
-    region_cluster_fasta_set = {os.path.join(region_fasta_out_dir, "region_cluster{}.fasta".format(k))
-                                for k in n_reads_region_cluster_counter}
     detected_regions_set = {names[r] for r, d in enumerate(detected) if d}
 
-    # the log, as region_split.py:285-331 builds it
     logging_str = "Total # primary alignments in bam file: " + str(n_primary_mapped) + "\n"
     logging_str += (
         "median # of primary alignments in region clusters that have minimal region overlap and are not too long: "
@@ -105,7 +110,38 @@ def filter_and_split_reads_by_region_cluster(bam_file: Union[str, os.PathLike[st
     with open(log_file, "w") as ferr:
         ferr.write(logging_str)
     del n_unmapped
-    return list(region_cluster_fasta_set)
+    return list(n_reads_region_cluster_counter)
+
+
+def filter_split_and_extract_umis(bam_file: Union[str, os.PathLike[str]],
+                                  region_cluster_dict_json: Union[str, os.PathLike[str]],
+                                  reference: Union[str, os.PathLike[str]], logs_dir: Union[str, os.PathLike[str]],
+                                  umi_fasta_out_dir: Union[str, os.PathLike[str]],
+                                  minimal_region_overlap: float = 0.95, max_softclip_5_end: int = 73,
+                                  max_softclip_3_end: int = 68, adapter_length_5_end: int = None,
+                                  adapter_length_3_end: int = None, max_pattern_dist: int = 3,
+                                  umi_fwd: str = UMI_FWD_DEFAULT, umi_rev: str = UMI_REV_DEFAULT):
+    """filter_and_split_reads_by_region_cluster followed by extract_umis(write_region=True) on every file it returns
+    (tcr_consensus.py:190-223; row f4+f1), in one pass over the BAM (umiclust_region_split_extract):
+    the same .err log and the same region_cluster<k>_detected_umis.fasta files in umi_fasta_out_dir, but no region
+    FASTA is written or read.  The adapter lengths default to the soft-clip lengths, as the pipeline passes them.
+    Returns the UMI FASTA paths that hold a record -- the pipeline's filtered_umi_fasta_list -- in a set's order."""
+    log_file = os.path.join(logs_dir,
+                            os.path.basename(bam_file).split(".")[0] + "_filter_and_split_reads_by_region_cluster.err")
+    with open(region_cluster_dict_json, "r") as json_in:
+        region_cluster_dict = json.load(json_in)
+    region_length_dict = generate_region_length_dict_from_ref_fa(reference=reference)
+    names = list(region_length_dict)
+    counts, per_cluster, umis, detected = _v.context().region_split_extract(
+        os.fspath(bam_file), names, [region_length_dict[n] for n in names],
+        [int(region_cluster_dict[n]) if n in region_cluster_dict else -1 for n in names], minimal_region_overlap,
+        max_softclip_5_end, max_softclip_3_end,
+        max_softclip_5_end if adapter_length_5_end is None else adapter_length_5_end,
+        max_softclip_3_end if adapter_length_3_end is None else adapter_length_3_end, max_pattern_dist, umi_fwd,
+        umi_rev, os.fspath(umi_fasta_out_dir))
+    _write_region_cluster_log(log_file, reference, names, counts, per_cluster, detected)
+    return list({os.path.join(umi_fasta_out_dir, "region_cluster{}_detected_umis.fasta".format(k))
+                 for k, v in enumerate(umis) if v})
 
 
 def filter_and_split_reads_by_region_from(src, keep, bam_file, reference, logs_dir, region_fasta_out_dir,
@@ -124,23 +160,32 @@ def filter_and_split_reads_by_region_from(src, keep, bam_file, reference, logs_d
                                                  list(range(len(names))), paths, minimal_region_overlap,
                                                  max_softclip_5_end, max_softclip_3_end)
     except KeyError:
-        # the reference looks the region up for every primary record, before either filter (:374): the first one
-        # whose reference name the FASTA lacks raises, and a refID of -1 is the name None, not the string 'None'
-        ref = np.asarray(src.ref)
-        primary = np.asarray(src.cls) == 2
-        if keep is not None:
-            primary &= np.asarray(keep) != 0
-        for r in np.flatnonzero(primary).tolist():
-            name = src.ref_names[ref[r]] if 0 <= ref[r] < len(src.ref_names) else None
-            if name not in region_length_dict:
-                raise KeyError(name) from None
+        _split_key_error(src, keep, region_length_dict)
         raise
+    _write_region_log(log_file, reference, names, counts, per_region, detected)
+    return list({paths[r] for r, v in enumerate(per_region) if v})
+
+
+def _split_key_error(src, keep, region_length_dict):
+    """The KeyError of the reference's loop, after the library's: the reference looks the region up for every primary
+    record, before either filter (:374), so the first one whose reference name the FASTA lacks raises, and a refID of
+    -1 is the name None, not the string 'None'."""
+    ref = np.asarray(src.ref)
+    primary = np.asarray(src.cls) == 2
+    if keep is not None:
+        primary &= np.asarray(keep) != 0
+    for r in np.flatnonzero(primary).tolist():
+        name = src.ref_names[ref[r]] if 0 <= ref[r] < len(src.ref_names) else None
+        if name not in region_length_dict:
+            raise KeyError(name) from None
+
+
+def _write_region_log(log_file, reference, names, counts, per_region, detected):
+    """The <bam>_filter_and_split_reads_by_region.err log, as region_split.py:397-430 builds it."""
     n_unmapped, n_primary_mapped, n_short, n_long = (int(x) for x in counts)
     n_reads_region_counter = {names[r]: int(v) for r, v in enumerate(per_region) if v}
-    region_fasta_set = {paths[r] for r, v in enumerate(per_region) if v}
     detected_regions_set = {names[r] for r, d in enumerate(detected) if d}
 
-    # the log, as region_split.py:397-430 builds it
     logging_str = "Total # primary alignments in bam file: " + str(n_primary_mapped) + "\n"
     logging_str += ("median # of primary alignments in regions that have minimal region overlap and are not too long: "
                     + str(round(np.median(list(n_reads_region_counter.values())), 3)) + "\n")
@@ -159,7 +204,39 @@ def filter_and_split_reads_by_region_from(src, keep, bam_file, reference, logs_d
     with open(log_file, "w") as ferr:
         ferr.write(logging_str)
     del n_unmapped
-    return list(region_fasta_set)
+
+
+def filter_split_and_extract_umis_by_region_from(src, keep, bam_file, reference, logs_dir, umi_fasta_out_dir,
+                                                 minimal_region_overlap=0.95, max_softclip_5_end=73,
+                                                 max_softclip_3_end=68, adapter_length_5_end=None,
+                                                 adapter_length_3_end=None, max_pattern_dist=3,
+                                                 umi_fwd=UMI_FWD_DEFAULT, umi_rev=UMI_REV_DEFAULT):
+    """filter_and_split_reads_by_region_from followed by extract_umis(write_region=True) on every file it returns
+    (tcr_consensus.py:376-403; row f4+f1), in one pass over the session (umiclust_bam_split_extract):
+    the same .err log and the same detected-UMI files, no region FASTA.  A region's file is named as extract_umis names
+    it after region_<name>.fasta: "region_<name>" up to its first ".", then "_detected_umis.fasta"; two regions whose
+    names give one path are a ValueError (the reference lets one file overwrite the other).  Returns the UMI FASTA
+    paths that hold a record, in a set's order."""
+    log_file = os.path.join(logs_dir, os.path.basename(bam_file).split(".")[0] + "_filter_and_split_reads_by_region.err")
+    region_length_dict = generate_region_length_dict_from_ref_fa(reference=reference)
+    names = list(region_length_dict)
+    paths = [os.path.join(umi_fasta_out_dir,
+                          os.path.basename("region_{}.fasta".format(n)).split(".")[0] + "_detected_umis.fasta")
+             for n in names]
+    if len(set(paths)) != len(paths):
+        raise ValueError("two regions share one detected-UMI file name")
+    try:
+        counts, per_region, umis, detected = src.split_extract(
+            keep, names, [region_length_dict[n] for n in names], list(range(len(names))), paths,
+            minimal_region_overlap, max_softclip_5_end, max_softclip_3_end,
+            max_softclip_5_end if adapter_length_5_end is None else adapter_length_5_end,
+            max_softclip_3_end if adapter_length_3_end is None else adapter_length_3_end, max_pattern_dist, umi_fwd,
+            umi_rev)
+    except KeyError:
+        _split_key_error(src, keep, region_length_dict)
+        raise
+    _write_region_log(log_file, reference, names, counts, per_region, detected)
+    return list({paths[r] for r, v in enumerate(umis) if v})
 
 
 def filter_and_split_reads_by_region(bam_file: Union[str, os.PathLike[str]], reference: Union[str, os.PathLike[str]],

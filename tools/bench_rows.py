@@ -8,7 +8,10 @@ used only as the checker and the CPU baseline) timed on a bounded sample on one 
   f1 extract_umis   (extract_umis.py:19-267): N synthetic ~1 kb reads with both UMIs in their adapter windows
   f3 overlap        (extract_umis.py:270-369): 40 regions x 20k UMIs (64 nt, shared pool -> overlaps)
   f4 region binning (region_split.py:219-333): a BGZF BAM of N/2 records over 60 regions
-Inputs are synthetic and seeded.  Prints one JSON object.
+  f4f1 region binning fused with the UMI extraction: a BGZF BAM of N reads of 600 nt with planted
+       UMIs over 60 regions, through region_split + extract_umis_file per file and through region_split_extract,
+       alternating; the median and spread of --repeats warm runs each, the bytes each path writes and reads
+Inputs are synthetic and seeded.  Prints one JSON object.  --rows selects the rows.
 """
 from __future__ import annotations
 
@@ -16,6 +19,8 @@ import argparse
 import ctypes as C
 import json
 import os
+import shutil
+import statistics
 import struct
 import sys
 import tempfile
@@ -168,8 +173,10 @@ def _bgzf(raw: bytes, block: int = 65000) -> bytes:
     return b"".join(out)
 
 
-def f4_bam(path: str, n: int, nref: int = 60, lseq: int = 600, seed: int = 17):
-    """A BAM of n fixed-layout records (name r%09d, one CIGAR op) over nref regions of length 500."""
+def f4_bam(path: str, n: int, nref: int = 60, lseq: int = 600, seed: int = 17, umis: bool = False):
+    """A BAM of n fixed-layout records (name r%09d, one CIGAR op) over nref regions of length 500.  umis: the forward
+    read is 20 nt, an instance of UMI_FWD, a body, an instance of UMI_REV and 15 nt (f1_reads' layout); a reverse
+    record stores its reverse complement."""
     rng = np.random.default_rng(seed)
     refs = [(f"TRBV{r}_1", 500) for r in range(nref)]
     hdr = bytearray(b"BAM\x01") + struct.pack("<i", 11) + b"@HD\tVN:1.6\n" + struct.pack("<i", nref)
@@ -198,6 +205,16 @@ def f4_bam(path: str, n: int, nref: int = 60, lseq: int = 600, seed: int = 17):
     rec["cig"] = (aln << 4).astype(np.uint32)
     codes = np.array([1, 2, 4, 8], np.uint8)
     s = codes[rng.integers(0, 4, (n, lseq))]
+    if umis:
+        fwd, rev = _instances(rng, synth.UMI_FWD, n), _instances(rng, synth.UMI_REV, n)
+        to_code = np.zeros(256, np.uint8)
+        to_code[ACGT] = codes
+        s[:, 20:20 + fwd.shape[1]] = to_code[fwd]
+        s[:, lseq - 15 - rev.shape[1]:lseq - 15] = to_code[rev]
+        comp = np.zeros(16, np.uint8)
+        comp[codes] = codes[::-1]  # A <-> T, C <-> G
+        back = (flag & 16) != 0
+        s[back] = comp[s[back][:, ::-1]]
     rec["seq"] = (s[:, 0::2] << 4) | s[:, 1::2]
     rec["qual"] = 0xff
     with open(path, "wb") as fh:
@@ -249,15 +266,79 @@ def bench_f4(ctx, n: int, cpu_records: int) -> dict:
                 note="wall through the C ABI: BGZF inflate on host threads, device classify/emit, files appended")
 
 
+def _dir_bytes(d: str) -> int:
+    return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+
+
+def bench_f4f1(ctx, n: int, repeats: int) -> dict:
+    """The two-step path and the fused call on one BAM, alternating, each into a fresh directory of the same kind."""
+    tmp = tempfile.mkdtemp(prefix="rows_f4f1_")
+    path = os.path.join(tmp, "bc.bam")
+    refs = f4_bam(path, n, umis=True)
+    names, lengths = [r[0] for r in refs], [r[1] for r in refs]
+    clusters = [i // 2 for i in range(len(refs))]
+    fwd, rev = synth.UMI_FWD, synth.UMI_REV
+
+    def two_step(fa, out):
+        t0 = time.perf_counter()
+        ctx.region_split(path, names, lengths, clusters, 0.95, 73, 68, fa)
+        t1 = time.perf_counter()
+        found = sum(ctx.extract_umis_file(os.path.join(fa, f), os.path.join(out, f[:-len(".fasta")] + "_detected_umis.fasta"),
+                                          73, 68, 3, fwd, rev) for f in sorted(os.listdir(fa)))
+        return time.perf_counter() - t0, t1 - t0, found
+
+    def fused(out):
+        t0 = time.perf_counter()
+        res = ctx.region_split_extract(path, names, lengths, clusters, 0.95, 73, 68, 73, 68, 3, fwd, rev, out)
+        return time.perf_counter() - t0, res
+
+    t_two, t_split, t_fused = [], [], []
+    same = found = res = None
+    io = {}
+    for it in range(repeats + 1):  # run 0 warms both paths up and compares their files
+        d = {k: os.path.join(tmp, f"{k}{it}") for k in ("fa", "two", "one")}
+        for v in d.values():
+            os.makedirs(v)
+        a, a_split, found = two_step(d["fa"], d["two"])
+        b, res = fused(d["one"])
+        if it == 0:
+            same = sorted(os.listdir(d["two"])) == sorted(os.listdir(d["one"])) and all(
+                open(os.path.join(d["two"], f), "rb").read() == open(os.path.join(d["one"], f), "rb").read()
+                for f in os.listdir(d["two"]))
+            same = same and int(res[2].sum()) == found
+            io = dict(region_fasta_bytes=_dir_bytes(d["fa"]), umi_fasta_bytes=_dir_bytes(d["one"]))
+        else:
+            t_two.append(a), t_split.append(a_split), t_fused.append(b)
+        for v in d.values():
+            shutil.rmtree(v)
+    bam_bytes = os.path.getsize(path)
+    shutil.rmtree(tmp)
+    stat = lambda ts: dict(median_s=statistics.median(ts), min_s=min(ts), max_s=max(ts), runs=len(ts))  # noqa: E731
+    return dict(row="f4+f1 filter_split_and_extract_umis", records=n, read_len=600, bam_bytes=bam_bytes,
+                kept=int(res[1].sum()), both_umis_found=int(found), files_equal=bool(same),
+                two_step=dict(stat(t_two), region_split_median_s=statistics.median(t_split),
+                              bytes_written=io["region_fasta_bytes"] + io["umi_fasta_bytes"],
+                              bytes_read=bam_bytes + io["region_fasta_bytes"]),
+                fused=dict(stat(t_fused), bytes_written=io["umi_fasta_bytes"], bytes_read=bam_bytes),
+                fused_over_two_step=statistics.median(t_fused) / statistics.median(t_two),
+                note="wall through the C ABI, the two paths alternating on one BAM, outputs under the temporary "
+                     "directory; run 0 (warm-up, file comparison) is not timed")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--rows", default="f1,f3,f4,f4f1")
+    ap.add_argument("--repeats", type=int, default=5, help="timed runs of each path of row f4f1")
     args = ap.parse_args()
     ctx = _lib.Context(0)
     rows = []
     for name, fn in (("f1", lambda: bench_f1(ctx, args.reads, 150)), ("f3", lambda: bench_f3(ctx, 40, 20_000, 40)),
-                     ("f4", lambda: bench_f4(ctx, args.reads // 2, 20_000))):
+                     ("f4", lambda: bench_f4(ctx, args.reads // 2, 20_000)),
+                     ("f4f1", lambda: bench_f4f1(ctx, args.reads, args.repeats))):
+        if name not in args.rows.split(","):
+            continue
         t0 = time.perf_counter()
         rows.append(fn())
         print(f"{name} done in {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
