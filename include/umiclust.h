@@ -278,7 +278,7 @@ int64_t umiclust_extract_umis_file(umiclust_ctx *ctx, const char *fastx_file, co
 
 /* ---- region binning ---- */
 /* Replaces the record loop of filter_and_split_reads_by_region_cluster
- * (/root/reference/ont_tcr_consensus/region_split.py:219-333): BAM in (BGZF inflated on the host threads,
+ * (/root/reference/ont_tcr_consensus/region_split.py:219-333): BAM in (BGZF inflated on the device, DESIGN.md §9e,
  * records classified and FASTA records built on the device), every kept primary alignment appended to
  * <out_dir>/region_cluster<k>.fasta as `>{query_name};strand={+|-}` + its forward sequence, in BAM order.
  * Regions come from the reference FASTA (names, lengths) and the cluster JSON (region_clusters[r], -1 if the
@@ -416,7 +416,7 @@ int64_t umiclust_fastq_filter_stats_argv(umiclust_ctx *ctx, int32_t argc, const 
 /* Replaces the per-record loops of ont_tcr_consensus/minimap2_align.py: count_cs_tags (:21-37, called on every
  * library's raw-read BAM at :140 and on the filtered consensus BAM at :341), calculate_blast_id (:13-18) and the
  * record loop and BAM output of filter_consensus_alignments (:158-359, :209-245).  A BAM session on the context:
- * open inflates the file on the host threads, scans every record on the device (class, refID, l_seq,
+ * open inflates the file on the device, scans every record on the device (class, refID, l_seq,
  * reference_length, the M/I/D column sum of :14-16, the NM and cs:Z aux tags) and groups the primary records by
  * their cs string exactly (hashed on the device, every member compared with its group's first record, re-run with
  * another seed on a collision).  The columns, names and strings are then read back in bulk and the Python drop-in
@@ -436,10 +436,15 @@ int64_t umiclust_bam_open(umiclust_ctx *ctx, const char *bam_file, int32_t hash_
  * unmapped, secondary or supplementary: the aux fields of such records are not walked, because the reference never
  * reads them, and any defect of a primary record has already failed the open with UMICLUST_EFORMAT */
 int32_t umiclust_bam_counts(umiclust_ctx *ctx, int64_t *out);
-/* DIAGNOSTIC, not part of the drop-in: out[0..2] = seconds of the last open: host inflate, host-to-device copy (HIP
- * events), scan + group + verify kernels of every hashing pass (HIP events).  tools/bam_scan_bench.py reads the
+/* DIAGNOSTIC, not part of the drop-in: out[0..2] = seconds of the last open: wall time from mapping the file until the
+ * inflated bytes are on the host (upload of the compressed bytes, k_bgzf_inflate, copy back), host-to-device copies of
+ * the compressed bytes and the record offsets (HIP events), scan + group + verify kernels of every hashing pass (HIP
+ * events).  tools/bam_scan_bench.py reads the
  * figures of DESIGN.md §9b through it */
 int32_t umiclust_bam_times(umiclust_ctx *ctx, double *out);
+/* DIAGNOSTIC (an added function, ABI version unchanged): out[0..2] of the last open = BGZF blocks in the file, blocks
+ * inflated on the device (every block with ISIZE > 0), compressed bytes uploaded */
+int32_t umiclust_bam_inflate_info(umiclust_ctx *ctx, int64_t *out);
 /* n-sized arrays, each may be NULL.  cls: 0 unmapped (flag & 4, tested first as :28 does), 1 secondary or
  * supplementary (flag & 0x900), 2 primary mapped.  l_seq is pysam's query_length.  reference_length: M/D/N/=/X
  * lengths, a zero sum counted as 1 (htslib bam_endpos).  cols: M/I/D lengths only (:14-16).  nm / nm_present: the
@@ -639,6 +644,17 @@ int32_t umiclust_pass(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int
                       uint16_t *peer_id, uint8_t *peer_count, uint8_t *npeer, umiclust_pass_qs *hostqs, uint32_t *rec,
                       int64_t rec_cap, int64_t *rec_total, uint32_t *res, uint64_t *aligned, umiclust_pass_walk *walk,
                       uint32_t *counters, int64_t *info);
+
+/* The BGZF inflate kernel alone (an added function, ABI version unchanged).
+ * file = a whole BGZF byte string in host memory.  cap == 0: returns the inflated size (sum of ISIZE) without a
+ * launch.  Otherwise inflates on the device into out and returns the size.  block_status (may be NULL): one int32 per
+ * block, 0 = ok, > 0 = the decoder's error class (csrc/inflate.h).  If any block fails: UMICLUST_EFORMAT, the message
+ * names the first bad block and its class, out holds the bytes of every good block at its offset.  A malformed
+ * gzip/BC framing is UMICLUST_EFORMAT before any launch.  n_blocks (may be NULL): the number of blocks, set by every
+ * call that passes the framing.  times (may be NULL): seconds of upload, kernel, download by HIP events.  CRC32 is
+ * not checked. */
+int64_t umiclust_bgzf_inflate(umiclust_ctx *ctx, const uint8_t *file, int64_t n, uint8_t *out, int64_t cap,
+                              int32_t *block_status, int64_t *n_blocks, double *times);
 
 /* ---- measurement (bench.py; no reference counterpart) ---- */
 /* Process-wide device timeline of the counting launches (kind 0) and the alignment chains

@@ -2,8 +2,8 @@
 // DESIGN.md §9b).
 //
 // Replaces the per-record Python loops of ont_tcr_consensus/minimap2_align.py: count_cs_tags (:21-37), calculate_blast_id
-// (:13-18) and the record loop of filter_consensus_alignments (:209-245).  The host inflates the BGZF blocks and
-// finds the record offsets (bam_host.cpp); here one wave per record decodes the fixed fields, sums the CIGAR
+// (:13-18) and the record loop of filter_consensus_alignments (:209-245).  The BGZF blocks are inflated on the device (bgzf.hip)
+// and the host finds the record offsets (bam_host.cpp); here one wave per record decodes the fixed fields, sums the CIGAR
 // lane-strided (reference_length = M/D/N/=/X, cols = M/I/D), and walks the aux fields of a primary record with a
 // wave-uniform cursor: fixed-size types advance by their size, B arrays by subtype size x count, Z/H strings are
 // searched for their NUL 64 bytes a step with a ballot.  The cs string is hashed in the pass that finds its NUL (a sum

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <memory>
 #include <new>
 #include <string>
 #include <utility>
@@ -127,18 +128,43 @@ struct FqState {
   Event ev[3];  // copy begin, kernel begin, kernel end
 };
 
+// The inflated file on the host: a byte array that is not zero-filled when it is made, because the copy from the
+// device writes every byte of it (zero-filling 540 MB on one thread cost more than inflating them)
+struct RawBuf {
+  std::unique_ptr<uint8_t[]> p;
+  size_t n = 0;
+  RawBuf() = default;
+  RawBuf(RawBuf&& o) noexcept : p(std::move(o.p)), n(o.n) { o.n = 0; }  // a moved-from buffer is empty: size() == 0
+  RawBuf& operator=(RawBuf&& o) noexcept {
+    p = std::move(o.p);
+    n = o.n;
+    o.n = 0;
+    return *this;
+  }
+  void alloc(size_t bytes) {
+    p.reset(new uint8_t[bytes ? bytes : 1]);
+    n = bytes;
+  }
+  uint8_t* data() { return p.get(); }
+  const uint8_t* data() const { return p.get(); }
+  size_t size() const { return n; }
+  uint8_t operator[](size_t i) const { return p[i]; }
+};
+
 // BAM session (f6, umiclust_bam_open .. umiclust_bam_close): the inflated file, its header, the record offsets and
-// the columns of the device scan.  Host memory only: umiclust_bam_split and umiclust_bam_name_suffix (f4b / f6b)
+// the columns of the device scan.  The open inflates the file on the device and copies it back; what
+// stays is host memory only: umiclust_bam_split and umiclust_bam_name_suffix (f4b / f6b)
 // upload what their kernels read and free it on return
 struct BamSession {
   bool open = false;
-  std::vector<uint8_t> raw;
+  RawBuf raw;
   bam::Header hdr;
   std::vector<int64_t> roff, reflen, cols, nm, cs_off, g_count, g_rep;
   std::vector<int32_t> ref, l_seq, cs_len, cs_group;
   std::vector<int8_t> cls;
   std::vector<uint8_t> nm_present;
   int64_t n_reruns = 0, first_bad = -1;
+  int64_t inflate_info[3] = {0, 0, 0};  // BGZF blocks, blocks inflated on the device, compressed bytes uploaded
   double t_inflate = 0, t_h2d = 0, t_dev = 0;
 };
 

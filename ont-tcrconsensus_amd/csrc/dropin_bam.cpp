@@ -1,8 +1,11 @@
 // dropin_bam.cpp -- the two BAM readers: region binning (§8f f4, regionsplit.hip) and the BAM session with its scan,
 // cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip), and on the session the round-2 region split and the
 // name suffix (§8f f4b / f6b, DESIGN.md §9c, bamsplit.hip), and on both readers the region split fused with the UMI
-// extraction (§8f f4+f1, DESIGN.md §9d, bamextract.hip).  Their HIP-free halves are in bam_host.h.
+// extraction (§8f f4+f1, DESIGN.md §9d, bamextract.hip).  Both readers inflate the file on the device (DESIGN.md §9e,
+// bgzf.hip on inflate.h), which umiclust_bgzf_inflate runs alone.  Their HIP-free halves are in bam_host.h.
 #include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -13,6 +16,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "inflate.h"
 
 using namespace uc;
 using namespace uc::io;
@@ -20,7 +24,7 @@ using namespace uc::io;
 namespace {
 int32_t rd_i32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
 // the query name of record r: at most l_read_name bytes and never past the record, up to its NUL
-std::string_view record_name(const std::vector<uint8_t>& raw, const std::vector<int64_t>& roff, int64_t r) {
+std::string_view record_name(const RawBuf& raw, const std::vector<int64_t>& roff, int64_t r) {
   const uint8_t* f = raw.data() + roff[r] + 4;
   const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(raw.data() + roff[r]) - 32);
   return {(const char*)f + 32, lrn ? strnlen((const char*)f + 32, lrn) : 0};
@@ -29,6 +33,117 @@ BamSession* bam_session(Ctx* c) {
   if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");
   return &c->bs;
 }
+// ---- BGZF blocks inflated on the device (bgzf.hip)
+// The block table of a BGZF byte string: the blocks with ISIZE > 0 (the others are not launched), their index among
+// all blocks, and the inflated size.
+struct BgzfPlan {
+  std::vector<BgzfBlock> blk;
+  std::vector<int64_t> file_idx;
+  int64_t n_blocks = 0, total = 0;
+};
+bool bgzf_plan(const uint8_t* d, size_t N, BgzfPlan& P) {
+  std::vector<size_t> boff, bsz;
+  std::vector<uint32_t> isz;
+  if (!io::bgzf_blocks(d, N, boff, bsz, isz)) return false;
+  P.n_blocks = (int64_t)boff.size();
+  for (size_t b = 0; b < boff.size(); b++) {
+    const size_t xlen = (size_t)d[boff[b] + 10] | ((size_t)d[boff[b] + 11] << 8);
+    if (isz[b]) {
+      P.blk.push_back({(int64_t)(boff[b] + 12 + xlen), P.total, (uint32_t)(bsz[b] - 12 - xlen - 8), isz[b]});
+      P.file_idx.push_back((int64_t)b);
+    }
+    P.total += isz[b];
+  }
+  return true;
+}
+// d[0 .. N) uploaded (with 8 zero bytes of padding, rounded up to whole words), P's blocks inflated into d_raw
+// (P.total + 1 bytes, as the scan kernels want it), their statuses into `status`, and the inflated bytes copied to
+// host_dst(), which is called once the upload and the kernel are queued, so what it does (allocating, touching the
+// pages) runs beside them.  Returns after the stream has drained.  times (may be null): upload, kernel, download in
+// seconds by HIP events.
+template <typename HostDst>
+void bgzf_inflate_device(Ctx* c, const uint8_t* d, size_t N, const BgzfPlan& P, DevBuf<uint8_t>& d_raw,
+                         std::vector<int32_t>& status, HostDst host_dst, double* times) {
+  const size_t nb = P.blk.size(), padded = (N + 8 + 3) & ~(size_t)3;
+  DevBuf<uint8_t> d_comp;
+  DevBuf<BgzfBlock> d_blk;
+  DevBuf<int32_t> d_st;
+  Event e[4];
+  c->hip(d_comp.ensure(padded), "alloc");
+  c->hip(d_raw.ensure((size_t)P.total + 1), "alloc");
+  alloc_each(c, nb + 1, d_blk, d_st);
+  status.assign(nb, 0);
+  c->hip(hipEventRecord(e[0].get(c), c->st), "event");
+  const size_t tail = std::min<size_t>(padded, 12);  // covers the padding whatever N % 4 is
+  c->hip(hipMemsetAsync(d_comp.p + (padded - tail), 0, tail, c->st), "memset");
+  if (N) c->hip(hipMemcpyAsync(d_comp.p, d, N, hipMemcpyHostToDevice, c->st), "h2d");
+  if (nb) c->hip(hipMemcpyAsync(d_blk.p, P.blk.data(), nb * sizeof(BgzfBlock), hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(hipEventRecord(e[1].get(c), c->st), "event");
+  c->hip(launch_bgzf_inflate(d_comp.p, (int64_t)padded, d_blk.p, (int64_t)nb, d_raw.p, d_st.p, c->st), "bgzf inflate");
+  c->hip(hipEventRecord(e[2].get(c), c->st), "event");
+  if (nb) c->hip(hipMemcpyAsync(status.data(), d_st.p, nb * 4, hipMemcpyDeviceToHost, c->st), "d2h");
+  uint8_t* const host_out = host_dst();
+  if (host_out && P.total)
+    c->hip(hipMemcpyAsync(host_out, d_raw.p, (size_t)P.total, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipEventRecord(e[3].get(c), c->st), "event");
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  if (times)
+    for (int x = 0; x < 3; x++) times[x] = elapsed_s(c, e[x], e[x + 1]);
+}
+
+// What both BAM readers start with: the file mapped and its block table built, the compressed bytes uploaded, the
+// blocks inflated into d_raw, and `raw` copied back to the host, where the header parser, record_offsets, the session
+// and the writer read it.  info: BGZF blocks, blocks inflated on the device, compressed bytes uploaded; *t_upload:
+// seconds of the compressed upload (HIP events).  False for a file that cannot be read, is not BGZF, or has a block
+// the decoder refuses -- what io::inflate_bgzf returned false for.
+bool read_bam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_t>& d_raw, int64_t info[3],
+                        double* t_upload) {
+  struct Map {
+    void* p = nullptr;
+    size_t n = 0;
+    ~Map() {
+      if (p) munmap(p, n);
+    }
+  } map;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return false;
+  struct stat sb;
+  if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) {
+    close(fd);
+    return false;
+  }
+  map.n = (size_t)sb.st_size;
+  if (map.n) map.p = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+  close(fd);
+  if (map.p == MAP_FAILED) {
+    map.p = nullptr;
+    return false;
+  }
+  BgzfPlan P;
+  if (!bgzf_plan((const uint8_t*)map.p, map.n, P)) return false;
+  std::vector<int32_t> status;
+  double t[3] = {0, 0, 0};
+  // while the device inflates: the host's array, its pages touched by the I/O threads (first touch is the cost of
+  // a fresh array this size, and one thread takes several times the kernel's time over it)
+  const auto host_dst = [&]() {
+    raw.alloc((size_t)P.total);
+    uint8_t* const p = raw.data();
+    const size_t n = raw.size(), page = 4096;
+    const int T = std::max(1, std::min<int>(io_threads(), (int)(n >> 22)));
+    parallel_for(T, [&](int th) {
+      const size_t lo = n / (size_t)T * (size_t)th, hi = th + 1 == T ? n : n / (size_t)T * (size_t)(th + 1);
+      for (size_t o = lo; o < hi; o += page) p[o] = 0;
+    });
+    return p;
+  };
+  bgzf_inflate_device(c, (const uint8_t*)map.p, map.n, P, d_raw, status, host_dst, t);
+  info[0] = P.n_blocks, info[1] = (int64_t)P.blk.size(), info[2] = (int64_t)map.n;
+  if (t_upload) *t_upload = t[0];
+  for (int32_t s : status)
+    if (s) return false;
+  return true;
+}
+
 // The text of the kept records among [0, stop), grouped by bucket and in BAM order within a bucket: the slots are laid
 // out here from olen (a kept record may have none), the bytes written by `launch(d_pos, d_out)` (k_bam_emit or
 // k_bam_emit_umi) and then by `patch(pos, out)` on the host, and every bucket's text goes to path_of(bucket), opened
@@ -113,7 +228,7 @@ void check_umi_args(Ctx* c, const UmiArgs& u, ExtractPatterns& P) {
 // record whose name holds "strand=" -- and one truncated file per bucket that holds a kept record.  A kept record
 // whose name holds white space is refused before any file is opened.  per_bucket[b] (b < cap) = records written.
 template <typename PathOf>
-std::vector<int32_t> emit_umis(Ctx* c, const std::vector<uint8_t>& raw, const std::vector<int64_t>& roff,
+std::vector<int32_t> emit_umis(Ctx* c, const RawBuf& raw, const std::vector<int64_t>& roff,
                                const uint8_t* d_raw, const int64_t* d_roff, const int8_t* d_cls, DevBuf<int64_t>& d_pos,
                                const std::vector<int8_t>& cls, const std::vector<int32_t>& bkt, int64_t stop,
                                const UmiArgs& u, const ExtractPatterns& P, PathOf path_of, int64_t* per_bucket,
@@ -176,8 +291,12 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
     if (!bam_file || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
         !counts || ncluster_cap < 0 || (ncluster_cap > 0 && !reads_per_cluster))
       c->fail(UMICLUST_EINVAL, "bad argument");
-    std::vector<uint8_t> raw;
-    if (!io::inflate_bgzf(bam_file, raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    // the file inflated on the device: raw there (d_raw) and on the host
+    RawBuf raw;
+    DevBuf<uint8_t> d_raw;
+    int64_t inflate_info[3];
+    if (!read_bam_on_device(c, bam_file, raw, d_raw, inflate_info, nullptr))
+      c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
     // header: text, then the reference names, matched to the regions of the reference FASTA
     bam::Header hdr;
     std::string herr;
@@ -201,15 +320,12 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
     // the kernels index each record by its own l_read_name, n_cigar_op and l_seq
     if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
     const int64_t n = (int64_t)roff.size();
-    // device: classify every record
-    DevBuf<uint8_t> d_raw;
+    // device: classify every record where the decoder wrote it
     DevBuf<int64_t> d_roff, d_rlen, d_outlen, d_pos;
     DevBuf<int32_t> d_rclu, d_clu;
     DevBuf<int8_t> d_cls;
-    c->hip(d_raw.ensure(raw.size() + 1), "alloc");
     alloc_each(c, (size_t)n + 1, d_roff, d_cls, d_clu, d_outlen, d_pos);
     alloc_each(c, (size_t)nref + 1, d_rlen, d_rclu);
-    c->hip(hipMemcpyAsync(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
     if (n) c->hip(hipMemcpyAsync(d_roff.p, roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
     if (nref) {
       c->hip(hipMemcpyAsync(d_rlen.p, rlen.data(), (size_t)nref * 8, hipMemcpyHostToDevice, c->st), "h2d");
@@ -300,6 +416,33 @@ int64_t umiclust_region_split_extract(umiclust_ctx* ctx, const char* bam_file, i
                            umis_per_cluster, ncluster_cap, region_detected, missing_name, missing_cap);
 }
 
+// ---------------------------------------------------------------- k_bgzf_inflate alone (kernel-level entry point, §9e)
+int64_t umiclust_bgzf_inflate(umiclust_ctx* ctx, const uint8_t* file, int64_t n, uint8_t* out, int64_t cap,
+                              int32_t* block_status, int64_t* n_blocks, double* times) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    if (n < 0 || (n > 0 && !file)) c->fail(UMICLUST_EINVAL, "bad argument");
+    BgzfPlan P;
+    if (!bgzf_plan(file, (size_t)n, P)) c->fail(UMICLUST_EFORMAT, "malformed BGZF framing");
+    if (n_blocks) *n_blocks = P.n_blocks;
+    if (cap == 0) return P.total;
+    if (!out || cap < P.total)
+      c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)P.total);
+    DevBuf<uint8_t> d_raw;
+    std::vector<int32_t> status;
+    bgzf_inflate_device(c, file, (size_t)n, P, d_raw, status, [&]() { return out; }, times);
+    if (block_status) {
+      std::fill(block_status, block_status + P.n_blocks, 0);
+      for (size_t b = 0; b < status.size(); b++) block_status[P.file_idx[b]] = status[b];
+    }
+    for (size_t b = 0; b < status.size(); b++)
+      if (status[b])
+        c->fail(UMICLUST_EFORMAT, "BGZF block %lld: %s (class %d)", (long long)P.file_idx[b],
+                inf::status_name(status[b]), status[b]);
+    return P.total;
+  });
+}
+
 // ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
 int64_t umiclust_bam_open(umiclust_ctx* ctx, const char* bam_file, int32_t hash_bits) {
   uc::Ctx* c = uc::core(ctx);
@@ -307,9 +450,12 @@ int64_t umiclust_bam_open(umiclust_ctx* ctx, const char* bam_file, int32_t hash_
     if (!bam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
     c->bs = BamSession();
     BamSession S;
+    DevBuf<uint8_t> d_raw, d_nmp;
     const double t0 = now_s();
-    if (!io::inflate_bgzf(bam_file, S.raw)) c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
-    S.t_inflate = now_s() - t0;
+    double t_upload = 0;
+    if (!read_bam_on_device(c, bam_file, S.raw, d_raw, S.inflate_info, &t_upload))
+      c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    S.t_inflate = now_s() - t0;  // from mapping the file until raw is on the host
     std::string herr;
     if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
     if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
@@ -317,26 +463,23 @@ int64_t umiclust_bam_open(umiclust_ctx* ctx, const char* bam_file, int32_t hash_
     const int64_t n = (int64_t)S.roff.size();
     uint64_t m = 1024;
     while (m < 2 * (uint64_t)n) m <<= 1;
-    DevBuf<uint8_t> d_raw, d_nmp;
     DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
     DevBuf<int32_t> d_ref, d_lseq, d_cslen;
     DevBuf<int8_t> d_cls, d_bad;
     DevBuf<uint64_t> d_hash;
     DevBuf<unsigned long long> d_keys, d_rep;
     DevBuf<uint32_t> d_cnt, d_coll;
-    c->hip(d_raw.ensure(S.raw.size() + 1), "alloc");
     alloc_each(c, (size_t)n + 1, d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot, d_ref, d_lseq, d_cslen, d_cls, d_bad,
                d_nmp, d_hash);
     alloc_each(c, (size_t)m, d_keys, d_rep, d_cnt);
     c->hip(d_coll.ensure(1), "alloc");
     float ms = 0.f;
     c->hip(hipEventRecord(c->ev0, c->st), "event");
-    c->hip(hipMemcpyAsync(d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
     if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
     c->hip(hipEventRecord(c->ev1, c->st), "event");
     c->hip(hipEventSynchronize(c->ev1), "sync");
     c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-    S.t_h2d = ms * 1e-3;
+    S.t_h2d = t_upload + ms * 1e-3;  // the compressed bytes and roff
     const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
                         d_bad.p};
     // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
@@ -423,6 +566,16 @@ int32_t umiclust_bam_times(umiclust_ctx* ctx, double* out) {
     auto& S = *bam_session(c);
     if (!out) c->fail(UMICLUST_EINVAL, "null argument");
     out[0] = S.t_inflate, out[1] = S.t_h2d, out[2] = S.t_dev;
+    return UMICLUST_OK;
+  });
+}
+
+int32_t umiclust_bam_inflate_info(umiclust_ctx* ctx, int64_t* out) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!out) c->fail(UMICLUST_EINVAL, "null argument");
+    for (int x = 0; x < 3; x++) out[x] = S.inflate_info[x];
     return UMICLUST_OK;
   });
 }

@@ -357,8 +357,35 @@ void revcomp_ref(const char* s, size_t n, std::string& out) {
   }
 }
 
-// BGZF (SAM/BAM specification §4.1): gzip members with a BC extra field holding BSIZE; every block is
-// inflated independently, so the blocks are split over the host threads
+// BGZF (SAM/BAM specification §4.1): gzip members with a BC extra field holding BSIZE.  The framing walk: offset,
+// size and ISIZE of every block of d[0 .. N); false for a member that is no BGZF block, that passes the end, or that
+// is too small for its own header and trailer, and for bytes after the last whole block
+bool bgzf_blocks(const uint8_t* d, size_t N, std::vector<size_t>& boff, std::vector<size_t>& bsz,
+                 std::vector<uint32_t>& isz) {
+  boff.clear(), bsz.clear(), isz.clear();
+  size_t o = 0;
+  while (o + 18 <= N) {
+    if (d[o] != 31 || d[o + 1] != 139 || d[o + 2] != 8 || !(d[o + 3] & 4)) return false;
+    const size_t xlen = (size_t)d[o + 10] | ((size_t)d[o + 11] << 8);
+    if (o + 12 + xlen > N) return false;
+    size_t bs = 0;
+    for (size_t x = o + 12; x + 4 <= o + 12 + xlen;) {
+      const size_t sl = (size_t)d[x + 2] | ((size_t)d[x + 3] << 8);
+      if (d[x] == 66 && d[x + 1] == 67 && sl == 2 && x + 6 <= o + 12 + xlen)
+        bs = ((size_t)d[x + 4] | ((size_t)d[x + 5] << 8)) + 1;
+      x += 4 + sl;
+    }
+    if (!bs || o + bs > N || bs < 12 + xlen + 8) return false;
+    boff.push_back(o);
+    bsz.push_back(bs);
+    isz.push_back((uint32_t)d[o + bs - 4] | ((uint32_t)d[o + bs - 3] << 8) | ((uint32_t)d[o + bs - 2] << 16) |
+                  ((uint32_t)d[o + bs - 1] << 24));
+    o += bs;
+  }
+  return o == N;
+}
+
+// every block is inflated independently, so the blocks are split over the host threads
 bool inflate_bgzf(const char* path, std::vector<uint8_t>& raw) {
   int fd = open(path, O_RDONLY);
   if (fd < 0) return false;
@@ -374,25 +401,7 @@ bool inflate_bgzf(const char* path, std::vector<uint8_t>& raw) {
   const uint8_t* d = (const uint8_t*)map;
   std::vector<size_t> boff, bsz;
   std::vector<uint32_t> isz;
-  size_t o = 0;
-  bool ok = true;
-  while (o + 18 <= N) {
-    if (d[o] != 31 || d[o + 1] != 139 || d[o + 2] != 8 || !(d[o + 3] & 4)) { ok = false; break; }
-    const size_t xlen = (size_t)d[o + 10] | ((size_t)d[o + 11] << 8);
-    size_t bs = 0;
-    for (size_t x = o + 12; x + 4 <= o + 12 + xlen;) {
-      const size_t sl = (size_t)d[x + 2] | ((size_t)d[x + 3] << 8);
-      if (d[x] == 66 && d[x + 1] == 67 && sl == 2) bs = ((size_t)d[x + 4] | ((size_t)d[x + 5] << 8)) + 1;
-      x += 4 + sl;
-    }
-    if (!bs || o + bs > N) { ok = false; break; }
-    boff.push_back(o);
-    bsz.push_back(bs);
-    isz.push_back((uint32_t)d[o + bs - 4] | ((uint32_t)d[o + bs - 3] << 8) | ((uint32_t)d[o + bs - 2] << 16) |
-                  ((uint32_t)d[o + bs - 1] << 24));
-    o += bs;
-  }
-  if (ok && o != N) ok = false;
+  bool ok = bgzf_blocks(d, N, boff, bsz, isz);
   std::vector<size_t> uo(boff.size() + 1, 0);
   for (size_t b = 0; b < boff.size(); b++) uo[b + 1] = uo[b] + isz[b];
   if (ok) {

@@ -145,6 +145,13 @@ LenSort sort_by_length(const uint32_t* rec_len, const int64_t* bin_in, int32_t n
 
 // BGZF (SAM/BAM specification §4.1) inflated on the host threads
 bool inflate_bgzf(const char* path, std::vector<uint8_t>& raw);
+// the framing walk of inflate_bgzf on d[0 .. N): per block its offset, its size (BSIZE + 1) and its ISIZE; false for
+// a member without the BC field, a block past the end or smaller than its own framing, or a trailing partial block.
+// A tightening of the loop it was factored out of, and so of inflate_bgzf: XLEN is checked against N, the BC subfield
+// must lie inside the extra field, and BSIZE + 1 >= 12 + XLEN + 8 -- the cases in which that loop read past the file
+// or handed zlib an underflowed length; every file it walked within bounds is walked as before
+bool bgzf_blocks(const uint8_t* d, size_t N, std::vector<size_t>& boff, std::vector<size_t>& bsz,
+                 std::vector<uint32_t>& isz);
 
 // the reference's string helpers
 struct Sv {

@@ -5,7 +5,7 @@
 // hot path: every BAM record is classified (unmapped / secondary or supplementary / too short an overlap /
 // too long / kept) and every kept read is written to region_cluster<k>.fasta as
 // `>{query_name};strand={+|-}` + its forward sequence (pysam get_forward_sequence: reverse-complemented for
-// reverse-strand records).  The host inflates the BGZF blocks on all its threads and finds the record
+// reverse-strand records).  The BGZF blocks are inflated on the device (bgzf.hip) and the host finds the record
 // offsets; on the device one thread per record decodes the fixed fields and the CIGAR (reference_length =
 // M/D/N/=/X lengths) and classifies it, and one wave per kept record writes its FASTA bytes -- the 4-bit
 // sequence decoded (and reverse-complemented) lane-parallel -- at its slot in a cluster-grouped output

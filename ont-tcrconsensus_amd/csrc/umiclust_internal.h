@@ -329,4 +329,17 @@ hipError_t launch_split_cols(const BamScanCols& o, const uint8_t* raw, const int
 hipError_t launch_name_suffix(const uint8_t* raw, const int64_t* roff, int64_t n, int64_t* value, uint8_t* status,
                               hipStream_t st);
 
+// ---- BGZF blocks inflated on the device (bgzf.hip) ----
+struct BgzfBlock {   // one entry per block with ISIZE > 0, built by the host from the framing walk
+  int64_t in_off;    // the DEFLATE payload in the compressed buffer
+  int64_t out_off;   // the block's first byte in the inflated buffer (the sum of the ISIZEs before it)
+  uint32_t in_len;
+  uint32_t isize;
+};
+// One wave per block: out[out_off, + isize) and status[b] = an inf:: status of inflate.h (0 = ok).  comp: 4-byte
+// aligned, comp_bytes a multiple of 4 that covers every payload (the bit reader reads whole words below it, none at or
+// past it); the statuses say which blocks' bytes are good.
+hipError_t launch_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, const BgzfBlock* blk, int64_t n, uint8_t* out,
+                               int32_t* status, hipStream_t st);
+
 }  // namespace uc

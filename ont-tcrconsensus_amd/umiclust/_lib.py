@@ -149,6 +149,7 @@ EXPORTS = [
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
+    "umiclust_bgzf_inflate", "umiclust_bam_inflate_info",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -291,6 +292,8 @@ def lib() -> C.CDLL:
     L.umiclust_bam_counts.argtypes = [C.c_void_p, P(C.c_int64)]
     L.umiclust_bam_times.restype = C.c_int32
     L.umiclust_bam_times.argtypes = [C.c_void_p, P(C.c_double)]
+    L.umiclust_bam_inflate_info.restype = C.c_int32
+    L.umiclust_bam_inflate_info.argtypes = [C.c_void_p, P(C.c_int64)]
     L.umiclust_bam_columns.restype = C.c_int32
     L.umiclust_bam_columns.argtypes = [C.c_void_p, P(C.c_int8), P(C.c_int32), P(C.c_int32), P(C.c_int64), P(C.c_int64),
                                        P(C.c_int64), P(C.c_uint8), P(C.c_int32)]
@@ -314,6 +317,9 @@ def lib() -> C.CDLL:
                                              P(C.c_int64), P(C.c_int64), P(C.c_uint8), C.c_char_p, C.c_int32]
     L.umiclust_bam_name_suffix.restype = C.c_int32
     L.umiclust_bam_name_suffix.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_uint8)]
+    L.umiclust_bgzf_inflate.restype = C.c_int64
+    L.umiclust_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int32),
+                                        P(C.c_int64), P(C.c_double)]
     L.umiclust_bam_close.restype = C.c_int32
     L.umiclust_bam_close.argtypes = [C.c_void_p]
     _lib = L
@@ -696,6 +702,35 @@ class Context:
         self._check(lib().umiclust_bam_open(self._h, os.fspath(bam_file).encode(), hash_bits), "bam_open")
         return BamSession(self)
 
+    def bgzf_inflate(self, data, want_status: bool = False):
+        """umiclust_bgzf_inflate: the BGZF byte string `data` inflated on the device, as a uint8 array.
+        want_status: returns (bytes, status, error) instead -- one int32 per block (0 = ok, else the decoder's error
+        class) and None or, where a block was refused, the UmiclustError (EFORMAT, naming the first such block) that
+        the plain call raises; the bytes of every good block are in place either way.  Malformed framing raises."""
+        L = lib()
+        src = np.frombuffer(data, np.uint8)
+        nblk = C.c_int64(-1)
+        size = self._check(L.umiclust_bgzf_inflate(self._h, src.ctypes.data, len(src), None, 0, None, C.byref(nblk),
+                                                   None), "bgzf_inflate")
+        out, status, times = np.zeros(max(size, 1), np.uint8), np.zeros(max(nblk.value, 1), np.int32), np.zeros(3)
+        rc = L.umiclust_bgzf_inflate(self._h, src.ctypes.data, len(src), out.ctypes.data, len(out),
+                                     status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nblk),
+                                     times.ctypes.data_as(C.POINTER(C.c_double)))
+        self.bgzf_times = {"h2d_s": float(times[0]), "kernel_s": float(times[1]), "d2h_s": float(times[2])}
+        out, status = out[:size], status[:nblk.value]
+        if not want_status:
+            self._check(rc, "bgzf_inflate")
+            return out
+        err = None
+        if rc < 0:
+            try:
+                self._check(rc, "bgzf_inflate")
+            except UmiclustError as e:
+                if e.code != -74 or not status.any():
+                    raise
+                err = e
+        return out, status, err
+
     def align_pairs(self, p: Params, queries, targets, with_ops: bool = False) -> dict:
         qb, qo = _pack(queries)
         tb, to = _pack(targets)
@@ -895,6 +930,13 @@ class BamSession:
                              "bam_strings")
         raw = buf.tobytes()
         return [raw[off[x]:off[x + 1]].decode("ascii") for x in range(m)]
+
+    def inflate_info(self) -> tuple:
+        """umiclust_bam_inflate_info: (BGZF blocks, blocks inflated on the device, compressed bytes uploaded) of the
+        open."""
+        out = np.zeros(3, np.int64)
+        self._ctx._check(lib().umiclust_bam_inflate_info(self._ctx._h, _i64(out)), "bam_inflate_info")
+        return tuple(int(x) for x in out)
 
     def query_names(self, idx) -> list:
         return self._strings(0, idx)

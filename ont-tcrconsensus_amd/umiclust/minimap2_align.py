@@ -4,8 +4,8 @@ count_cs_tags (:21-37), the cs-tag log blocks of minimap2_ont_align (:141-150), 
 filter_consensus_alignments_and_split, which runs the filter and the round-2 split of region_split.py:336-435 on one
 session.
 
-The BAM is read once by a session of the library (umiclust_bam_open: BGZF inflated on the host threads, every
-record scanned and the cs:Z strings grouped exactly on the GPU); this module only forms the reference's floats and
+The BAM is read once by a session of the library (umiclust_bam_open: BGZF inflated on the device, DESIGN.md §9e,
+every record scanned and the cs:Z strings grouped exactly on the GPU); this module only forms the reference's floats and
 text from the integer columns, with the same Python and numpy expressions as the reference, so values and their
 repr are equal by construction.  It needs numpy only (no pysam, no pandas).  No CPU fallback: the columns come from
 the device, or -- in the CPU tests -- from any object with the attributes of _lib.BamSession.

@@ -3,8 +3,8 @@
 
 Same signature, defaults, files (append-mode region_cluster<k>.fasta, the
 <bam>_filter_and_split_reads_by_region_cluster.err log) and return value (the list of cluster FASTA paths, a
-set's order).  The BAM record loop runs in the library (umiclust_region_split: BGZF inflated on the host
-threads, records classified and FASTA records built on the GPU); the log is formatted here with the same
+set's order).  The BAM record loop runs in the library (umiclust_region_split: BGZF inflated on the device, DESIGN.md
+§9e, records classified and FASTA records built on the GPU); the log is formatted here with the same
 Python expressions as the reference.  No CPU fallback.
 
 Also the round-2 function of the same file, filter_and_split_reads_by_region (:336-435, row f4b): one

@@ -1,6 +1,7 @@
-"""Measurement tool for DESIGN.md §9b (row f6): the device time of scan + group + verify (HIP events, through
-umiclust_bam_times) and the host inflate time of a BAM session on a seeded synthetic BAM, next to a device-to-device
-copy of the same inflated bytes timed in the same process.  Not a gate and not part of bench.py.
+"""Measurement tool for DESIGN.md §9b and §9e (row f6): the device time of scan + group + verify (HIP events, through
+umiclust_bam_times), the inflate time and the wall time of umiclust_bam_open on a seeded synthetic BAM, next to a
+device-to-device copy of the same inflated bytes timed in the same process; where the library has it, the BGZF inflate
+kernel alone (umiclust_bgzf_inflate, HIP events) and the session's inflate_info.  Not a gate and not part of bench.py.
 
     python tools/bam_scan_bench.py [records = 200000] [--out DIR]
 
@@ -71,9 +72,15 @@ def main():
     from umiclust import _lib
     ctx = _lib.Context(0)
     runs = []
+    opens = []
     for _ in range(5):
-        with ctx.bam_open(path) as s:
+        t1 = time.perf_counter()
+        ctx._check(_lib.lib().umiclust_bam_open(ctx._h, path.encode(), 64), "bam_open")
+        opens.append(time.perf_counter() - t1)  # the C call alone: the first open is the warm-up
+        with _lib.BamSession(ctx) as s:
             runs.append(dict(s.times))
+            if hasattr(s, "inflate_info"):
+                res["inflate_info"] = s.inflate_info()
             res["groups"], res["reruns"] = s.n_cs_groups, s.n_hash_reruns
             t1 = time.time()
             k = s.write((s.cls == 2).astype("uint8"), os.path.join(out, "synth_filtered.bam"))
@@ -89,8 +96,21 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         copies.append(e0.elapsed_time(e1) * 1e-3)
+    if hasattr(ctx, "bgzf_inflate"):  # the kernel alone, on the same file
+        data, k = open(path, "rb").read(), []
+        for _ in range(5):
+            ctx.bgzf_inflate(data)
+            k.append(dict(ctx.bgzf_times))
+        res["bgzf_kernel_s_runs"] = [r["kernel_s"] for r in k]
+        res["bgzf_kernel_s"] = statistics.median(r["kernel_s"] for r in k[1:])
+        res["bgzf_h2d_s"] = statistics.median(r["h2d_s"] for r in k[1:])
+        res["bgzf_d2h_s"] = statistics.median(r["d2h_s"] for r in k[1:])
     os.remove(path)
     warm = runs[1:]
+    res["open_s_runs"] = opens
+    res["open_s"] = statistics.median(opens[1:])
+    res["open_s_spread"] = max(opens[1:]) - min(opens[1:])
+    res["inflate_s_runs"] = [r["inflate_s"] for r in runs]
     res["device_s_runs"] = [r["device_s"] for r in runs]
     res["device_s"] = statistics.median(r["device_s"] for r in warm)
     res["inflate_s"] = statistics.median(r["inflate_s"] for r in warm)
