@@ -511,6 +511,50 @@ int64_t umiclust_bam_split_extract(umiclust_ctx *ctx, const uint8_t *keep, int32
 int32_t umiclust_bam_name_suffix(umiclust_ctx *ctx, int64_t *value, uint8_t *status);
 int32_t umiclust_bam_close(umiclust_ctx *ctx);
 
+/* ---- a BAM session straight from SAM text, sorted on the device (added functions, ABI version
+ * unchanged) ---- */
+/* Replaces `samtools sort` and the read-back of its file in minimap2_ont_align (ont_tcr_consensus/minimap2_align.py
+ * :133-137, and the count_cs_tags open of :140): sam_file is what `minimap2 -a` writes (:88-132).  A regular file is
+ * mapped; any other readable path (a FIFO, /dev/fd/N) is read to its end, so minimap2 can stream into the call.  The
+ * device splits the text into lines, parses every field, encodes the BAM records and sorts them stably by (refID as
+ * unsigned, pos + 1, flag & 0x10) -- samtools' coordinate order, ties in input order; the host edits the header (@HD
+ * SO:coordinate, GO: dropped, an @HD line added where there is none, no @PG) and parses the aux f values.  The session
+ * is then exactly the one umiclust_bam_open builds from the sorted BAM: every umiclust_bam_* call works on it, and
+ * umiclust_bam_write with every record kept is the drop-in for `samtools sort -o`.  `samtools index` (:138) and
+ * `samtools flagstat` (:152-153) are not replaced: a caller that wants them writes the BAM.
+ * The rules (csrc/sam_text.h, policy O9) restate htslib's sam_parse1; every refusal names the 1-based line and the
+ * field, and leaves no session: UMICLUST_EFORMAT for a malformed header or line (fewer than 11 fields, an empty line,
+ * a name over 254 bytes, an unknown RNAME / RNEXT -- named --, a malformed number or CIGAR, QUAL and SEQ of different
+ * lengths, an aux type outside A i f Z H), UMICLUST_ERANGE for more than 65535 CIGAR operations, UMICLUST_EIO for a
+ * path that cannot be read, UMICLUST_ENOMEM when the text and the records do not fit the device together.
+ * Memory model: umiclust_bam_open's, with the text in place of the compressed file.  hash_bits: as umiclust_bam_open.
+ * Returns the number of records. */
+int64_t umiclust_sam_open(umiclust_ctx *ctx, const char *sam_file, int32_t hash_bits);
+/* DIAGNOSTIC of a session that umiclust_sam_open made (UMICLUST_ESTATE for any other): out[0..3] = lines (header
+ * included), records, text bytes uploaded, aux f values parsed on the host; times[0..4] = seconds by HIP events of the
+ * upload, lines + measure, sort, encode, copy back.  Either may be NULL.  umiclust_bam_inflate_info reports 0, 0, 0
+ * for such a session.  tools/sam_sort_bench.py reads the figures of DESIGN.md §9f through it */
+int32_t umiclust_sam_info(umiclust_ctx *ctx, int64_t *out, double *times);
+/* umiclust_region_split and umiclust_region_split_extract on the open session instead of a file (replacing the second
+ * open of the raw-read BAM by filter_and_split_reads_by_region_cluster, region_split.py:219-333, after
+ * minimap2_align.py:140 has read it once): no bam_file argument; the other arguments, the counters, the files, the
+ * KeyError with its name, the white-space refusal and the error codes are theirs.  The session's raw bytes are
+ * uploaded for the call, as umiclust_bam_split does, and the session stays open.  UMICLUST_ESTATE without one. */
+int64_t umiclust_bam_region_split(umiclust_ctx *ctx, int32_t nregions, const char *const *region_names,
+                                  const int64_t *region_lengths, const int32_t *region_clusters,
+                                  double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                  const char *out_dir, int64_t *counts, int64_t *reads_per_cluster,
+                                  int32_t ncluster_cap, uint8_t *region_detected, char *missing_name,
+                                  int32_t missing_cap);
+int64_t umiclust_bam_region_split_extract(umiclust_ctx *ctx, int32_t nregions, const char *const *region_names,
+                                          const int64_t *region_lengths, const int32_t *region_clusters,
+                                          double minimal_region_overlap, int32_t max_softclip_5_end,
+                                          int32_t max_softclip_3_end, int32_t adapter_length_5_end,
+                                          int32_t adapter_length_3_end, int32_t max_pattern_dist, const char *umi_fwd,
+                                          const char *umi_rev, const char *umi_out_dir, int64_t *counts,
+                                          int64_t *reads_per_cluster, int64_t *umis_per_cluster, int32_t ncluster_cap,
+                                          uint8_t *region_detected, char *missing_name, int32_t missing_cap);
+
 /* ---- kernel-level entry points (parity tests) ---- */
 /* The quality kernel alone: record i = quals[offsets[i] .. offsets[i+1]); ee_fx[i] = sum over its bytes b with
  * 0 <= b - fastq_ascii <= 93 of llrint(10^(-(b - fastq_ascii)/10) * 2^40) (other bytes add 0), qlo[i] / qhi[i] = its

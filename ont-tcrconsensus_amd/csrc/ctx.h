@@ -166,6 +166,11 @@ struct BamSession {
   int64_t n_reruns = 0, first_bad = -1;
   int64_t inflate_info[3] = {0, 0, 0};  // BGZF blocks, blocks inflated on the device, compressed bytes uploaded
   double t_inflate = 0, t_h2d = 0, t_dev = 0;
+  // a session opened from SAM text (umiclust_sam_open): lines, records, text bytes uploaded, aux f
+  // values the host parsed; seconds of upload, lines + measure, sort, encode, copy back
+  bool from_sam = false;
+  int64_t sam_info[4] = {0, 0, 0, 0};
+  double sam_times[5] = {0, 0, 0, 0, 0};
 };
 
 struct Ctx {

@@ -2,7 +2,10 @@
 // cs group-by and writer (§8f f6, DESIGN.md §9b, bamscan.hip), and on the session the round-2 region split and the
 // name suffix (§8f f4b / f6b, DESIGN.md §9c, bamsplit.hip), and on both readers the region split fused with the UMI
 // extraction (§8f f4+f1, DESIGN.md §9d, bamextract.hip).  Both readers inflate the file on the device (DESIGN.md §9e,
-// bgzf.hip on inflate.h), which umiclust_bgzf_inflate runs alone.  Their HIP-free halves are in bam_host.h.
+// bgzf.hip on inflate.h), which umiclust_bgzf_inflate runs alone.  Their HIP-free halves are in bam_host.h.  The
+// session also opens from SAM text, parsed, encoded and coordinate-sorted on the device (samsort.hip on
+// sam_text.h), and the round-1 split then runs on it (umiclust_bam_region_split[_extract]).
+#include <errno.h>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -17,6 +20,7 @@
 
 #include "ctx.h"
 #include "inflate.h"
+#include "sam_text.h"
 
 using namespace uc;
 using namespace uc::io;
@@ -91,6 +95,20 @@ void bgzf_inflate_device(Ctx* c, const uint8_t* d, size_t N, const BgzfPlan& P, 
     for (int x = 0; x < 3; x++) times[x] = elapsed_s(c, e[x], e[x + 1]);
 }
 
+// raw sized to `bytes` with its pages touched by the I/O threads (first touch is the cost of a fresh array this size,
+// and one thread takes several times the inflate kernel's time over it)
+uint8_t* alloc_touched(RawBuf& raw, size_t bytes) {
+  raw.alloc(bytes);
+  uint8_t* const p = raw.data();
+  const size_t n = raw.size(), page = 4096;
+  const int T = std::max(1, std::min<int>(io_threads(), (int)(n >> 22)));
+  parallel_for(T, [&](int th) {
+    const size_t lo = n / (size_t)T * (size_t)th, hi = th + 1 == T ? n : n / (size_t)T * (size_t)(th + 1);
+    for (size_t o = lo; o < hi; o += page) p[o] = 0;
+  });
+  return p;
+}
+
 // What both BAM readers start with: the file mapped and its block table built, the compressed bytes uploaded, the
 // blocks inflated into d_raw, and `raw` copied back to the host, where the header parser, record_offsets, the session
 // and the writer read it.  info: BGZF blocks, blocks inflated on the device, compressed bytes uploaded; *t_upload:
@@ -123,25 +141,184 @@ bool read_bam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_t>& 
   if (!bgzf_plan((const uint8_t*)map.p, map.n, P)) return false;
   std::vector<int32_t> status;
   double t[3] = {0, 0, 0};
-  // while the device inflates: the host's array, its pages touched by the I/O threads (first touch is the cost of
-  // a fresh array this size, and one thread takes several times the kernel's time over it)
-  const auto host_dst = [&]() {
-    raw.alloc((size_t)P.total);
-    uint8_t* const p = raw.data();
-    const size_t n = raw.size(), page = 4096;
-    const int T = std::max(1, std::min<int>(io_threads(), (int)(n >> 22)));
-    parallel_for(T, [&](int th) {
-      const size_t lo = n / (size_t)T * (size_t)th, hi = th + 1 == T ? n : n / (size_t)T * (size_t)(th + 1);
-      for (size_t o = lo; o < hi; o += page) p[o] = 0;
-    });
-    return p;
-  };
+  // while the device inflates: the host's array, its pages touched by the I/O threads
+  const auto host_dst = [&]() { return alloc_touched(raw, (size_t)P.total); };
   bgzf_inflate_device(c, (const uint8_t*)map.p, map.n, P, d_raw, status, host_dst, t);
   info[0] = P.n_blocks, info[1] = (int64_t)P.blk.size(), info[2] = (int64_t)map.n;
   if (t_upload) *t_upload = t[0];
   for (int32_t s : status)
     if (s) return false;
   return true;
+}
+
+// ---- SAM text to raw on the device (samsort.hip on sam_text.h)
+// The bytes of `path`: a regular file is mapped, any other readable path (a FIFO, /dev/fd/N) is read to its end.
+struct TextInput {
+  void* map = nullptr;
+  size_t map_n = 0;
+  std::vector<uint8_t> buf;
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+  ~TextInput() {
+    if (map) munmap(map, map_n);
+  }
+  bool read(const char* path) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return false;
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) return close(fd), false;
+    if (S_ISREG(sb.st_mode)) {
+      map_n = (size_t)sb.st_size;
+      if (map_n) map = mmap(nullptr, map_n, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+      close(fd);
+      if (map == MAP_FAILED) return map = nullptr, false;
+      p = (const uint8_t*)map, n = map_n;
+      return true;
+    }
+    for (size_t have = 0;;) {
+      if (buf.size() - have < (1u << 20)) buf.resize(std::max<size_t>(buf.size() * 2, 1u << 22));
+      const ssize_t k = ::read(fd, buf.data() + have, buf.size() - have);
+      if (k < 0 && errno == EINTR) continue;
+      if (k < 0) return close(fd), false;
+      if (k == 0) {
+        n = have;
+        break;
+      }
+      have += (size_t)k;
+    }
+    close(fd);
+    p = buf.data();
+    return true;
+  }
+};
+
+// The sibling of read_bam_on_device for SAM text: the text uploaded, its lines split, measured, sorted and encoded on
+// the device into d_raw -- the BAM header the host built, then the records in coordinate order -- and `raw` copied back
+// to the host.  Text and raw are both on the device until this returns.  info: lines (header included), records, text
+// bytes uploaded, aux f values the host parsed; times: upload, lines + measure, sort, encode, copy back in seconds by
+// HIP events.  Fails the context: UMICLUST_EIO for a path that cannot be read, UMICLUST_EFORMAT / UMICLUST_ERANGE for
+// a refused header or line (named), UMICLUST_ENOMEM for a device allocation that fails.
+void read_sam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_t>& d_raw, int64_t info[4],
+                        double times[5]) {
+  TextInput in;
+  if (!in.read(path)) c->fail(UMICLUST_EIO, "cannot read SAM %s", path);
+  sam::Header H;
+  std::string herr;
+  if (!sam::build_header(in.p, in.n, H, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", path, herr.c_str());
+  sam::NameTable T;
+  T.build(H.ref_name);
+  const uint8_t* const body = in.p + H.body;
+  const int64_t N = (int64_t)(in.n - H.body), hdr_len = (int64_t)H.bam.size();
+  const auto dev = [&](hipError_t e) {
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      c->fail(UMICLUST_ENOMEM, "device allocation failed");
+    }
+    c->hip(e, "alloc");
+  };
+  const auto h2d = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes) c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->st), "h2d");
+  };
+  const auto d2h = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes) c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
+  };
+  Event e[6];
+  const auto mark = [&](int k) { c->hip(hipEventRecord(e[k].get(c), c->st), "event"); };
+  // upload: the text after the header and the name table
+  DevBuf<uint8_t> d_text, d_nbytes;
+  DevBuf<int32_t> d_noff, d_nslot;
+  dev(d_text.ensure((size_t)N + 1)), dev(d_nbytes.ensure(T.bytes.size())), dev(d_noff.ensure(T.off.size()));
+  dev(d_nslot.ensure(T.slot.size()));
+  mark(0);
+  h2d(d_text.p, body, (size_t)N), h2d(d_nbytes.p, T.bytes.data(), T.bytes.size());
+  h2d(d_noff.p, T.off.data(), T.off.size() * 4), h2d(d_nslot.p, T.slot.data(), T.slot.size() * 4);
+  const sam::Names names{d_nbytes.p, d_noff.p, d_nslot.p, T.mask, (int32_t)H.ref_name.size()};
+  mark(1);
+  // lines
+  int64_t n = 0;
+  DevBuf<int64_t> d_cnt, d_first, d_start, d_one;
+  dev(d_one.ensure(1));
+  if (N > 0) {
+    const size_t nc = (size_t)sam_line_chunks(N);
+    dev(d_cnt.ensure(nc)), dev(d_first.ensure(nc));
+    c->hip(launch_sam_count_lines(d_text.p, N, d_cnt.p, d_first.p, d_one.p, c->st), "sam lines");
+    d2h(&n, d_one.p, 8);
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    n += 1;
+    if (n > INT32_MAX) c->fail(UMICLUST_ERANGE, "%s: more than 2^31 - 1 lines", path);
+    dev(d_start.ensure((size_t)n + 1));
+    c->hip(launch_sam_scatter_lines(d_text.p, N, d_first.p, n, d_start.p, c->st), "sam lines");
+  }
+  // measure: per line the field table, size, key and status
+  const int64_t nb = (n + 255) / 256;
+  DevBuf<sam::Fields> d_fields;
+  DevBuf<int64_t> d_size, d_roff, d_hist;
+  DevBuf<uint64_t> d_key, d_key2, d_acc;
+  DevBuf<uint32_t> d_idx, d_idx2;
+  DevBuf<int32_t> d_status;
+  dev(d_fields.ensure((size_t)n)), dev(d_size.ensure((size_t)n)), dev(d_roff.ensure((size_t)n));
+  dev(d_hist.ensure((size_t)nb * 256)), dev(d_key.ensure((size_t)n)), dev(d_key2.ensure((size_t)n));
+  dev(d_acc.ensure(4)), dev(d_idx.ensure((size_t)n)), dev(d_idx2.ensure((size_t)n)), dev(d_status.ensure((size_t)n));
+  uint64_t acc[4] = {~0ull, 0, 0, 0};  // first refused line, OR of the keys, aux f values, slots appended by encode
+  h2d(d_acc.p, acc, sizeof(acc));
+  c->hip(launch_sam_measure(d_text.p, d_start.p, n, names, d_fields.p, d_size.p, d_key.p, d_status.p, d_acc.p, c->st),
+         "sam measure");
+  d2h(acc, d_acc.p, sizeof(acc));
+  mark(2);
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  if (acc[0] != ~0ull) {
+    // the refusal's text comes from the host restatement of the same rules, on that line alone
+    int64_t be[2] = {0, 0};
+    d2h(be, d_start.p + acc[0], 16);
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    int32_t status = 0;
+    const std::string what = sam::describe(body, be[0], be[1] - 1, T.view(), H.lines + (int64_t)acc[0] + 1, &status);
+    c->fail((status & 0xff) == sam::kERange ? UMICLUST_ERANGE : UMICLUST_EFORMAT, "%s: %s", path, what.c_str());
+  }
+  // sort: stable by key
+  const uint32_t* d_order = d_idx.p;
+  c->hip(launch_sam_sort(d_key.p, d_idx.p, d_key2.p, d_idx2.p, n, acc[1], d_hist.p, &d_order, c->st), "sam sort");
+  mark(3);
+  // encode: roff, the header bytes, the records, the f values
+  int64_t total = hdr_len;
+  c->hip(launch_sam_roff(d_size.p, d_order, n, hdr_len, d_roff.p, d_one.p, c->st), "sam roff");
+  d2h(&total, d_one.p, 8);
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  const int64_t nf = (int64_t)acc[2];
+  DevBuf<sam::FSlot> d_slots;
+  dev(d_raw.ensure((size_t)total + 1)), dev(d_slots.ensure((size_t)nf));
+  h2d(d_raw.p, H.bam.data(), H.bam.size());
+  c->hip(launch_sam_encode(d_text.p, d_start.p, d_order, d_roff.p, n, names, d_fields.p, d_size.p, d_raw.p, d_slots.p,
+                           d_acc.p + 3, nf, c->st),
+         "sam encode");
+  DevBuf<int64_t> d_at;
+  DevBuf<uint32_t> d_bits;
+  std::vector<int64_t> at((size_t)nf);
+  std::vector<uint32_t> bits((size_t)nf);
+  if (nf) {
+    std::vector<sam::FSlot> slots((size_t)nf);
+    d2h(slots.data(), d_slots.p, (size_t)nf * sizeof(sam::FSlot)), d2h(acc, d_acc.p, sizeof(acc));
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    if ((int64_t)acc[3] != nf) c->fail(UMICLUST_EDEVICE, "%s: the encode pass listed %lld f values, the measure pass %lld",
+                                       path, (long long)acc[3], (long long)nf);
+    for (int64_t k = 0; k < nf; k++) {
+      uint8_t b[4];
+      if (!sam::float_bytes(body, (size_t)N, slots[k].text, b))
+        c->fail(UMICLUST_EFORMAT, "%s: line %lld: aux: an f value is no number", path,
+                (long long)(H.lines + slots[k].line + 1));
+      at[k] = slots[k].at;
+      memcpy(&bits[k], b, 4);
+    }
+    dev(d_at.ensure((size_t)nf)), dev(d_bits.ensure((size_t)nf));
+    h2d(d_at.p, at.data(), (size_t)nf * 8), h2d(d_bits.p, bits.data(), (size_t)nf * 4);
+    c->hip(launch_sam_put_f(d_raw.p, d_at.p, d_bits.p, nf, c->st), "sam put f");
+  }
+  mark(4);
+  d2h(alloc_touched(raw, (size_t)total), d_raw.p, (size_t)total);
+  mark(5);
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  info[0] = H.lines + n, info[1] = n, info[2] = N, info[3] = nf;
+  for (int x = 0; x < 5; x++) times[x] = elapsed_s(c, e[x], e[x + 1]);
 }
 
 // The text of the kept records among [0, stop), grouped by bucket and in BAM order within a bucket: the slots are laid
@@ -276,9 +453,45 @@ std::vector<int32_t> emit_umis(Ctx* c, const RawBuf& raw, const std::vector<int6
       });
 }
 
+// What the round-1 split reads: the inflated file on the host and on the device, its header and its record offsets.
+// The path-based entries fill it from read_bam_on_device and own what they made; the session entries point into the
+// open session and upload its raw, as umiclust_bam_split does.
+struct SplitSource {
+  const RawBuf* raw = nullptr;
+  const bam::Header* hdr = nullptr;
+  const std::vector<int64_t>* roff = nullptr;
+  const uint8_t* d_raw = nullptr;
+  std::string what;  // the file's name in a refusal
+  RawBuf own_raw;
+  bam::Header own_hdr;
+  std::vector<int64_t> own_roff;
+  DevBuf<uint8_t> own_d_raw;
+
+  void from_path(Ctx* c, const char* bam_file) {
+    // the file inflated on the device: raw there (d_raw) and on the host (DESIGN.md §9e)
+    int64_t inflate_info[3];
+    if (!read_bam_on_device(c, bam_file, own_raw, own_d_raw, inflate_info, nullptr))
+      c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
+    std::string herr;
+    if (!bam::parse_header(own_raw.data(), own_raw.size(), own_hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
+    if (!bam::record_offsets(own_raw.data(), own_raw.size(), own_hdr.end, own_roff, herr))
+      c->fail(UMICLUST_EFORMAT, "truncated BAM record");
+    raw = &own_raw, hdr = &own_hdr, roff = &own_roff, d_raw = own_d_raw.p, what = bam_file;
+  }
+  void from_session(Ctx* c) {
+    const BamSession& S = *bam_session(c);
+    c->hip(own_d_raw.ensure(S.raw.size() + 1), "alloc");
+    if (S.raw.size())
+      c->hip(hipMemcpyAsync(own_d_raw.p, S.raw.data(), S.raw.size(), hipMemcpyHostToDevice, c->st), "h2d");
+    raw = &S.raw, hdr = &S.hdr, roff = &S.roff, d_raw = own_d_raw.p, what = "the BAM session";
+  }
+};
+
 // umiclust_region_split (umi null: region_cluster<k>.fasta in out_dir) and umiclust_region_split_extract (umi set:
-// region_cluster<k>_detected_umis.fasta in out_dir, their record counts in umis_per_cluster)
-int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregions, const char* const* region_names,
+// region_cluster<k>_detected_umis.fasta in out_dir, their record counts in umis_per_cluster); session: the open
+// session is the file and bam_file is not read (umiclust_bam_region_split[_extract])
+int64_t region_split_impl(umiclust_ctx* ctx, bool session, const char* bam_file, int32_t nregions,
+                          const char* const* region_names,
                           const int64_t* region_lengths, const int32_t* region_clusters, double minimal_region_overlap,
                           int32_t max_softclip_5_end, int32_t max_softclip_3_end, const UmiArgs* umi,
                           const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int64_t* umis_per_cluster,
@@ -288,19 +501,20 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
     if (umi && ncluster_cap > 0 && !umis_per_cluster) c->fail(UMICLUST_EINVAL, "bad argument");
     ExtractPatterns pat;
     if (umi) check_umi_args(c, *umi, pat);
-    if (!bam_file || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
+    if ((!session && !bam_file) || !out_dir || nregions < 0 || (nregions > 0 && (!region_names || !region_lengths || !region_clusters)) ||
         !counts || ncluster_cap < 0 || (ncluster_cap > 0 && !reads_per_cluster))
       c->fail(UMICLUST_EINVAL, "bad argument");
-    // the file inflated on the device: raw there (d_raw) and on the host (DESIGN.md §9e)
-    RawBuf raw;
-    DevBuf<uint8_t> d_raw;
-    int64_t inflate_info[3];
-    if (!read_bam_on_device(c, bam_file, raw, d_raw, inflate_info, nullptr))
-      c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
-    // header: text, then the reference names, matched to the regions of the reference FASTA
-    bam::Header hdr;
+    SplitSource src;
+    if (session)
+      src.from_session(c);
+    else
+      src.from_path(c, bam_file);
+    const RawBuf& raw = *src.raw;
+    const bam::Header& hdr = *src.hdr;
+    const std::vector<int64_t>& roff = *src.roff;
+    const uint8_t* const d_raw = src.d_raw;
     std::string herr;
-    if (!bam::parse_header(raw.data(), raw.size(), hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s is not BAM", bam_file);
+    // the reference names of the header, matched to the regions of the reference FASTA
     std::unordered_map<std::string, int32_t> rid;
     for (int32_t r = 0; r < nregions; r++) rid.emplace(region_names[r], r);
     const int32_t nref = (int32_t)hdr.ref_name.size();
@@ -315,10 +529,8 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
         rclu[r] = region_clusters[it->second];
       }
     }
-    std::vector<int64_t> roff;
-    if (!bam::record_offsets(raw.data(), raw.size(), hdr.end, roff, herr)) c->fail(UMICLUST_EFORMAT, "truncated BAM record");
     // the kernels index each record by its own l_read_name, n_cigar_op and l_seq
-    if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+    if (!bam::check_record_fields(raw.data(), roff, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", src.what.c_str(), herr.c_str());
     const int64_t n = (int64_t)roff.size();
     // device: classify every record where the decoder wrote it
     DevBuf<int64_t> d_roff, d_rlen, d_outlen, d_pos;
@@ -331,7 +543,7 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
       c->hip(hipMemcpyAsync(d_rlen.p, rlen.data(), (size_t)nref * 8, hipMemcpyHostToDevice, c->st), "h2d");
       c->hip(hipMemcpyAsync(d_rclu.p, rclu.data(), (size_t)nref * 4, hipMemcpyHostToDevice, c->st), "h2d");
     }
-    c->hip(launch_bam_classify(d_raw.p, d_roff.p, n, nref, d_rlen.p, d_rclu.p, minimal_region_overlap,
+    c->hip(launch_bam_classify(d_raw, d_roff.p, n, nref, d_rlen.p, d_rclu.p, minimal_region_overlap,
                                max_softclip_5_end, max_softclip_3_end, d_cls.p, d_clu.p, d_outlen.p, c->st),
            "bam classify");
     std::vector<int8_t> cls(n);
@@ -358,9 +570,9 @@ int64_t region_split_impl(umiclust_ctx* ctx, const char* bam_file, int32_t nregi
     // (the reference's KeyError ends the pipeline before extract_umis starts: no UMI file then)
     std::vector<int32_t> used;
     if (!umi)
-      used = emit_fasta(c, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, olen, stop, cluster_fasta);
+      used = emit_fasta(c, d_raw, d_roff.p, d_cls.p, d_pos, cls, clu, olen, stop, cluster_fasta);
     else if (stop == n)
-      used = emit_umis(c, raw, roff, d_raw.p, d_roff.p, d_cls.p, d_pos, cls, clu, stop, *umi, pat, cluster_umis,
+      used = emit_umis(c, raw, roff, d_raw, d_roff.p, d_cls.p, d_pos, cls, clu, stop, *umi, pat, cluster_umis,
                        umis_per_cluster, ncluster_cap);
     // counters of the records the reference reached
     int64_t cnt[4] = {0, 0, 0, 0};  // unmapped, primary mapped, short, long
@@ -397,8 +609,8 @@ int64_t umiclust_region_split(umiclust_ctx* ctx, const char* bam_file, int32_t n
                               double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
                               const char* out_dir, int64_t* counts, int64_t* reads_per_cluster, int32_t ncluster_cap,
                               uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
-  return region_split_impl(ctx, bam_file, nregions, region_names, region_lengths, region_clusters, minimal_region_overlap,
-                           max_softclip_5_end, max_softclip_3_end, nullptr, out_dir, counts, reads_per_cluster, nullptr,
+  return region_split_impl(ctx, false, bam_file, nregions, region_names, region_lengths, region_clusters,
+                           minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, nullptr, out_dir, counts, reads_per_cluster, nullptr,
                            ncluster_cap, region_detected, missing_name, missing_cap);
 }
 
@@ -411,9 +623,36 @@ int64_t umiclust_region_split_extract(umiclust_ctx* ctx, const char* bam_file, i
                                       int64_t* reads_per_cluster, int64_t* umis_per_cluster, int32_t ncluster_cap,
                                       uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
   const UmiArgs umi{adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev};
-  return region_split_impl(ctx, bam_file, nregions, region_names, region_lengths, region_clusters, minimal_region_overlap,
-                           max_softclip_5_end, max_softclip_3_end, &umi, umi_out_dir, counts, reads_per_cluster,
+  return region_split_impl(ctx, false, bam_file, nregions, region_names, region_lengths, region_clusters,
+                           minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, &umi, umi_out_dir, counts, reads_per_cluster,
                            umis_per_cluster, ncluster_cap, region_detected, missing_name, missing_cap);
+}
+
+// the same two on the open session: no bam_file, everything else as above
+int64_t umiclust_bam_region_split(umiclust_ctx* ctx, int32_t nregions, const char* const* region_names,
+                                  const int64_t* region_lengths, const int32_t* region_clusters,
+                                  double minimal_region_overlap, int32_t max_softclip_5_end, int32_t max_softclip_3_end,
+                                  const char* out_dir, int64_t* counts, int64_t* reads_per_cluster,
+                                  int32_t ncluster_cap, uint8_t* region_detected, char* missing_name,
+                                  int32_t missing_cap) {
+  return region_split_impl(ctx, true, nullptr, nregions, region_names, region_lengths, region_clusters,
+                           minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, nullptr, out_dir, counts,
+                           reads_per_cluster, nullptr, ncluster_cap, region_detected, missing_name, missing_cap);
+}
+
+int64_t umiclust_bam_region_split_extract(umiclust_ctx* ctx, int32_t nregions, const char* const* region_names,
+                                          const int64_t* region_lengths, const int32_t* region_clusters,
+                                          double minimal_region_overlap, int32_t max_softclip_5_end,
+                                          int32_t max_softclip_3_end, int32_t adapter_length_5_end,
+                                          int32_t adapter_length_3_end, int32_t max_pattern_dist, const char* umi_fwd,
+                                          const char* umi_rev, const char* umi_out_dir, int64_t* counts,
+                                          int64_t* reads_per_cluster, int64_t* umis_per_cluster, int32_t ncluster_cap,
+                                          uint8_t* region_detected, char* missing_name, int32_t missing_cap) {
+  const UmiArgs umi{adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev};
+  return region_split_impl(ctx, true, nullptr, nregions, region_names, region_lengths, region_clusters,
+                           minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, &umi, umi_out_dir, counts,
+                           reads_per_cluster, umis_per_cluster, ncluster_cap, region_detected, missing_name,
+                           missing_cap);
 }
 
 // ---------------------------------------------------------------- k_bgzf_inflate alone (kernel-level entry point, §9e)
@@ -444,105 +683,144 @@ int64_t umiclust_bgzf_inflate(umiclust_ctx* ctx, const uint8_t* file, int64_t n,
 }
 
 // ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
+namespace {
+// What every open ends with, once S.raw holds the inflated file and d_raw the same bytes on the device: the header,
+// the record offsets, the scan with tags, the cs group-by, and the session put in place.  t_upload: the seconds the
+// open has already spent uploading.  Returns the number of records.
+int64_t finish_open(Ctx* c, BamSession& S, DevBuf<uint8_t>& d_raw, const char* bam_file, int32_t hash_bits,
+                    double t_upload) {
+  DevBuf<uint8_t> d_nmp;
+  std::string herr;
+  if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+  if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
+    c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
+  const int64_t n = (int64_t)S.roff.size();
+  uint64_t m = 1024;
+  while (m < 2 * (uint64_t)n) m <<= 1;
+  DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
+  DevBuf<int32_t> d_ref, d_lseq, d_cslen;
+  DevBuf<int8_t> d_cls, d_bad;
+  DevBuf<uint64_t> d_hash;
+  DevBuf<unsigned long long> d_keys, d_rep;
+  DevBuf<uint32_t> d_cnt, d_coll;
+  alloc_each(c, (size_t)n + 1, d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot, d_ref, d_lseq, d_cslen, d_cls, d_bad,
+             d_nmp, d_hash);
+  alloc_each(c, (size_t)m, d_keys, d_rep, d_cnt);
+  c->hip(d_coll.ensure(1), "alloc");
+  float ms = 0.f;
+  c->hip(hipEventRecord(c->ev0, c->st), "event");
+  if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(hipEventRecord(c->ev1, c->st), "event");
+  c->hip(hipEventSynchronize(c->ev1), "sync");
+  c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+  S.t_h2d = t_upload + ms * 1e-3;  // the compressed bytes and roff
+  const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
+                      d_bad.p};
+  // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
+  constexpr int kMaxSeeds = 8;
+  int pass = 0;
+  for (;; pass++) {
+    if (pass == kMaxSeeds) c->fail(UMICLUST_EDEVICE, "cs hash collisions under %d seeds", kMaxSeeds);
+    const uint64_t hmask = (pass == 0 && hash_bits < 64) ? ((1ull << hash_bits) - 1) : ~0ull;
+    uint32_t coll = 0;
+    c->hip(hipEventRecord(c->ev0, c->st), "event");
+    c->hip(launch_bam_scan(d_raw.p, (int64_t)S.raw.size(), d_roff.p, n, bam::cs_seed(pass), hmask, o, c->st), "bam scan");
+    c->hip(launch_cs_group(d_raw.p, o, n, m - 1, d_keys.p, d_rep.p, d_cnt.p, d_slot.p, d_coll.p, c->st), "cs group");
+    c->hip(hipEventRecord(c->ev1, c->st), "event");
+    c->hip(hipMemcpyAsync(&coll, d_coll.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
+    S.t_dev += ms * 1e-3;
+    if (!coll) break;
+  }
+  S.n_reruns = pass;
+  S.cls.resize(n), S.ref.resize(n), S.l_seq.resize(n), S.reflen.resize(n), S.cols.resize(n), S.nm.resize(n);
+  S.nm_present.resize(n), S.cs_off.resize(n), S.cs_len.resize(n), S.cs_group.assign(n, -1);
+  std::vector<int8_t> bad(n);
+  std::vector<int64_t> slot(n);
+  std::vector<unsigned long long> rep((size_t)m);
+  std::vector<uint32_t> cnt((size_t)m);
+  if (n) {
+    auto d2h = [&](void* dst, const void* src, size_t bytes) {
+      c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
+    };
+    d2h(S.cls.data(), d_cls.p, (size_t)n), d2h(S.ref.data(), d_ref.p, (size_t)n * 4);
+    d2h(S.l_seq.data(), d_lseq.p, (size_t)n * 4), d2h(S.reflen.data(), d_reflen.p, (size_t)n * 8);
+    d2h(S.cols.data(), d_cols.p, (size_t)n * 8), d2h(S.nm.data(), d_nm.p, (size_t)n * 8);
+    d2h(S.nm_present.data(), d_nmp.p, (size_t)n), d2h(S.cs_off.data(), d_csoff.p, (size_t)n * 8);
+    d2h(S.cs_len.data(), d_cslen.p, (size_t)n * 4), d2h(bad.data(), d_bad.p, (size_t)n);
+    d2h(slot.data(), d_slot.p, (size_t)n * 8), d2h(rep.data(), d_rep.p, (size_t)m * 8);
+    d2h(cnt.data(), d_cnt.p, (size_t)m * 4);
+    c->hip(hipStreamSynchronize(c->st), "sync");
+  }
+  for (int64_t r = 0; r < n; r++)
+    if (bad[r] && S.first_bad < 0) S.first_bad = r;  // a primary one fails below: what stays is a record never read
+  for (int64_t r = 0; r < n; r++)
+    if (S.cls[r] == bam::kScanPrimary && bad[r]) {
+      const std::string name(record_name(S.raw, S.roff, r));
+      c->fail(UMICLUST_EFORMAT, "malformed BAM record %lld (%s): a field or an aux tag does not fit the record",
+              (long long)r, name.c_str());
+    }
+  // dense group ids in order of the representative = first-seen order (a representative is its group's first record)
+  std::vector<int32_t> gid_of_slot;
+  gid_of_slot.assign((size_t)m, -1);
+  for (int64_t r = 0; r < n; r++) {
+    const int64_t s = slot[r];
+    if (s < 0) continue;
+    if ((int64_t)rep[s] == r) {
+      gid_of_slot[s] = (int32_t)S.g_rep.size();
+      S.g_rep.push_back(r);
+      S.g_count.push_back((int64_t)cnt[s]);
+    }
+    S.cs_group[r] = gid_of_slot[s];
+  }
+  S.open = true;
+  c->bs = std::move(S);
+  return n;
+}
+}  // namespace
+
 int64_t umiclust_bam_open(umiclust_ctx* ctx, const char* bam_file, int32_t hash_bits) {
   uc::Ctx* c = uc::core(ctx);
   UC_GUARD(c, {
     if (!bam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
     c->bs = BamSession();
     BamSession S;
-    DevBuf<uint8_t> d_raw, d_nmp;
+    DevBuf<uint8_t> d_raw;
     const double t0 = now_s();
     double t_upload = 0;
     if (!read_bam_on_device(c, bam_file, S.raw, d_raw, S.inflate_info, &t_upload))
       c->fail(UMICLUST_EIO, "cannot read BGZF/BAM %s", bam_file);
     S.t_inflate = now_s() - t0;  // from mapping the file until raw is on the host
-    std::string herr;
-    if (!bam::parse_header(S.raw.data(), S.raw.size(), S.hdr, herr)) c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
-    if (!bam::record_offsets(S.raw.data(), S.raw.size(), S.hdr.end, S.roff, herr))
-      c->fail(UMICLUST_EFORMAT, "%s: %s", bam_file, herr.c_str());
-    const int64_t n = (int64_t)S.roff.size();
-    uint64_t m = 1024;
-    while (m < 2 * (uint64_t)n) m <<= 1;
-    DevBuf<int64_t> d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot;
-    DevBuf<int32_t> d_ref, d_lseq, d_cslen;
-    DevBuf<int8_t> d_cls, d_bad;
-    DevBuf<uint64_t> d_hash;
-    DevBuf<unsigned long long> d_keys, d_rep;
-    DevBuf<uint32_t> d_cnt, d_coll;
-    alloc_each(c, (size_t)n + 1, d_roff, d_reflen, d_cols, d_nm, d_csoff, d_slot, d_ref, d_lseq, d_cslen, d_cls, d_bad,
-               d_nmp, d_hash);
-    alloc_each(c, (size_t)m, d_keys, d_rep, d_cnt);
-    c->hip(d_coll.ensure(1), "alloc");
-    float ms = 0.f;
-    c->hip(hipEventRecord(c->ev0, c->st), "event");
-    if (n) c->hip(hipMemcpyAsync(d_roff.p, S.roff.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->st), "h2d");
-    c->hip(hipEventRecord(c->ev1, c->st), "event");
-    c->hip(hipEventSynchronize(c->ev1), "sync");
-    c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-    S.t_h2d = t_upload + ms * 1e-3;  // the compressed bytes and roff
-    const BamScanCols o{d_cls.p, d_ref.p, d_lseq.p, d_reflen.p, d_cols.p, d_nm.p, d_nmp.p, d_csoff.p, d_cslen.p, d_hash.p,
-                        d_bad.p};
-    // hash, group, verify; a detected collision (two different strings, one hash) moves on to the next seed
-    constexpr int kMaxSeeds = 8;
-    int pass = 0;
-    for (;; pass++) {
-      if (pass == kMaxSeeds) c->fail(UMICLUST_EDEVICE, "cs hash collisions under %d seeds", kMaxSeeds);
-      const uint64_t hmask = (pass == 0 && hash_bits < 64) ? ((1ull << hash_bits) - 1) : ~0ull;
-      uint32_t coll = 0;
-      c->hip(hipEventRecord(c->ev0, c->st), "event");
-      c->hip(launch_bam_scan(d_raw.p, (int64_t)S.raw.size(), d_roff.p, n, bam::cs_seed(pass), hmask, o, c->st), "bam scan");
-      c->hip(launch_cs_group(d_raw.p, o, n, m - 1, d_keys.p, d_rep.p, d_cnt.p, d_slot.p, d_coll.p, c->st), "cs group");
-      c->hip(hipEventRecord(c->ev1, c->st), "event");
-      c->hip(hipMemcpyAsync(&coll, d_coll.p, 4, hipMemcpyDeviceToHost, c->st), "d2h");
-      c->hip(hipStreamSynchronize(c->st), "sync");
-      c->hip(hipEventElapsedTime(&ms, c->ev0, c->ev1), "elapsed");
-      S.t_dev += ms * 1e-3;
-      if (!coll) break;
-    }
-    S.n_reruns = pass;
-    S.cls.resize(n), S.ref.resize(n), S.l_seq.resize(n), S.reflen.resize(n), S.cols.resize(n), S.nm.resize(n);
-    S.nm_present.resize(n), S.cs_off.resize(n), S.cs_len.resize(n), S.cs_group.assign(n, -1);
-    std::vector<int8_t> bad(n);
-    std::vector<int64_t> slot(n);
-    std::vector<unsigned long long> rep((size_t)m);
-    std::vector<uint32_t> cnt((size_t)m);
-    if (n) {
-      auto d2h = [&](void* dst, const void* src, size_t bytes) {
-        c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
-      };
-      d2h(S.cls.data(), d_cls.p, (size_t)n), d2h(S.ref.data(), d_ref.p, (size_t)n * 4);
-      d2h(S.l_seq.data(), d_lseq.p, (size_t)n * 4), d2h(S.reflen.data(), d_reflen.p, (size_t)n * 8);
-      d2h(S.cols.data(), d_cols.p, (size_t)n * 8), d2h(S.nm.data(), d_nm.p, (size_t)n * 8);
-      d2h(S.nm_present.data(), d_nmp.p, (size_t)n), d2h(S.cs_off.data(), d_csoff.p, (size_t)n * 8);
-      d2h(S.cs_len.data(), d_cslen.p, (size_t)n * 4), d2h(bad.data(), d_bad.p, (size_t)n);
-      d2h(slot.data(), d_slot.p, (size_t)n * 8), d2h(rep.data(), d_rep.p, (size_t)m * 8);
-      d2h(cnt.data(), d_cnt.p, (size_t)m * 4);
-      c->hip(hipStreamSynchronize(c->st), "sync");
-    }
-    for (int64_t r = 0; r < n; r++)
-      if (bad[r] && S.first_bad < 0) S.first_bad = r;  // a primary one fails below: what stays is a record never read
-    for (int64_t r = 0; r < n; r++)
-      if (S.cls[r] == bam::kScanPrimary && bad[r]) {
-        const std::string name(record_name(S.raw, S.roff, r));
-        c->fail(UMICLUST_EFORMAT, "malformed BAM record %lld (%s): a field or an aux tag does not fit the record",
-                (long long)r, name.c_str());
-      }
-    // dense group ids in order of the representative = first-seen order (a representative is its group's first record)
-    std::vector<int32_t> gid_of_slot;
-    gid_of_slot.assign((size_t)m, -1);
-    for (int64_t r = 0; r < n; r++) {
-      const int64_t s = slot[r];
-      if (s < 0) continue;
-      if ((int64_t)rep[s] == r) {
-        gid_of_slot[s] = (int32_t)S.g_rep.size();
-        S.g_rep.push_back(r);
-        S.g_count.push_back((int64_t)cnt[s]);
-      }
-      S.cs_group[r] = gid_of_slot[s];
-    }
-    S.open = true;
-    c->bs = std::move(S);
-    return n;
+    return finish_open(c, S, d_raw, bam_file, hash_bits, t_upload);
+  });
+}
+
+int64_t umiclust_sam_open(umiclust_ctx* ctx, const char* sam_file, int32_t hash_bits) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    if (!sam_file || hash_bits < 1 || hash_bits > 64) c->fail(UMICLUST_EINVAL, "bad argument");
+    c->bs = BamSession();
+    BamSession S;
+    DevBuf<uint8_t> d_raw;
+    const double t0 = now_s();
+    S.from_sam = true;
+    read_sam_on_device(c, sam_file, S.raw, d_raw, S.sam_info, S.sam_times);
+    S.t_inflate = now_s() - t0;  // from reading the text until raw is on the host
+    return finish_open(c, S, d_raw, sam_file, hash_bits, S.sam_times[0]);
+  });
+}
+
+int32_t umiclust_sam_info(umiclust_ctx* ctx, int64_t* out, double* times) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!S.from_sam) c->fail(UMICLUST_ESTATE, "the session was not opened from SAM text (umiclust_sam_open)");
+    if (out)
+      for (int x = 0; x < 4; x++) out[x] = S.sam_info[x];
+    if (times)
+      for (int x = 0; x < 5; x++) times[x] = S.sam_times[x];
+    return UMICLUST_OK;
   });
 }
 

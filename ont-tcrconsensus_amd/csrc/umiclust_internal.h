@@ -342,4 +342,40 @@ struct BgzfBlock {   // one entry per block with ISIZE > 0, built by the host fr
 hipError_t launch_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, const BgzfBlock* blk, int64_t n, uint8_t* out,
                                int32_t* status, hipStream_t st);
 
+// ---- SAM text to the session's raw and roff (samsort.hip on sam_text.h) ----
+// body = the text after the header, n bytes.  Every pointer is device memory.
+namespace sam {
+struct Names;
+struct Fields;
+struct FSlot;
+}  // namespace sam
+// out[i] = base + in[0] + .. + in[i - 1]; *total (may be null) = base + the sum; in may be out
+hipError_t launch_scan_i64(const int64_t* in, int64_t* out, int64_t n, int64_t base, int64_t* total, hipStream_t st);
+// the chunks the line kernels split n bytes into: count[] and first[] have one entry per chunk
+int64_t sam_line_chunks(int64_t n);
+// *total = lines - 1 (a line starts at 0 and after every '\n' but the text's last byte); n > 0
+hipError_t launch_sam_count_lines(const uint8_t* body, int64_t n, int64_t* count, int64_t* first, int64_t* total,
+                                  hipStream_t st);
+// start[nlines + 1]: line l = body[start[l], start[l + 1] - 1)
+hipError_t launch_sam_scatter_lines(const uint8_t* body, int64_t n, const int64_t* first, int64_t nlines,
+                                    int64_t* start, hipStream_t st);
+// per line: fields, size, key, status (sam::measure); acc[0] = first refused line (start it at ~0), acc[1] = OR of the
+// accepted keys, acc[2] = aux f values
+hipError_t launch_sam_measure(const uint8_t* body, const int64_t* start, int64_t n, const sam::Names& N,
+                              sam::Fields* fields, int64_t* size, uint64_t* key, int32_t* status, uint64_t* acc,
+                              hipStream_t st);
+// stable sort of (key, line) by key: key_a holds the keys (both key arrays are scratch afterwards), key_bits = the OR
+// of all keys, hist = 256 * ceil(n / 256) entries; *sorted_idx = idx_a or idx_b, whichever holds the order
+hipError_t launch_sam_sort(uint64_t* key_a, uint32_t* idx_a, uint64_t* key_b, uint32_t* idx_b, int64_t n,
+                           uint64_t key_bits, int64_t* hist, const uint32_t** sorted_idx, hipStream_t st);
+// roff[r] = base + the sizes of the records before r in sorted order; *total = one past the last record
+hipError_t launch_sam_roff(const int64_t* size, const uint32_t* idx, int64_t n, int64_t base, int64_t* roff,
+                           int64_t* total, hipStream_t st);
+// the records at raw + roff[r] (sam::encode); the aux f values appended to slots[0, cap) through *nslots
+hipError_t launch_sam_encode(const uint8_t* body, const int64_t* start, const uint32_t* idx, const int64_t* roff,
+                             int64_t n, const sam::Names& N, const sam::Fields* fields, const int64_t* size,
+                             uint8_t* raw, sam::FSlot* slots, uint64_t* nslots, int64_t cap, hipStream_t st);
+// raw[at[i] .. + 4) = bits[i], little-endian
+hipError_t launch_sam_put_f(uint8_t* raw, const int64_t* at, const uint32_t* bits, int64_t n, hipStream_t st);
+
 }  // namespace uc

@@ -149,7 +149,8 @@ EXPORTS = [
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
-    "umiclust_bgzf_inflate", "umiclust_bam_inflate_info",
+    "umiclust_bgzf_inflate", "umiclust_bam_inflate_info", "umiclust_sam_open", "umiclust_sam_info",
+    "umiclust_bam_region_split", "umiclust_bam_region_split_extract",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -322,6 +323,16 @@ def lib() -> C.CDLL:
                                         P(C.c_int64), P(C.c_double)]
     L.umiclust_bam_close.restype = C.c_int32
     L.umiclust_bam_close.argtypes = [C.c_void_p]
+    L.umiclust_sam_open.restype = C.c_int64
+    L.umiclust_sam_open.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.umiclust_sam_info.restype = C.c_int32
+    L.umiclust_sam_info.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
+    # the path-based calls without their bam_file argument
+    L.umiclust_bam_region_split.restype = C.c_int64
+    L.umiclust_bam_region_split.argtypes = [a for k, a in enumerate(L.umiclust_region_split.argtypes) if k != 1]
+    L.umiclust_bam_region_split_extract.restype = C.c_int64
+    L.umiclust_bam_region_split_extract.argtypes = [a for k, a in enumerate(L.umiclust_region_split_extract.argtypes)
+                                                    if k != 1]
     _lib = L
     return L
 
@@ -652,7 +663,7 @@ class Context:
 
     def region_split(self, bam_file: str, names, lengths, clusters, minov: float, s5: int, s3: int, out_dir: str):
         """umiclust_region_split: (counts[4], reads_per_cluster, region_detected); KeyError(name) as the
-        reference raises it."""
+        reference raises it.  bam_file None: umiclust_bam_region_split, on the open session."""
         R = len(names)
         nm = (C.c_char_p * max(R, 1))(*[x.encode() for x in names])
         ln = np.asarray(lengths, np.int64)
@@ -663,9 +674,12 @@ class Context:
         det = np.zeros(max(R, 1), np.uint8)
         miss = C.create_string_buffer(4096)
         P = C.POINTER
-        rc = lib().umiclust_region_split(self._h, bam_file.encode(), R, nm, _i64(ln), cl.ctypes.data_as(P(C.c_int32)),
-                                         minov, s5, s3, out_dir.encode(), _i64(counts), _i64(rpc), cap,
-                                         det.ctypes.data_as(P(C.c_uint8)), miss, 4096)
+        tail = (R, nm, _i64(ln), cl.ctypes.data_as(P(C.c_int32)), minov, s5, s3, os.fspath(out_dir).encode(),
+                _i64(counts), _i64(rpc), cap, det.ctypes.data_as(P(C.c_uint8)), miss, 4096)
+        if bam_file is None:
+            rc = lib().umiclust_bam_region_split(self._h, *tail)
+        else:
+            rc = lib().umiclust_region_split(self._h, os.fspath(bam_file).encode(), *tail)
         if rc == -74 and miss.value:
             raise KeyError(miss.value.decode())
         if rc == -74 and (lib().umiclust_last_error(self._h) or b"").startswith(b"TypeError: "):
@@ -677,7 +691,8 @@ class Context:
                              a3: int, k: int, fwd: str, rev: str, umi_out_dir: str):
         """umiclust_region_split_extract (row f4+f1): region_split and extract_umis_file in one pass,
         region_cluster<k>_detected_umis.fasta in umi_out_dir and no region FASTA.  (counts[4], reads_per_cluster,
-        umis_per_cluster, region_detected); KeyError(name) as region_split raises it, with no file written."""
+        umis_per_cluster, region_detected); KeyError(name) as region_split raises it, with no file written.  bam_file
+        None: umiclust_bam_region_split_extract, on the open session."""
         R = len(names)
         nm = (C.c_char_p * max(R, 1))(*[x.encode() for x in names])
         ln = np.asarray(lengths, np.int64)
@@ -688,10 +703,13 @@ class Context:
         det = np.zeros(max(R, 1), np.uint8)
         miss = C.create_string_buffer(4096)
         P = C.POINTER
-        rc = lib().umiclust_region_split_extract(
-            self._h, os.fspath(bam_file).encode(), R, nm, _i64(ln), cl.ctypes.data_as(P(C.c_int32)), minov, s5, s3, a5,
-            a3, k, fwd.encode(), rev.encode(), os.fspath(umi_out_dir).encode(), _i64(counts), _i64(rpc), _i64(upc), cap,
-            det.ctypes.data_as(P(C.c_uint8)), miss, 4096)
+        tail = (R, nm, _i64(ln), cl.ctypes.data_as(P(C.c_int32)), minov, s5, s3, a5, a3, k, fwd.encode(), rev.encode(),
+                os.fspath(umi_out_dir).encode(), _i64(counts), _i64(rpc), _i64(upc), cap,
+                det.ctypes.data_as(P(C.c_uint8)), miss, 4096)
+        if bam_file is None:
+            rc = lib().umiclust_bam_region_split_extract(self._h, *tail)
+        else:
+            rc = lib().umiclust_region_split_extract(self._h, os.fspath(bam_file).encode(), *tail)
         if rc == -74 and miss.value:
             raise KeyError(miss.value.decode())
         self._check(rc, "region_split_extract")
@@ -700,6 +718,12 @@ class Context:
     def bam_open(self, bam_file: str, hash_bits: int = 64) -> "BamSession":
         """umiclust_bam_open: the BAM session of this context (one at a time; row f6)."""
         self._check(lib().umiclust_bam_open(self._h, os.fspath(bam_file).encode(), hash_bits), "bam_open")
+        return BamSession(self)
+
+    def sam_open(self, sam_file, hash_bits: int = 64) -> "BamSession":
+        """umiclust_sam_open: the BAM session of SAM text -- a file, a FIFO or /dev/fd/N -- parsed,
+        encoded and coordinate-sorted on the device; the session umiclust_bam_open gives for `samtools sort`'s file."""
+        self._check(lib().umiclust_sam_open(self._h, os.fspath(sam_file).encode(), hash_bits), "sam_open")
         return BamSession(self)
 
     def bgzf_inflate(self, data, want_status: bool = False):
@@ -937,6 +961,25 @@ class BamSession:
         out = np.zeros(3, np.int64)
         self._ctx._check(lib().umiclust_bam_inflate_info(self._ctx._h, _i64(out)), "bam_inflate_info")
         return tuple(int(x) for x in out)
+
+    def sam_info(self) -> dict:
+        """umiclust_sam_info: the counts and HIP-event seconds of the umiclust_sam_open that made this session"""
+        out, t = np.zeros(4, np.int64), np.zeros(5, np.float64)
+        self._ctx._check(lib().umiclust_sam_info(self._ctx._h, _i64(out), t.ctypes.data_as(C.POINTER(C.c_double))),
+                         "sam_info")
+        d = dict(zip(("lines", "records", "text_bytes", "f_values"), (int(x) for x in out)))
+        d.update(zip(("upload_s", "measure_s", "sort_s", "encode_s", "copy_back_s"), (float(x) for x in t)))
+        return d
+
+    def region_split(self, names, lengths, clusters, minov: float, s5: int, s3: int, out_dir):
+        """umiclust_bam_region_split: Context.region_split on this session instead of a file"""
+        return self._ctx.region_split(None, names, lengths, clusters, minov, s5, s3, out_dir)
+
+    def region_split_extract(self, names, lengths, clusters, minov: float, s5: int, s3: int, a5: int, a3: int, k: int,
+                             fwd: str, rev: str, umi_out_dir):
+        """umiclust_bam_region_split_extract: Context.region_split_extract on this session instead of a file"""
+        return self._ctx.region_split_extract(None, names, lengths, clusters, minov, s5, s3, a5, a3, k, fwd, rev,
+                                              umi_out_dir)
 
     def query_names(self, idx) -> list:
         return self._strings(0, idx)

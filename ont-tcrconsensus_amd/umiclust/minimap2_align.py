@@ -119,6 +119,61 @@ def write_cs_tag_report(fh, bam_file_or_session, keep=None, top: int = 40, sub: 
     fh.write(cs_tag_report(bam_file_or_session, keep=keep, top=top, sub=sub))
 
 
+def samtools_sort(sam_file: Union[str, os.PathLike[str]], bam_file: Union[str, os.PathLike[str]]) -> int:
+    """`samtools sort -o bam_file sam_file` (:133-137) on the device (umiclust_sam_open): the text --
+    a file, a FIFO or /dev/fd/N -- parsed, encoded and coordinate-sorted, every record written.  Returns their number.
+    No index is written: `samtools index` runs on the file as before."""
+    with _v.context().sam_open(os.fspath(sam_file)) as src:
+        return src.write(np.ones(src.n, np.uint8), bam_file)
+
+
+def minimap2_ont_align_session(fastx: Union[str, os.PathLike[str]], reference: Union[str, os.PathLike[str]],
+                               logs_dir: Union[str, os.PathLike[str]], minimap2_threads: int,
+                               minimap2_params: str = None, bam_file: Union[str, os.PathLike[str]] = None):
+    """minimap2_ont_align (:76-155) without the BAM in the middle: minimap2 runs with the reference's argv and its
+    stderr in the same <fastx>_minimap2.err log; its SAM output is read from the pipe by umiclust_sam_open, which
+    parses, encodes and coordinate-sorts it on the device; the three cs-tag blocks of :140-150 are appended to the log
+    from that session; and the open session is returned, for region_split.filter_split_and_extract_umis_from and its
+    like.  The sorted BAM is written only when bam_file is given.  `samtools index` (:138) and `samtools flagstat`
+    (:152-153) are not replaced: a caller that wants them passes bam_file and runs them on it."""
+    log_file = os.path.join(logs_dir, os.path.basename(fastx).split(".")[0] + "_minimap2")
+    with open(log_file + ".err", "w") as ferr:
+        minimap2_process = subprocess.Popen(
+            [
+                "minimap2",
+                "-ax",
+                "map-ont",
+                "-k19",
+                "-w 19",
+                "-U50,500",
+                "-g10k",
+                "--end-bonus=10",
+                "-t",
+                str(minimap2_threads),
+                "--cap-kalloc",
+                "500m",
+                minimap2_params if minimap2_params else "--cs",
+                reference,
+                fastx,
+            ],
+            stdout=subprocess.PIPE,
+            stderr=ferr,
+        )
+        try:
+            src = _v.context().sam_open("/dev/fd/%d" % minimap2_process.stdout.fileno())
+        finally:
+            minimap2_process.stdout.close()
+            minimap2_process.wait()
+        try:
+            write_cs_tag_report(ferr, src)
+            if bam_file is not None:
+                src.write(np.ones(src.n, np.uint8), bam_file)
+        except Exception:
+            src.close()
+            raise
+    return src
+
+
 def _to_csv(path, columns, rows) -> None:
     """pandas.DataFrame(rows, columns=columns).to_csv(path, index=False): minimal quoting, floats as repr"""
     with open(path, "w", newline="") as fh:

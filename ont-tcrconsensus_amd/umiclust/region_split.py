@@ -11,6 +11,10 @@ Also the round-2 function of the same file, filter_and_split_reads_by_region (:3
 append-mode region_<name>.fasta per reference name, no cluster lookup, the
 <bam>_filter_and_split_reads_by_region.err log.  It runs on a BAM session (umiclust_bam_open + umiclust_bam_split),
 so that minimap2_align.filter_consensus_alignments_and_split can split the session that filtered the consensus BAM.
+
+The round-1 functions have session forms too: filter_and_split_reads_by_region_cluster_from and
+filter_split_and_extract_umis_from take an open session -- the one minimap2_align.minimap2_ont_align_session returns --
+in place of the BAM path, so that the raw-read alignments are parsed and scanned once and no BAM is read back.
 """
 from __future__ import annotations
 
@@ -136,6 +140,52 @@ def filter_split_and_extract_umis(bam_file: Union[str, os.PathLike[str]],
         os.fspath(bam_file), names, [region_length_dict[n] for n in names],
         [int(region_cluster_dict[n]) if n in region_cluster_dict else -1 for n in names], minimal_region_overlap,
         max_softclip_5_end, max_softclip_3_end,
+        max_softclip_5_end if adapter_length_5_end is None else adapter_length_5_end,
+        max_softclip_3_end if adapter_length_3_end is None else adapter_length_3_end, max_pattern_dist, umi_fwd,
+        umi_rev, os.fspath(umi_fasta_out_dir))
+    _write_region_cluster_log(log_file, reference, names, counts, per_cluster, detected)
+    return list({os.path.join(umi_fasta_out_dir, "region_cluster{}_detected_umis.fasta".format(k))
+                 for k, v in enumerate(umis) if v})
+
+
+def _round1_inputs(bam_file, region_cluster_dict_json, reference, logs_dir):
+    """log path, region names, lengths and clusters as the round-1 functions above hand them to the library"""
+    log_file = os.path.join(logs_dir,
+                            os.path.basename(bam_file).split(".")[0] + "_filter_and_split_reads_by_region_cluster.err")
+    with open(region_cluster_dict_json, "r") as json_in:
+        region_cluster_dict = json.load(json_in)
+    region_length_dict = generate_region_length_dict_from_ref_fa(reference=reference)
+    names = list(region_length_dict)
+    return (log_file, names, [region_length_dict[n] for n in names],
+            [int(region_cluster_dict[n]) if n in region_cluster_dict else -1 for n in names])
+
+
+def filter_and_split_reads_by_region_cluster_from(src, bam_file, region_cluster_dict_json, reference, logs_dir,
+                                                  region_fasta_out_dir, minimal_region_overlap: float = 0.95,
+                                                  max_softclip_5_end: int = 73, max_softclip_3_end: int = 68):
+    """filter_and_split_reads_by_region_cluster over an open BAM session `src` (a _lib.BamSession, from bam_open or
+    sam_open) instead of the file: the same region_cluster<k>.fasta files, the same log -- named after `bam_file`, which
+    need not exist -- and the same return value (umiclust_bam_region_split)."""
+    log_file, names, lengths, clusters = _round1_inputs(bam_file, region_cluster_dict_json, reference, logs_dir)
+    counts, per_cluster, detected = src.region_split(names, lengths, clusters, minimal_region_overlap,
+                                                     max_softclip_5_end, max_softclip_3_end,
+                                                     os.fspath(region_fasta_out_dir))
+    kept = _write_region_cluster_log(log_file, reference, names, counts, per_cluster, detected)
+    return list({os.path.join(region_fasta_out_dir, "region_cluster{}.fasta".format(k)) for k in kept})
+
+
+def filter_split_and_extract_umis_from(src, bam_file, region_cluster_dict_json, reference, logs_dir, umi_fasta_out_dir,
+                                       minimal_region_overlap: float = 0.95, max_softclip_5_end: int = 73,
+                                       max_softclip_3_end: int = 68, adapter_length_5_end: int = None,
+                                       adapter_length_3_end: int = None, max_pattern_dist: int = 3,
+                                       umi_fwd: str = UMI_FWD_DEFAULT, umi_rev: str = UMI_REV_DEFAULT):
+    """filter_split_and_extract_umis over an open BAM session `src` instead of the file: the same log, named after
+    `bam_file`, the same region_cluster<k>_detected_umis.fasta files and the same return value
+    (umiclust_bam_region_split_extract).  With the session of minimap2_ont_align_session this is the
+    whole of tcr_consensus.py:170-223 on one parse and one scan, with no BAM in between."""
+    log_file, names, lengths, clusters = _round1_inputs(bam_file, region_cluster_dict_json, reference, logs_dir)
+    counts, per_cluster, umis, detected = src.region_split_extract(
+        names, lengths, clusters, minimal_region_overlap, max_softclip_5_end, max_softclip_3_end,
         max_softclip_5_end if adapter_length_5_end is None else adapter_length_5_end,
         max_softclip_3_end if adapter_length_3_end is None else adapter_length_3_end, max_pattern_dist, umi_fwd,
         umi_rev, os.fspath(umi_fasta_out_dir))
