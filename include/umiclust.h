@@ -461,8 +461,17 @@ int32_t umiclust_bam_cs_groups(umiclust_ctx *ctx, int64_t *count, int64_t *rep);
 /* header + the records with keep[r] != 0, as BGZF (blocks of at most 0xff00 payload bytes, EOF block last): the
  * file inflates to the input's header bytes and the kept records' bytes verbatim, in input order (what
  * pysam.AlignmentFile(..., "wb", template=bam_in).write(entry) leaves, :207/:245, up to the compressed form);
- * returns the number written */
+ * returns the number written.  The blocks are deflated on the device (batches of UMICLUST_BGZF_BATCH
+ * blocks, gathered and CRC32'd by the I/O threads, deflated and framed by k_bgzf_deflate / k_bgzf_frame, written in
+ * order); the compressed bytes are valid gzip members but not zlib's.  zlib on the host writes the file instead with
+ * UMICLUST_BGZF_WRITE=host, where the memory for a batch cannot be had, and for a single block the encoder refuses */
 int64_t umiclust_bam_write(umiclust_ctx *ctx, const uint8_t *keep, const char *out_bam);
+/* DIAGNOSTIC (an added function, ABI version unchanged): the session's last umiclust_bam_write.  out[0..7] = blocks
+ * (EOF block not counted), blocks deflated on the device, of those stored / fixed / dynamic, blocks redone on the host,
+ * batches, compressed bytes (the file's size); times[0..3] = seconds of upload, kernels, copy back (HIP events) and of
+ * the host's gather + CRC32.  Either may be NULL.  A file the host wrote reports its blocks and bytes, zero elsewhere.
+ * UMICLUST_ESTATE before the first write */
+int32_t umiclust_bam_write_info(umiclust_ctx *ctx, int64_t *out, double *times);
 
 /* ---- round-2 region split and precision census on the session (rows f4b / f6b) ---- */
 /* Replaces the record loops of filter_and_split_reads_by_region (ont_tcr_consensus/region_split.py:336-435) and of
@@ -699,6 +708,17 @@ int32_t umiclust_pass(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int
  * not checked. */
 int64_t umiclust_bgzf_inflate(umiclust_ctx *ctx, const uint8_t *file, int64_t n, uint8_t *out, int64_t cap,
                               int32_t *block_status, int64_t *n_blocks, double *times);
+
+/* The BGZF deflate kernels alone (an added function, ABI version unchanged).
+ * data = n bytes in host memory, cut into blocks of 0xff00 bytes (the last one shorter).  cap == 0: returns an upper
+ * bound on the output size without a launch.  Otherwise (cap at least that bound) deflates and frames every block on
+ * the device and returns the size of the BGZF written to out, the 28-byte EOF block included; empty input gives the
+ * EOF block alone.  Each block is one gzip member that inflates to its input bytes, and is byte for byte what
+ * uc::deflate_block (csrc/deflate.h, the host restatement) produces; the CRC32s are computed on the host.
+ * block_kind (may be NULL): per block 0 = stored, 1 = fixed, 2 = dynamic.  n_blocks (may be NULL): ceil(n / 0xff00),
+ * set by every call.  times (may be NULL): seconds of upload, kernels, download by HIP events. */
+int64_t umiclust_bgzf_deflate(umiclust_ctx *ctx, const uint8_t *data, int64_t n, uint8_t *out, int64_t cap,
+                              int32_t *block_kind, int64_t *n_blocks, double *times);
 
 /* ---- measurement (bench.py; no reference counterpart) ---- */
 /* Process-wide device timeline of the counting launches (kind 0) and the alignment chains

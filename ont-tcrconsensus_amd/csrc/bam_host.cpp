@@ -232,13 +232,9 @@ std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3
 }
 
 // ---------------------------------------------------------------- BGZF writer
-namespace {
-
-constexpr size_t kBgzfPayload = 0xff00;
 const uint8_t kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43,
                               0x02, 0,    0x1b, 0,    0x03, 0, 0, 0, 0, 0, 0, 0,    0,    0};
 
-// one block of at most kBgzfPayload bytes; level 0 (stored) if the deflated form would not fit BSIZE
 bool bgzf_block(const uint8_t* src, size_t n, std::vector<uint8_t>& out) {
   for (int level : {6, 0}) {
     out.assign(18 + compressBound((uLong)n) + 64 + 8, 0);
@@ -279,26 +275,56 @@ bool write_fd(int fd, const uint8_t* p, size_t n) {
   return true;
 }
 
-}  // namespace
+uint32_t bgzf_crc32(const uint8_t* p, size_t n) { return (uint32_t)crc32(crc32(0L, Z_NULL, 0), p, (uInt)n); }
 
-int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
-                   const uint8_t* keep, int threads, std::string& err) {
-  // the uncompressed stream as segments of raw: the header bytes, then the kept records (a run of adjacent kept
-  // records is one segment); seg_at[k] = stream offset of segment k.  Blocks are cut from the segments directly, so
-  // the stream itself is never materialised.
-  std::vector<std::pair<size_t, size_t>> seg;  // (offset in raw, length)
-  seg.emplace_back(0, header_end);
-  int64_t nkept = 0;
+BgzfStream bgzf_stream(const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff, const uint8_t* keep) {
+  BgzfStream S;
+  S.raw = raw;
+  S.seg.emplace_back(0, header_end);
   for (size_t r = 0; r < roff.size(); r++)
     if (keep[r]) {
       const size_t o = (size_t)roff[r], n = 4 + (size_t)ld_u32(raw + o);
-      if (seg.back().first + seg.back().second == o) seg.back().second += n;
-      else seg.emplace_back(o, n);
-      nkept++;
+      if (S.seg.back().first + S.seg.back().second == o) S.seg.back().second += n;
+      else S.seg.emplace_back(o, n);
+      S.nkept++;
     }
-  std::vector<size_t> seg_at(seg.size() + 1, 0);
-  for (size_t k = 0; k < seg.size(); k++) seg_at[k + 1] = seg_at[k] + seg[k].second;
-  const size_t total = seg_at.back();
+  S.seg_at.assign(S.seg.size() + 1, 0);
+  for (size_t k = 0; k < S.seg.size(); k++) S.seg_at[k + 1] = S.seg_at[k] + S.seg[k].second;
+  S.total = S.seg_at.back();
+  return S;
+}
+
+void BgzfStream::gather(size_t at, size_t n, uint8_t* dst) const {
+  size_t k = (size_t)(std::upper_bound(seg_at.begin(), seg_at.end(), at) - seg_at.begin()) - 1, got = 0;
+  for (size_t in_seg = at - seg_at[k]; got < n; k++, in_seg = 0) {
+    const size_t m = std::min(n - got, seg[k].second - in_seg);
+    memcpy(dst + got, raw + seg[k].first + in_seg, m);
+    got += m;
+  }
+}
+
+void bgzf_gather_crc(const BgzfStream& S, size_t b0, size_t b1, uint8_t* dst, uint32_t* crc, int threads) {
+  const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, threads), b1 - b0));
+  std::atomic<size_t> next(b0);
+  auto work = [&]() {
+    for (size_t b = next.fetch_add(1); b < b1; b = next.fetch_add(1)) {
+      const size_t n = S.block_bytes(b);
+      uint8_t* const d = dst + (b - b0) * kBgzfPayload;
+      S.gather(b * kBgzfPayload, n, d);
+      crc[b - b0] = bgzf_crc32(d, n);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; t++) th.emplace_back(work);
+  work();
+  for (auto& x : th) x.join();
+}
+
+int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
+                   const uint8_t* keep, int threads, std::string& err) {
+  const BgzfStream S = bgzf_stream(raw, header_end, roff, keep);
+  const size_t total = S.total;
+  const int64_t nkept = S.nkept;
   const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
   if (fd < 0) {
     err = std::string("cannot create ") + path;
@@ -317,12 +343,7 @@ int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, cons
       std::vector<uint8_t> in(kBgzfPayload);
       for (size_t b = next.fetch_add(1); b < b1; b = next.fetch_add(1)) {
         const size_t a = b * kBgzfPayload, n = std::min(kBgzfPayload, total - a);
-        size_t k = (size_t)(std::upper_bound(seg_at.begin(), seg_at.end(), a) - seg_at.begin()) - 1, got = 0;
-        for (size_t in_seg = a - seg_at[k]; got < n; k++, in_seg = 0) {  // gather the block's bytes
-          const size_t m = std::min(n - got, seg[k].second - in_seg);
-          memcpy(in.data() + got, raw + seg[k].first + in_seg, m);
-          got += m;
-        }
+        S.gather(a, n, in.data());  // the block's bytes
         if (!bgzf_block(in.data(), n, out[b - b0])) failed = 1;
       }
     };

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -81,6 +82,31 @@ std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3
 // and written in order.  Returns the number of records written, -1 + err on an I/O failure.
 int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
                    const uint8_t* keep, int threads, std::string& err);
+
+// The pieces of it that the device writer (dropin_bam.cpp) shares.
+constexpr size_t kBgzfPayload = 0xff00;
+extern const uint8_t kBgzfEof[28];
+// The uncompressed stream as segments of raw: the header bytes, then the kept records (a run of adjacent kept records
+// is one segment); seg_at[k] = stream offset of segment k.  Blocks are cut from the segments directly, so the stream
+// itself is never materialised.
+struct BgzfStream {
+  const uint8_t* raw = nullptr;
+  std::vector<std::pair<size_t, size_t>> seg;  // (offset in raw, length)
+  std::vector<size_t> seg_at;
+  size_t total = 0;
+  int64_t nkept = 0;
+  size_t blocks() const { return (total + kBgzfPayload - 1) / kBgzfPayload; }
+  size_t block_bytes(size_t b) const { return std::min(kBgzfPayload, total - b * kBgzfPayload); }
+  void gather(size_t at, size_t n, uint8_t* dst) const;  // stream bytes [at, at + n) to dst
+};
+BgzfStream bgzf_stream(const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff, const uint8_t* keep);
+// blocks [b0, b1) of the stream to dst (block b at (b - b0) * 0xff00) and the CRC32 of each to crc[b - b0], on
+// `threads` threads
+void bgzf_gather_crc(const BgzfStream& S, size_t b0, size_t b1, uint8_t* dst, uint32_t* crc, int threads);
+// one block of at most 0xff00 bytes by zlib at level 6, framed (level 0 if the deflated form would not fit BSIZE)
+bool bgzf_block(const uint8_t* src, size_t n, std::vector<uint8_t>& out);
+bool write_fd(int fd, const uint8_t* p, size_t n);
+uint32_t bgzf_crc32(const uint8_t* p, size_t n);  // zlib's
 
 }  // namespace bam
 }  // namespace uc

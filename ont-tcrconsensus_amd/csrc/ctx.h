@@ -128,6 +128,52 @@ struct FqState {
   Event ev[3];  // copy begin, kernel begin, kernel end
 };
 
+// The device writer of the BAM session.
+constexpr size_t kDeflateIn = bam::kBgzfPayload;       // a block's input bytes at most
+constexpr size_t kDeflateFramed = kDeflateIn + 5 + 26;  // its framed bytes at most: stored form, header and trailer
+// The device buffers of one batch of at most `cap` blocks and the host copies of its tables.
+struct DeflateDev {
+  DevBuf<uint8_t> d_in, d_slots, d_out;
+  DevBuf<uint32_t> d_tok, d_crc;
+  DevBuf<DeflateBlock> d_blk;
+  DevBuf<int32_t> d_meta;
+  DevBuf<int64_t> d_fsize, d_foff;
+  std::vector<DeflateBlock> blk;
+  std::vector<int32_t> meta;  // per block: kind, payload bytes, status, flags
+  std::vector<int64_t> foff;  // per block: its framed bytes' offset; foff[nb] = the batch's framed bytes
+  Event e[4];
+  void release() {
+    d_in.release(), d_slots.release(), d_out.release(), d_tok.release(), d_crc.release(), d_blk.release();
+    d_meta.release(), d_fsize.release(), d_foff.release();
+  }
+  // an allocation failure is returned, not thrown: the writer then takes the host path
+  hipError_t ensure(size_t cap) {
+    const size_t grid = std::min<size_t>(cap, (size_t)kDeflateGrid);
+    hipError_t r = hipSuccess;
+    auto on = [&](hipError_t x) { r = r == hipSuccess ? x : r; };
+    on(d_in.ensure(cap * kDeflateIn + 8)), on(d_slots.ensure(cap * (size_t)kDeflateSlot)), on(d_out.ensure(cap * kDeflateFramed + 8));
+    on(d_tok.ensure(grid * kDeflateIn)), on(d_crc.ensure(cap)), on(d_blk.ensure(cap)), on(d_meta.ensure(4 * cap));
+    on(d_fsize.ensure(cap)), on(d_foff.ensure(cap + 1));
+    for (Event& x : e) on(x.create());
+    if (r != hipSuccess) (void)hipGetLastError();
+    return r;
+  }
+};
+// The writer's buffers, kept across calls: one batch on the device, two pinned staging slots (one being gathered
+// while the other is on the device) and the pinned framed bytes of a batch.
+struct BgzfWriteState {
+  DeflateDev dev;
+  struct Slot {
+    PinBuf<uint8_t> in;
+    PinBuf<uint32_t> crc;
+  } slot[2];
+  PinBuf<uint8_t> out;
+  void release() {
+    dev.release(), out.release();
+    for (Slot& s : slot) s.in.release(), s.crc.release();
+  }
+};
+
 // The inflated file on the host: a byte array that is not zero-filled when it is made, because the copy from the
 // device writes every byte of it (zero-filling 540 MB on one thread cost more than inflating them)
 struct RawBuf {
@@ -166,6 +212,12 @@ struct BamSession {
   int64_t n_reruns = 0, first_bad = -1;
   int64_t inflate_info[3] = {0, 0, 0};  // BGZF blocks, blocks inflated on the device, compressed bytes uploaded
   double t_inflate = 0, t_h2d = 0, t_dev = 0;
+  // the last umiclust_bam_write: blocks, blocks deflated on the device, of them stored / fixed /
+  // dynamic, blocks redone on the host, batches, compressed bytes; seconds of upload, kernels, copy back (HIP events)
+  // and of the host's gather + CRC32
+  bool wrote = false;
+  int64_t write_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double write_times[4] = {0, 0, 0, 0};
   // a session opened from SAM text (umiclust_sam_open): lines, records, text bytes uploaded, aux f
   // values the host parsed; seconds of upload, lines + measure, sort, encode, copy back
   bool from_sam = false;
@@ -183,6 +235,7 @@ struct Ctx {
   ExtractState ex;
   FqState fq;
   BamSession bs;
+  BgzfWriteState bw;
   // (the members go after the derived context's destructor, which selects the device)
 
   void fail(int code, const char* fmt, ...) {

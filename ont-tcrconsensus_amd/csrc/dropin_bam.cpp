@@ -4,7 +4,8 @@
 // extraction (§8f f4+f1, DESIGN.md §9d, bamextract.hip).  Both readers inflate the file on the device (DESIGN.md §9e,
 // bgzf.hip on inflate.h), which umiclust_bgzf_inflate runs alone.  Their HIP-free halves are in bam_host.h.  The
 // session also opens from SAM text, parsed, encoded and coordinate-sorted on the device (samsort.hip on
-// sam_text.h), and the round-1 split then runs on it (umiclust_bam_region_split[_extract]).
+// sam_text.h), and the round-1 split then runs on it (umiclust_bam_region_split[_extract]).  The session's writer
+// deflates its blocks on the device (bgzf.hip on deflate.h), which umiclust_bgzf_deflate runs alone.
 #include <errno.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -14,11 +15,13 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <string_view>
 #include <unordered_map>
 #include <vector>
 
 #include "ctx.h"
+#include "deflate.h"
 #include "inflate.h"
 #include "sam_text.h"
 
@@ -93,6 +96,143 @@ void bgzf_inflate_device(Ctx* c, const uint8_t* d, size_t N, const BgzfPlan& P, 
   c->hip(hipStreamSynchronize(c->st), "sync");
   if (times)
     for (int x = 0; x < 3; x++) times[x] = elapsed_s(c, e[x], e[x + 1]);
+}
+
+// ---- BGZF blocks deflated on the device (bgzf.hip on deflate.h)
+constexpr size_t kBlk = kDeflateIn, kFramedMax = kDeflateFramed;
+// nb blocks -- in[0 .. in_bytes), cut every 0xff00 bytes -- uploaded with their CRC32s, deflated, framed and copied
+// back to out (nb * kFramedMax bytes at most): the bytes a file takes as they are.  D.meta and D.foff say what each
+// block became; a block with a status has no bytes in out.  Returns the framed bytes; times (may be null): upload,
+// kernels, copy back in seconds by HIP events, added to what is there.
+size_t deflate_batch(Ctx* c, DeflateDev& D, const uint8_t* in, size_t in_bytes, size_t nb, const uint32_t* crc,
+                     uint8_t* out, double* times) {
+  D.blk.resize(nb), D.meta.assign(4 * nb, 0), D.foff.assign(nb + 1, 0);
+  for (size_t b = 0; b < nb; b++) D.blk[b] = {(int64_t)(b * kBlk), (uint32_t)std::min(kBlk, in_bytes - b * kBlk), 0};
+  c->hip(hipEventRecord(D.e[0], c->st), "event");
+  c->hip(hipMemcpyAsync(D.d_in.p, in, in_bytes, hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(hipMemcpyAsync(D.d_blk.p, D.blk.data(), nb * sizeof(DeflateBlock), hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(hipMemcpyAsync(D.d_crc.p, crc, nb * 4, hipMemcpyHostToDevice, c->st), "h2d");
+  c->hip(hipEventRecord(D.e[1], c->st), "event");
+  c->hip(launch_bgzf_deflate(D.d_in.p, D.d_blk.p, (int64_t)nb, D.d_slots.p, D.d_tok.p, D.d_meta.p, D.d_fsize.p, c->st),
+         "bgzf deflate");
+  c->hip(launch_scan_i64(D.d_fsize.p, D.d_foff.p, (int64_t)nb, 0, D.d_foff.p + nb, c->st), "scan");
+  c->hip(launch_bgzf_frame(D.d_slots.p, D.d_blk.p, D.d_meta.p, D.d_foff.p, D.d_crc.p, (int64_t)nb, D.d_out.p, c->st),
+         "bgzf frame");
+  c->hip(hipEventRecord(D.e[2], c->st), "event");
+  c->hip(hipMemcpyAsync(D.meta.data(), D.d_meta.p, 4 * nb * 4, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipMemcpyAsync(D.foff.data(), D.d_foff.p, (nb + 1) * 8, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  const size_t total = (size_t)D.foff[nb];
+  if (total > nb * kFramedMax) c->fail(UMICLUST_EDEVICE, "bgzf deflate: %zu framed bytes from %zu blocks", total, nb);
+  if (total) c->hip(hipMemcpyAsync(out, D.d_out.p, total, hipMemcpyDeviceToHost, c->st), "d2h");
+  c->hip(hipEventRecord(D.e[3], c->st), "event");
+  c->hip(hipStreamSynchronize(c->st), "sync");
+  if (times)
+    for (int x = 0; x < 3; x++) times[x] += elapsed_s(c, D.e[x], D.e[x + 1]);
+  return total;
+}
+
+// umiclust_bam_write on the device: the stream cut into batches of c->tun.bgzf_batch blocks; while the device deflates
+// batch k and its bytes are written, the I/O threads gather batch k + 1 into the other staging slot and compute its
+// CRC32s.  A block with a status is redone by zlib in place.  Returns the records written, -1 + err on an I/O
+// failure, -2 where device or pinned memory could not be had (nothing has been written: the caller takes the host
+// writer).
+int64_t write_bgzf_device(Ctx* c, BamSession& S, const uint8_t* keep, const char* path, std::string& err) {
+  const bam::BgzfStream Z = bam::bgzf_stream(S.raw.data(), S.hdr.end, S.roff, keep);
+  const size_t nb = Z.blocks(), batch = std::max<size_t>(1, std::min<size_t>((size_t)c->tun.bgzf_batch, std::max<size_t>(nb, 1)));
+  // the context's buffers, kept across calls as the fastq_filter drop-in keeps its own: allocating the pinned ones
+  // anew cost each write more than its kernels
+  typedef BgzfWriteState::Slot Slot;
+  DeflateDev& D = c->bw.dev;
+  Slot* const slot = c->bw.slot;
+  PinBuf<uint8_t>& out = c->bw.out;
+  bool have = D.ensure(batch) == hipSuccess && out.ensure(batch * kFramedMax) == hipSuccess;
+  for (int k = 0; k < 2; k++) have = have && slot[k].in.ensure(batch * kBlk) == hipSuccess && slot[k].crc.ensure(batch) == hipSuccess;
+  if (!have) {
+    (void)hipGetLastError();
+    c->bw.release();
+    return -2;
+  }
+  const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+  if (fd < 0) {
+    err = std::string("cannot create ") + path;
+    return -1;
+  }
+  struct Fd {
+    int fd;
+    ~Fd() {
+      if (fd >= 0) close(fd);
+    }
+  } guard{fd};
+  // the gather of one batch on a thread of its own (which spreads it over the I/O threads); joined before the batch is
+  // used and before this function is left, however it is left
+  struct Gather {
+    std::thread th;
+    double seconds = 0;
+    void join() {
+      if (th.joinable()) th.join();
+    }
+    ~Gather() { join(); }
+  } g;
+  const int threads = io_threads();
+  auto start_gather = [&](size_t b0) {
+    Slot& s = slot[(b0 / batch) & 1];
+    const size_t b1 = std::min(nb, b0 + batch);
+    g.th = std::thread([&Z, &s, &g, b0, b1, threads]() {
+      const double t0 = now_s();
+      bam::bgzf_gather_crc(Z, b0, b1, s.in.p, s.crc.p, threads);
+      g.seconds += now_s() - t0;
+    });
+  };
+  int64_t* const I = S.write_info;
+  std::fill(I, I + 8, 0);
+  std::fill(S.write_times, S.write_times + 4, 0.0);
+  I[0] = (int64_t)nb;
+  size_t bytes = 0;
+  bool ok = true;
+  std::vector<uint8_t> redo;
+  if (nb) start_gather(0);
+  for (size_t b0 = 0; b0 < nb && ok; b0 += batch) {
+    const size_t b1 = std::min(nb, b0 + batch), n = b1 - b0;
+    Slot& s = slot[(b0 / batch) & 1];
+    g.join();
+    if (b1 < nb) start_gather(b1);
+    const size_t in_bytes = std::min(Z.total, b1 * kBlk) - b0 * kBlk;
+    const size_t total = deflate_batch(c, D, s.in.p, in_bytes, n, s.crc.p, out.p, S.write_times);
+    I[6]++;
+    int64_t bad = 0;
+    for (size_t b = 0; b < n; b++) {
+      if (D.meta[4 * b + 2]) bad++;
+      else I[2 + std::min(2, std::max(0, D.meta[4 * b]))]++;
+    }
+    I[1] += (int64_t)n - bad, I[5] += bad;
+    if (!bad) {
+      ok = bam::write_fd(fd, out.p, total);
+      bytes += total;
+      continue;
+    }
+    for (size_t b = 0; b < n && ok; b++) {  // block by block: a refused block by zlib, in its place
+      if (!D.meta[4 * b + 2]) {
+        const size_t len = (size_t)(D.foff[b + 1] - D.foff[b]);
+        ok = bam::write_fd(fd, out.p + D.foff[b], len);
+        bytes += len;
+      } else {
+        ok = bam::bgzf_block(s.in.p + b * kBlk, D.blk[b].n, redo) && bam::write_fd(fd, redo.data(), redo.size());
+        bytes += redo.size();
+      }
+    }
+  }
+  g.join();
+  S.write_times[3] = g.seconds;
+  ok = ok && bam::write_fd(fd, bam::kBgzfEof, sizeof bam::kBgzfEof);
+  guard.fd = -1;
+  ok = (close(fd) == 0) && ok;
+  if (!ok) {
+    err = std::string("cannot write ") + path;
+    return -1;
+  }
+  I[7] = (int64_t)(bytes + sizeof bam::kBgzfEof);
+  return Z.nkept;
 }
 
 // raw sized to `bytes` with its pages touched by the I/O threads (first touch is the cost of a fresh array this size,
@@ -682,6 +822,39 @@ int64_t umiclust_bgzf_inflate(umiclust_ctx* ctx, const uint8_t* file, int64_t n,
   });
 }
 
+// ---------------------------------------------------------------- k_bgzf_deflate alone (kernel-level entry point, §9g)
+int64_t umiclust_bgzf_deflate(umiclust_ctx* ctx, const uint8_t* data, int64_t n, uint8_t* out, int64_t cap,
+                              int32_t* block_kind, int64_t* n_blocks, double* times) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    if (n < 0 || (n > 0 && !data)) c->fail(UMICLUST_EINVAL, "bad argument");
+    const size_t nb = ((size_t)n + kBlk - 1) / kBlk;
+    const int64_t bound = (int64_t)(nb * kFramedMax + sizeof bam::kBgzfEof);
+    if (n_blocks) *n_blocks = (int64_t)nb;
+    if (cap == 0) return bound;
+    if (!out || cap < bound) c->fail(UMICLUST_ERANGE, "buffer of %lld bytes, %lld needed", (long long)cap, (long long)bound);
+    if (times) times[0] = times[1] = times[2] = 0;
+    size_t total = 0;
+    if (nb) {
+      DeflateDev D;
+      c->hip(D.ensure(nb), "alloc");
+      std::vector<uint32_t> crc(nb);
+      const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)io_threads(), nb));
+      parallel_for(T, [&](int t) {
+        for (size_t b = (size_t)t; b < nb; b += (size_t)T)
+          crc[b] = bam::bgzf_crc32(data + b * kBlk, std::min(kBlk, (size_t)n - b * kBlk));
+      });
+      total = deflate_batch(c, D, data, (size_t)n, nb, crc.data(), out, times);
+      for (size_t b = 0; b < nb; b++) {
+        if (D.meta[4 * b + 2]) c->fail(UMICLUST_EDEVICE, "BGZF block %zu: the encoder refused it (status %d)", b, D.meta[4 * b + 2]);
+        if (block_kind) block_kind[b] = D.meta[4 * b];
+      }
+    }
+    memcpy(out + total, bam::kBgzfEof, sizeof bam::kBgzfEof);
+    return (int64_t)(total + sizeof bam::kBgzfEof);
+  });
+}
+
 // ---------------------------------------------------------------- BAM session: scan with tags, cs group-by, writer (§8f f6)
 namespace {
 // What every open ends with, once S.raw holds the inflated file and d_raw the same bytes on the device: the header,
@@ -952,9 +1125,33 @@ int64_t umiclust_bam_write(umiclust_ctx* ctx, const uint8_t* keep, const char* o
     auto& S = *bam_session(c);
     if (!out_bam || (!keep && !S.roff.empty())) c->fail(UMICLUST_EINVAL, "null argument");
     std::string err;
-    const int64_t k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
+    static const uint8_t none = 0;
+    if (!keep) keep = &none;  // (no records: nothing reads it)
+    int64_t k = c->tun.bgzf_device ? write_bgzf_device(c, S, keep, out_bam, err) : -2;
+    if (k == -2) {  // the host writer: by the switch, or without the memory for a batch
+      k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
+      std::fill(S.write_info, S.write_info + 8, 0);
+      std::fill(S.write_times, S.write_times + 4, 0.0);
+      struct stat sb;
+      if (k >= 0 && stat(out_bam, &sb) == 0) {
+        S.write_info[0] = (int64_t)bam::bgzf_stream(S.raw.data(), S.hdr.end, S.roff, keep).blocks();
+        S.write_info[7] = (int64_t)sb.st_size;
+      }
+    }
     if (k < 0) c->fail(UMICLUST_EIO, "%s", err.c_str());
+    S.wrote = true;
     return k;
+  });
+}
+
+int32_t umiclust_bam_write_info(umiclust_ctx* ctx, int64_t* out, double* times) {
+  uc::Ctx* c = uc::core(ctx);
+  UC_GUARD(c, {
+    auto& S = *bam_session(c);
+    if (!S.wrote) c->fail(UMICLUST_ESTATE, "the session has written no file (umiclust_bam_write)");
+    if (out) memcpy(out, S.write_info, sizeof S.write_info);
+    if (times) memcpy(times, S.write_times, sizeof S.write_times);
+    return UMICLUST_OK;
   });
 }
 

@@ -13,8 +13,9 @@ namespace uc {
 // The switches read below.  The enum and the names come from this one list and get() is the only way from here to the
 // environment, so a switch the reader takes is a switch warn_unknown_env knows.
 #define UC_SWITCHES(X)                                                                                         \
-  X(BAND) X(BLOCK) X(DEBUG) X(FQ_CHUNK) X(IO_THREADS) X(MIXLEN) X(O4) X(OVERLAP_TEST_COLLIDE) X(PAR_MIN) X(PF1) \
-  X(PFPROBE) X(PFPROF) X(PIN) X(REGROW) X(RESOLVE_DUMP) X(RESOLVE_THREADS) X(SPLIT) X(WALK_DUMP)
+  X(BAND) X(BGZF_BATCH) X(BGZF_WRITE) X(BLOCK) X(DEBUG) X(FQ_CHUNK) X(IO_THREADS) X(MIXLEN) X(O4)              \
+  X(OVERLAP_TEST_COLLIDE) X(PAR_MIN) X(PF1) X(PFPROBE) X(PFPROF) X(PIN) X(REGROW) X(RESOLVE_DUMP)              \
+  X(RESOLVE_THREADS) X(SPLIT) X(WALK_DUMP)
 #define UC_ENUM(n) k##n,
 #define UC_NAME(n) "UMICLUST_" #n,
 enum Switch { UC_SWITCHES(UC_ENUM) };
@@ -30,6 +31,8 @@ Tunables read_tunables() {
   if (const char* e = get(kPF1)) t.pf1_lds = std::max(0, atoi(e));
   if (const char* e = get(kREGROW)) t.regrow = std::max(0, atoi(e));
   if (const char* e = get(kFQ_CHUNK)) t.fq_chunk = std::max<int64_t>(1024, std::min<int64_t>(atoll(e), 1ll << 31));
+  if (const char* e = get(kBGZF_WRITE)) t.bgzf_device = strcmp(e, "host") != 0;
+  if (const char* e = get(kBGZF_BATCH)) t.bgzf_batch = std::max(1, std::min(atoi(e), 65536));
   if (const char* e = getenv("LOCAL_WORLD_SIZE")) t.pin = atoi(e) <= 1;
   if (const char* e = get(kPIN)) {
     t.pin = atoi(e) != 0;

@@ -33,6 +33,11 @@ struct Tunables {
   // UMICLUST_FQ_CHUNK: quality bytes per chunk of the fastq_filter drop-in (its memory use: two pinned staging buffers
   // of this size plus one on the device; the file is never held whole), within [1 KiB, 2 GiB]
   int64_t fq_chunk = 64ll << 20;
+  // UMICLUST_BGZF_WRITE=device|host: where umiclust_bam_write deflates its blocks; UMICLUST_BGZF_BATCH:
+  // blocks per batch of the device writer within [1, 65536] (its memory use: two pinned staging buffers of
+  // 0xff00 bytes a block, and on the device the input, one output slot a block and the framed bytes)
+  bool bgzf_device = true;
+  int32_t bgzf_batch = 1024;
   bool pf_prof = false, pf_probe = false;  // UMICLUST_PFPROF, UMICLUST_PFPROBE: the counting kernel's two instruments
   int debug = 0;  // UMICLUST_DEBUG: 1 per-block lines and sequential in-order resolution; 2 the per-bin summary only
   // UMICLUST_WALK_DUMP=<file>: per sorted seqno of the bin, the alignments each strand's walk counted and the

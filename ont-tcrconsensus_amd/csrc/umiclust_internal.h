@@ -342,6 +342,23 @@ struct BgzfBlock {   // one entry per block with ISIZE > 0, built by the host fr
 hipError_t launch_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, const BgzfBlock* blk, int64_t n, uint8_t* out,
                                int32_t* status, hipStream_t st);
 
+// ---- BGZF blocks deflated on the device (bgzf.hip on deflate.h) ----
+struct DeflateBlock {  // one entry per block, in file order
+  int64_t in_off;      // the block's first byte in the input buffer
+  uint32_t n;          // its bytes, 1..0xff00
+  uint32_t pad;
+};
+constexpr int64_t kDeflateSlot = 0xff00 + 8;  // bytes between two blocks' output slots (n + 5 are used; a multiple of 4)
+constexpr int64_t kDeflateGrid = 2048;        // workgroups of k_bgzf_deflate at most; tok holds 0xff00 words for each
+// One wave per block, persistent: slots[b * kDeflateSlot, + payload) = the block's DEFLATE stream (dfl::run of
+// deflate.h), meta[4 b ..] = kind (0 stored, 1 fixed, 2 dynamic), payload bytes, status (0 = ok), flags, fsize[b] =
+// 26 + payload bytes (0 with a status).  tok: min(n, kDeflateGrid) * 0xff00 words of scratch; slots 4-byte aligned.
+hipError_t launch_bgzf_deflate(const uint8_t* in, const DeflateBlock* blk, int64_t n, uint8_t* slots, uint32_t* tok,
+                               int32_t* meta, int64_t* fsize, hipStream_t st);
+// out[foff[b], + fsize[b]) = block b framed: header with BSIZE, payload, crc[b], ISIZE (foff = the scan of fsize)
+hipError_t launch_bgzf_frame(const uint8_t* slots, const DeflateBlock* blk, const int32_t* meta, const int64_t* foff,
+                             const uint32_t* crc, int64_t n, uint8_t* out, hipStream_t st);
+
 // ---- SAM text to the session's raw and roff (samsort.hip on sam_text.h) ----
 // body = the text after the header, n bytes.  Every pointer is device memory.
 namespace sam {

@@ -150,7 +150,8 @@ EXPORTS = [
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
     "umiclust_bgzf_inflate", "umiclust_bam_inflate_info", "umiclust_sam_open", "umiclust_sam_info",
-    "umiclust_bam_region_split", "umiclust_bam_region_split_extract",
+    "umiclust_bam_region_split", "umiclust_bam_region_split_extract", "umiclust_bgzf_deflate",
+    "umiclust_bam_write_info",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -321,6 +322,11 @@ def lib() -> C.CDLL:
     L.umiclust_bgzf_inflate.restype = C.c_int64
     L.umiclust_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int32),
                                         P(C.c_int64), P(C.c_double)]
+    L.umiclust_bgzf_deflate.restype = C.c_int64
+    L.umiclust_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, P(C.c_int32),
+                                        P(C.c_int64), P(C.c_double)]
+    L.umiclust_bam_write_info.restype = C.c_int32
+    L.umiclust_bam_write_info.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     L.umiclust_bam_close.restype = C.c_int32
     L.umiclust_bam_close.argtypes = [C.c_void_p]
     L.umiclust_sam_open.restype = C.c_int64
@@ -755,6 +761,22 @@ class Context:
                 err = e
         return out, status, err
 
+    def bgzf_deflate(self, data, want_info: bool = False):
+        """umiclust_bgzf_deflate: `data` cut into 0xff00-byte blocks, deflated and framed on the
+        device, as the uint8 array of a BGZF file (EOF block included).  want_info: returns (bytes, kinds) instead --
+        one int32 per block, 0 = stored, 1 = fixed, 2 = dynamic."""
+        L = lib()
+        src = np.frombuffer(data, np.uint8)
+        nblk = C.c_int64(-1)
+        cap = self._check(L.umiclust_bgzf_deflate(self._h, src.ctypes.data, len(src), None, 0, None, C.byref(nblk),
+                                                  None), "bgzf_deflate")
+        out, kinds, times = np.zeros(cap, np.uint8), np.zeros(max(nblk.value, 1), np.int32), np.zeros(3)
+        size = self._check(L.umiclust_bgzf_deflate(self._h, src.ctypes.data, len(src), out.ctypes.data, len(out),
+                                                   kinds.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nblk),
+                                                   times.ctypes.data_as(C.POINTER(C.c_double))), "bgzf_deflate")
+        self.bgzf_times = {"h2d_s": float(times[0]), "kernel_s": float(times[1]), "d2h_s": float(times[2])}
+        return (out[:size], kinds[:nblk.value]) if want_info else out[:size]
+
     def align_pairs(self, p: Params, queries, targets, with_ops: bool = False) -> dict:
         qb, qo = _pack(queries)
         tb, to = _pack(targets)
@@ -961,6 +983,16 @@ class BamSession:
         out = np.zeros(3, np.int64)
         self._ctx._check(lib().umiclust_bam_inflate_info(self._ctx._h, _i64(out)), "bam_inflate_info")
         return tuple(int(x) for x in out)
+
+    def write_info(self) -> dict:
+        """umiclust_bam_write_info: the counts and seconds of this session's last write"""
+        out, t = np.zeros(8, np.int64), np.zeros(4, np.float64)
+        self._ctx._check(lib().umiclust_bam_write_info(self._ctx._h, _i64(out), t.ctypes.data_as(C.POINTER(C.c_double))),
+                         "bam_write_info")
+        d = dict(zip(("blocks", "device_blocks", "stored", "fixed", "dynamic", "host_blocks", "batches",
+                      "compressed_bytes"), (int(x) for x in out)))
+        d.update(zip(("upload_s", "kernel_s", "copy_back_s", "gather_crc_s"), (float(x) for x in t)))
+        return d
 
     def sam_info(self) -> dict:
         """umiclust_sam_info: the counts and HIP-event seconds of the umiclust_sam_open that made this session"""
