@@ -83,7 +83,7 @@ std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3
 int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
                    const uint8_t* keep, int threads, std::string& err);
 
-// The pieces of it that the device writer (dropin_bam.cpp) shares.
+// The pieces of it that the device writer (dropin_bgzf.cpp) shares.
 constexpr size_t kBgzfPayload = 0xff00;
 extern const uint8_t kBgzfEof[28];
 // The uncompressed stream as segments of raw: the header bytes, then the kept records (a run of adjacent kept records

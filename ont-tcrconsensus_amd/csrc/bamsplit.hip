@@ -4,7 +4,7 @@
 // Replaces the record loops of filter_and_split_reads_by_region (ont_tcr_consensus/region_split.py:336-435) and of
 // estimate_precision_at_num_subreads (minimap2_align.py:362-435).  Both read the filtered consensus BAM, which the
 // session (bamscan.hip) has scanned already: k_split_cols classifies a record from the session's columns (class,
-// refID, l_seq, reference_length) with the comparisons of k_bam_classify and never walks a CIGAR again; the FASTA
+// refID, l_seq, reference_length) with k_bam_classify's decision chain (bam_bounds.h) and never walks a CIGAR again; the FASTA
 // bytes of the kept records are k_bam_emit's (regionsplit.hip), unchanged.  k_name_suffix parses the decimal field
 // after the last "_" of every query name.  One thread per record, a few bytes each: launch-bound, no LDS, no atomics.
 #include <hip/hip_runtime.h>
@@ -36,23 +36,9 @@ __global__ void k_split_cols(const BamScanCols o, const uint8_t* __restrict__ ra
     c = kBamUnmapped;
   } else if (scan == bam::kScanSecondary) {
     c = kBamSecondary;
-  } else if (ref < 0 || ref >= nref || ref_len[ref] < 0) {
-    c = kBamNoRegion;  // region_length_dict[entry.reference_name] raises
   } else {
-    const double L = (double)ref_len[ref];
-    const double bound = long_bound(L, minov, s5 + s3);
-    if ((double)o.reflen[r] < L * minov) {
-      c = kBamShort;
-    } else if ((double)lseq > bound) {
-      c = kBamLong;
-    } else if (ref_bucket[ref] < 0) {
-      c = kBamNoCluster;
-    } else {
-      c = kBamKept;
-      k = ref_bucket[ref];
-      const int64_t lrn = raw[roff[r] + 12];  // l_read_name, with the NUL; the host refuses a kept record with 0
-      len = 1 + (lrn ? lrn - 1 : 0) + 9 + 1 + (lseq > 0 ? lseq : 4) + 1;  // ">name;strand=s\nSEQ\n" ("None")
-    }
+    const uint32_t lrn = raw[roff[r] + 12];  // l_read_name, with the NUL; the host refuses a kept record with 0
+    region_class(ref, nref, ref_len, ref_bucket, o.reflen[r], lseq, lrn, minov, s5 + s3, c, k, len);
   }
   cls[r] = c;
   bucket[r] = k;

@@ -250,6 +250,13 @@ struct Ctx {
   void hip(hipError_t e, const char* what) {
     if (e != hipSuccess) fail(UMICLUST_EDEVICE, "%s: %s", what, hipGetErrorString(e));
   }
+  // a copy to or from the device queued on st; nothing for 0 bytes
+  void h2d(void* dst, const void* src, size_t bytes) {
+    if (bytes) hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "h2d");
+  }
+  void d2h(void* dst, const void* src, size_t bytes) {
+    if (bytes) hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "d2h");
+  }
 };
 
 // the core of a context (driver.cpp: the upcast); null for null

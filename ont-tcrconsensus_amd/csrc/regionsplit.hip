@@ -24,7 +24,8 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
 }
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
-// long_bound, the `too long` bound as the reference rounds it (:264-267): bam_bounds.h
+// region_class, the decision chain on a primary record (:261-271), with long_bound, the `too long` bound as the
+// reference rounds it (:264-267): bam_bounds.h
 
 // per record: class (kBamUnmapped ... kBamNoCluster), cluster, output bytes
 __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* __restrict__ roff, int64_t n,
@@ -44,8 +45,6 @@ __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* _
     c = kBamUnmapped;
   } else if (flag & 0x900u) {
     c = kBamSecondary;
-  } else if (ref < 0 || ref >= nref || ref_len[ref] < 0) {
-    c = kBamNoRegion;  // region_length_dict[entry.reference_name] raises
   } else {
     const uint8_t* cg = p + 32 + lrn;
     int64_t rl = 0;
@@ -56,19 +55,7 @@ __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* _
     // pysam's reference_length = bam_endpos - pos, and htslib's bam_endpos counts a zero reference span (no CIGAR,
     // or only I/S/H/P ops) as 1: such a record is 1 base long and drops as short (:261-263)
     if (rl == 0) rl = 1;
-    const double L = (double)ref_len[ref];
-    const double bound = long_bound(L, minov, s5 + s3);
-    if ((double)rl < L * minov) {
-      c = kBamShort;
-    } else if ((double)lseq > bound) {
-      c = kBamLong;
-    } else if (ref_cluster[ref] < 0) {
-      c = kBamNoCluster;  // region_cluster_dict[entry.reference_name] raises
-    } else {
-      c = kBamKept;
-      k = ref_cluster[ref];
-      len = 1 + (int64_t)(lrn - 1) + 9 + 1 + (lseq > 0 ? lseq : 4) + 1;  // ">name;strand=s\nSEQ\n" ("None")
-    }
+    region_class(ref, nref, ref_len, ref_cluster, rl, lseq, lrn, minov, s5 + s3, c, k, len);
   }
   cls[r] = c;
   cluster[r] = k;

@@ -190,3 +190,55 @@ def test_split_and_suffix_errors(tmp_path):
     counts = np.zeros(4, np.int64)
     assert L.umiclust_bam_split(h, None, 0, None, None, None, 0, None, 0.9, 0, 0, _lib._i64(counts), None, None, None,
                                 0) == ESTATE
+
+
+def test_refusal_order_of_the_six_split_entries(tmp_path):
+    """What each of the six split entries refuses first, by raw ABI calls.  Round 2 (umiclust_bam_split[_extract]) asks
+    for the session before it looks at an argument; the round-1 session entries check their arguments and the UMI
+    patterns first and ask for the session afterwards; in all of them the umis_per_* check and the patterns come before
+    the remaining arguments; and a counter capacity below the cluster ids is UMICLUST_ERANGE only after the files are
+    written and the counters below the capacity are filled."""
+    ERANGE = -34
+    ctx = _v.context()
+    case = BY_REGION["kept_without_seq"]
+    bam.write_bam(str(tmp_path / "in.bam"), [tuple(r) for r in case["refs"]], case["records"])
+    names, lengths = [nm for nm, _ in case["regions"]], [ln for _, ln in case["regions"]]
+    L, h, P = _lib.lib(), ctx._h, _lib.C.POINTER
+    c_i32, c_u8 = _lib.C.c_int32, _lib.C.c_uint8
+    nm = (_lib.C.c_char_p * 2)(*[x.encode() for x in names])
+    ln, cl = np.asarray(lengths, np.int64), np.asarray([0, 1], np.int32)
+    counts, rpc, upc = np.zeros(4, np.int64), np.full(2, -1, np.int64), np.zeros(2, np.int64)
+    regions = (2, nm, _lib._i64(ln), cl.ctypes.data_as(P(c_i32)))
+    paths = (_lib.C.c_char_p * 2)(*[str(tmp_path / ("b%d.fasta" % k)).encode() for k in range(2)])
+    out = str(tmp_path).encode()
+    umi = (73, 68, 3, b"TTTVVVVTTVVVVTTVVVVTTVVVVTTT", b"AAABBBBAABBBBAABBBBAABBBBAAA")
+    last = lambda: L.umiclust_last_error(h).decode()
+    with ctx.bam_open(tmp_path / "in.bam"):
+        # the umis_per_bucket check comes before the region arguments (nregions < 0 here)
+        assert L.umiclust_bam_split_extract(h, None, -1, None, None, None, 2, paths, 0.95, 73, 68, *umi,
+                                            _lib._i64(counts), _lib._i64(rpc), None, None, None, 0) == EINVAL
+        # capacity 1, cluster ids 0 and 1: refused after the files and the counters
+        assert L.umiclust_region_split(h, str(tmp_path / "in.bam").encode(), *regions, 0.95, 73, 68, out,
+                                       _lib._i64(counts), _lib._i64(rpc), 1, None, None, 0) == ERANGE
+        assert "cluster ids up to 1 exceed the counter capacity" in last()
+        assert sorted(os.listdir(tmp_path)) == ["in.bam", "region_cluster0.fasta", "region_cluster1.fasta"]
+        assert (tmp_path / "region_cluster0.fasta").read_text() == case["out_files"]["region_TRBV1_1.fasta"]
+        assert (tmp_path / "region_cluster1.fasta").read_text() == case["out_files"]["region_TRBV2_2.fasta"]
+        assert rpc.tolist() == [3, -1] and counts.tolist() == [0, 6, 1, 0]
+    # no session
+    assert L.umiclust_bam_split(h, None, 0, None, None, None, 0, None, 0.9, 0, 0, None, None, None, None, 0) == ESTATE
+    assert L.umiclust_bam_split_extract(h, None, 0, None, None, None, 0, None, 0.9, 0, 0, *umi, None, None, None, None,
+                                        None, 0) == ESTATE
+    tail = (_lib._i64(counts), _lib._i64(rpc))
+    assert L.umiclust_bam_region_split(h, *regions, 0.95, 73, 68, None, *tail, 2, None, None, 0) == EINVAL
+    assert L.umiclust_bam_region_split_extract(h, *regions, 0.95, 73, 68, *umi, None, *tail, _lib._i64(upc), 2, None,
+                                               None, 0) == EINVAL
+    assert last() == "bad argument"
+    assert L.umiclust_bam_region_split(h, *regions, 0.95, 73, 68, out, *tail, 2, None, None, 0) == ESTATE
+    assert L.umiclust_bam_region_split_extract(h, *regions, 0.95, 73, 68, *umi, out, *tail, _lib._i64(upc), 2, None,
+                                               None, 0) == ESTATE
+    long_umi = umi[:3] + (b"N" * 65, umi[4])
+    assert L.umiclust_bam_region_split_extract(h, *regions, 0.95, 73, 68, *long_umi, None, *tail, _lib._i64(upc), 2,
+                                               None, None, 0) == EINVAL
+    assert last() == "UMI patterns of 1..64 symbols are supported (got 65)"
+    assert sorted(os.listdir(tmp_path)) == ["in.bam", "region_cluster0.fasta", "region_cluster1.fasta"]
