@@ -53,7 +53,9 @@ typedef struct umiclust_params {
   int32_t match;          /* --match */
   int32_t mismatch;       /* --mismatch */
   int32_t gap_open[6];    /* --gapopen, indexed by UMICLUST_QL..UMICLUST_TR */
-  int32_t gap_ext[6];     /* --gapext */
+  int32_t gap_ext[6];     /* --gapext.  The 16-bit aligners take |match| + |mismatch| <= 66 and, per index,
+                             gap_open >= 0, gap_ext >= 0, gap_open + gap_ext <= 66; anything else is
+                             UMICLUST_EINVAL (DESIGN.md section 6 has the full condition) */
   int32_t strand_both;    /* --strand both */
   int32_t qmask_dust;     /* --qmask dust (vsearch default) */
   int32_t clusterout_sort;/* --clusterout_sort */

@@ -2174,9 +2174,11 @@ __global__ __launch_bounds__(64 * kTwWaves) void k_trace_wave(DevSeqs s, const u
   const uint32_t qword = lane < kCodeWords ? qcp[lane] : 0u, tword = lane < kCodeWords ? tcp[lane] : 0u;
   for (int i = lane; i < ql; i += 64) S.qraw[i] = (uint8_t)((qcp[i >> 3] >> ((i & 7) * 4)) & 15u);
   // identical sequences of one-hot codes (a member equal to its centroid: about (1 - error)^L of them): the all-M
-  // path is the only optimum -- any other path trades matches for gaps or mismatches -- so its ops, matches and
-  // internal length are known without the DP (codes past the length are 0 in both)
-  if (ql == tl) {
+  // path is the one backtrack16 takes -- any other path trades matches for gaps or mismatches -- so its ops, matches
+  // and internal length are known without the DP (codes past the length are 0 in both).  That needs a match to be the
+  // best move there is (match >= mismatch, match >= 0; gap penalties are >= 0 by validate()): a path into cell (i, i)
+  // then scores at most (i + 1) match, the all-M value, and ties go to the diagonal.  Other scorings run the DP.
+  if (ql == tl && sc.match >= sc.mismatch && sc.match >= 0) {
     bool same = qword == tword;
     if (same && lane < kCodeWords)
 #pragma unroll

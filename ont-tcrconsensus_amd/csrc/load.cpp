@@ -30,9 +30,28 @@ void validate(umiclust_ctx* c, const umiclust_params& p) {
   if (p.policy_threads != 0 && p.policy_threads != 1) c->fail(UMICLUST_EINVAL, "policy_threads must be 0 or 1");
   if (p.policy_threads && (p.threads < 1 || p.threads > kMaxBlock))
     c->fail(UMICLUST_EINVAL, "policy_threads = 1 needs 1 <= threads <= %d", kMaxBlock);
-  int mx = std::abs(p.match) + std::abs(p.mismatch);
-  for (int k = 0; k < 6; k++) mx = std::max(mx, p.gap_open[k] + p.gap_ext[k]);
-  if (mx * 2 * kMaxLen > 15000) c->fail(UMICLUST_EINVAL, "scores too large for 16-bit DP");
+  // The alignment kernels' 16-bit cells (DESIGN.md section 6, K3P range argument).  Gap penalties are costs: a
+  // negative component passes a bound on the sums alone and does not fit the cells.
+  int64_t mx = (int64_t)std::abs((int64_t)p.match) + std::abs((int64_t)p.mismatch);
+  for (int k = 0; k < 6; k++) {
+    if (p.gap_open[k] < 0) c->fail(UMICLUST_EINVAL, "gap_open[%d] = %d is negative", k, p.gap_open[k]);
+    if (p.gap_ext[k] < 0) c->fail(UMICLUST_EINVAL, "gap_ext[%d] = %d is negative", k, p.gap_ext[k]);
+    mx = std::max(mx, (int64_t)p.gap_open[k] + p.gap_ext[k]);
+  }
+  if (mx * 2 * kMaxLen > 15000)
+    c->fail(UMICLUST_EINVAL, "scores too large for 16-bit DP (|match| + |mismatch| and every gap_open + gap_ext <= %d)",
+            15000 / (2 * kMaxLen));
+  // The closed boundary's state is the constant -16000 in the packed kernels' frame H'' = H - (mismatch + ge[QI]) (row
+  // + 1) + ...; it has to stay below column 0's real cells, the lowest of which is the boundary column's last row
+  // plus one diagonal move.  Only a positive mismatch score beside large extension penalties comes near.
+  if (!p.policy_boundary_open) {
+    const int64_t low = p.gap_open[1] + (int64_t)(kMaxLen - 1) * (p.gap_ext[1] + p.mismatch + p.gap_ext[2]) +
+                        std::max(0, p.mismatch - p.match) + std::max(p.gap_open[2], p.gap_open[4]);
+    if (low > 16000)
+      c->fail(UMICLUST_EINVAL, "policy_boundary_open = 0 with mismatch %d, gap_ext[1] %d and gap_ext[2] %d: column 0 "
+              "falls below the 16-bit boundary state (use policy_boundary_open = 1)", p.mismatch, p.gap_ext[1],
+              p.gap_ext[2]);
+  }
 }
 
 namespace {

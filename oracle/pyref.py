@@ -45,9 +45,28 @@ def _sub(p, a, b):
     return p.match if x == y else p.mismatch
 
 
-def nw(p, q, t):
+# One switch per rule of nw / trim_id.  Every switch at its default is the operation; one switch flipped is what a
+# kernel with exactly that mistake computes (tests/test_align_ref_cpu.py shows that each flip is visible in the cases
+# the alignment kernels are given).
+NW_RULES = ("f_ge",              # F > h made >=
+            "e_ge",              # E > h made >=
+            "i_before_d",        # I tried before D
+            "extup_ge",          # F extension > opening made >=
+            "extleft_ge",        # E extension > opening made >=
+            "last_row_interior",  # the last row's terminal penalties replaced by the interior ones
+            "last_col_interior",  # the same for the last column
+            "boundary_flip")     # policy_boundary_open inverted
+TRIM_RULES = ("keep_right",      # the trailing run not trimmed
+              "keep_left",       # the leading run not trimmed
+              "no_single_run")   # the left >= cols rule dropped
+RULES = NW_RULES + TRIM_RULES
+
+
+def nw(p, q, t, rules=()):
     """Gotoh DP with vsearch's path bits, then backtrack16. Returns (score, cigar, matches)."""
+    assert all(r in RULES for r in rules), rules
     n, m = len(q), len(t)
+    bopen = bool(p.boundary_open) != ("boundary_flip" in rules)
     H = [[0] * (m + 1) for _ in range(n + 1)]  # H[i+1][j+1]
     for j in range(m):
         H[0][j + 1] = -(p.go[QL] + (j + 1) * p.ge[QL])
@@ -56,26 +75,32 @@ def nw(p, q, t):
     D = {}
     Fcol = []
     for j in range(m):
-        r = TR if j == m - 1 else TI
-        Fcol.append(H[0][j + 1] - (p.go[r] + p.ge[r]) if p.boundary_open else NEG)
+        r = TR if j == m - 1 and "last_col_interior" not in rules else TI
+        Fcol.append(H[0][j + 1] - (p.go[r] + p.ge[r]) if bopen else NEG)
     for i in range(n):
-        rq = QR if i == n - 1 else QI
-        E = H[i + 1][0] - (p.go[rq] + p.ge[rq]) if p.boundary_open else NEG
+        rq = QR if i == n - 1 and "last_row_interior" not in rules else QI
+        E = H[i + 1][0] - (p.go[rq] + p.ge[rq]) if bopen else NEG
         for j in range(m):
-            rt = TR if j == m - 1 else TI
+            rt = TR if j == m - 1 and "last_col_interior" not in rules else TI
             diag = H[i][j] + _sub(p, q[i], t[j])
             F = Fcol[j]
-            best, up, left = diag, F > diag, False
-            if up:
-                best = F
-            if E > best:
-                best, left = E, True
+            best, up, left = diag, False, False
+            if "i_before_d" in rules:
+                if E >= best if "e_ge" in rules else E > best:
+                    best, left = E, True
+                if F >= best if "f_ge" in rules else F > best:
+                    best, up, left = F, True, False
+            else:
+                if F >= best if "f_ge" in rules else F > best:
+                    best, up = F, True
+                if E >= best if "e_ge" in rules else E > best:
+                    best, left = E, True
             H[i + 1][j + 1] = best
             fo, fe = best - (p.go[rt] + p.ge[rt]), F - p.ge[rt]
-            extup = fe > fo
+            extup = fe >= fo if "extup_ge" in rules else fe > fo
             Fcol[j] = fe if extup else fo
             eo, ee = best - (p.go[rq] + p.ge[rq]), E - p.ge[rq]
-            extleft = ee > eo
+            extleft = ee >= eo if "extleft_ge" in rules else ee > eo
             E = ee if extleft else eo
             D[(i, j)] = (up, left, extup, extleft)
     ops = []
@@ -105,13 +130,13 @@ def nw(p, q, t):
     return H[n][m], cigar, matches
 
 
-def trim_id(cigar, matches):
+def trim_id(cigar, matches, rules=()):
     """align_trim + iddef 2 on a vsearch CIGAR string."""
     runs = [(int(n) if n else 1, o) for n, o in re.findall(r"(\d*)([MDI])", cigar)]
     cols = sum(r for r, _ in runs)
-    left = runs[0][0] if runs[0][1] != "M" else 0
-    right = runs[-1][0] if runs[-1][1] != "M" else 0
-    if left >= cols:
+    left = runs[0][0] if runs[0][1] != "M" and "keep_left" not in rules else 0
+    right = runs[-1][0] if runs[-1][1] != "M" and "keep_right" not in rules else 0
+    if left >= cols and "no_single_run" not in rules:
         right = 0
     internal = cols - left - right
     return (100.0 * matches / internal if internal > 0 else 0.0), internal

@@ -58,7 +58,10 @@ def _pairs(seed, n, qlens, tl_lo=16, tl_hi=72, ambig=False):
                                              (1, False, _lib.MAX_LEN), (2, False, _lib.MAX_LEN),
                                              (1, True, _lib.MAX_LEN), (2, True, _lib.MAX_LEN)])
 def test_align_pairs_vs_oracle(gpu_ctx, preset, ambig, hi):
-    """Every query length 32..hi (one kernel instantiation each), targets 16..hi."""
+    """Every query length 32..hi, targets 16..hi.  align_pairs launches once per query length, so the 3,000 pairs
+    arrive in launches of a few dozen: at the default UMICLUST_BAND (140,000 pairs) the non-ambiguous cases run
+    k_align_band<QL> and the ambiguous ones k_align<QL, true>, one instantiation per length each, and with_ops runs
+    k_trace_wave.  k_align_pk is not reached here; tests/test_gpu_align_kernels.py selects it with UMICLUST_BAND=0."""
     p = _lib.params(preset, 0.93, 32, hi)
     op = orc.params(preset, 0.93, 32, hi)
     qs, ts = _pairs(100 + preset + 10 * ambig + hi, 3000, list(range(32, hi + 1)), tl_hi=hi, ambig=ambig)
