@@ -625,6 +625,28 @@ int32_t umiclust_consensus(umiclust_ctx *ctx, const umiclust_params *p, const ch
 int32_t umiclust_prep(umiclust_ctx *ctx, const umiclust_params *p, const char *seqs,
                       const int64_t *offsets, int64_t n, char *masked, uint16_t *kmers,
                       int32_t kstride, int32_t *nk);
+/* Everything K1 (k_prep_wave) writes, copied out as the device holds it (an added function, ABI version unchanged).
+ * Records are ASCII, record i at seqs[offsets[i] .. offsets[i+1]), 0..UMICLUST_MAX_LEN long, taken as they are (no
+ * length filter); p->qmask_dust alone is read of p.  perm (n int32, or NULL: the identity) is a permutation of
+ * 0..n-1: output row s is record perm[s], the way umiclust_prepare launches the kernel over its length sort.  Each
+ * output may be NULL:
+ *   masked[s * UMICLUST_MAX_LEN ...]   the output characters of row s (its length's worth; the rest is not written)
+ *   codes[(s * 2 + strand) * 14 ...]   the 4-bit codes, 8 per u32, nibble t of word w = position 8 w + t, 0 past the
+ *                                      record; strand 1 is the complemented reverse
+ *   lens[s]                            the record's length
+ *   kmers[(s * 2 + strand) * kstride ...], nk[s * 2 + strand]   the unique 8-mers in the order the device holds them
+ *                                      (ascending), nk of them; kstride >= UMICLUST_MAX_LEN - 7, and kmers needs nk
+ *   changed[s]                         1: the output characters of row s differ from its input (what the cluster-file
+ *                                      writer reads to fetch single rows)
+ *   flags[0], flags[1]                 bit 0: some output symbol is not A, C, G, T or U (selects the aligner family);
+ *                                      the number of rows with changed = 1 (selects the writer's branch)
+ * The flag words are allocated and zeroed by the call.  UMICLUST_EINVAL: perm is no permutation, decreasing offsets,
+ * a short kstride; UMICLUST_ERANGE: a record longer than UMICLUST_MAX_LEN (nothing is launched).  Works beside the
+ * context's load: a loaded or clustered context stays as it was. */
+int32_t umiclust_prep_outputs(umiclust_ctx *ctx, const umiclust_params *p, const char *seqs,
+                              const int64_t *offsets, int64_t n, const int32_t *perm, char *masked,
+                              uint32_t *codes, uint8_t *lens, uint16_t *kmers, int32_t kstride, int32_t *nk,
+                              uint8_t *changed, uint32_t *flags);
 
 /* The k-mer prefilter alone (k_pf_count, k_pf_full, k_pf_merge), launched as a whole pass of the pipeline launches
  * it, on the sequences of the current single-bin load (umiclust_load / umiclust_prepare; sequences given longest

@@ -72,6 +72,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
       t_cons = now_s() - t1;
     });
   double t_mask = 0.0;
+  int64_t n_rows = 0;  // masked rows downloaded for the cluster files: none, the changed rows alone, or every row
   if (clusters_prefix) {
     // vsearch prints the DUST-masked (upper-cased) db sequence.  Where no sequence changed (prepare counted them:
     // nothing masked, input already upper case) that is the input's own bytes, so the 112 B-per-UMI masked
@@ -88,6 +89,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
         for (int32_t s = 0; s < c->n; s++)
           if (chg[s]) mrow[s] = r++;
         masked.resize((size_t)r * kMaxLen);
+        n_rows = r;
         for (int32_t s = 0; s < c->n; s++)
           if (mrow[s] >= 0)
             c->hip(hipMemcpyAsync(masked.data() + (size_t)mrow[s] * kMaxLen, c->d_masked.p + (size_t)s * kMaxLen,
@@ -95,6 +97,7 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
         c->hip(hipStreamSynchronize(c->st), "sync");
       } else {
         masked.resize((size_t)c->n * kMaxLen);
+        n_rows = c->n;
         c->hip(hipMemcpy(masked.data(), c->d_masked.p, masked.size(), hipMemcpyDeviceToHost), "d2h masked");
       }
       t_mask = now_s() - tm;
@@ -107,9 +110,9 @@ int64_t run_fasta_impl(umiclust_ctx* c, const umiclust_params* p, const char* in
   if (cons_err) std::rethrow_exception(cons_err);
   const double t_write = now_s() - t1;
   if (c->tun.debug)
-    fprintf(stderr, "umiclust: file path: read %.3f s, cluster %.3f s, masked download %.3f s (%lld changed), "
-                    "cluster files done at %.3f s, consout (beside them) at %.3f s\n", t_read, t1 - t0 - t_read, t_mask,
-            (long long)c->n_changed, t_files, t_cons);
+    fprintf(stderr, "umiclust: file path: read %.3f s, cluster %.3f s, masked download %.3f s (%lld changed, %lld of %lld "
+                    "rows), cluster files done at %.3f s, consout (beside them) at %.3f s\n", t_read, t1 - t0 - t_read,
+            t_mask, (long long)c->n_changed, (long long)n_rows, (long long)c->n, t_files, t_cons);
   if (log_path) {
     const umiclust_stats& s = c->stats;
     int64_t nt = 0, singles = 0;

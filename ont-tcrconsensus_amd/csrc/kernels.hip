@@ -160,6 +160,11 @@ __global__ __launch_bounds__(64) void k_prep_wave(const char* __restrict__ ascii
       __syncthreads();  // s_w is rewritten by the next window
     }
   }
+  // a byte that is no letter has no case: dust()'s tolower leaves it as it is inside a masked interval, and
+  // unique.cc's islower test drops no k-mer for it, so it counts as unmasked from here on
+  auto letter = [](uint8_t c) { return (uint8_t)((c | 0x20) - 'a') < 26; };
+  m0 = m0 && letter(ch0);
+  m1 = m1 && letter(ch1);
   // output characters: dust() upper-cases the sequence and lower-cases the masked intervals
   auto fin = [&](uint8_t c, bool m) -> uint8_t {
     const uint8_t up = (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c;

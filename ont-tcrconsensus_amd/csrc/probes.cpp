@@ -1,6 +1,6 @@
 // probes.cpp -- the kernel-level entry points of the C ABI, for the test suite: one prefilter or one whole pass
 // through the pipeline's own steps (umiclust_prefilter, umiclust_pass), and the alignment, consensus and preparation
-// kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep).
+// kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep, umiclust_prep_outputs).
 #include <algorithm>
 #include <cstddef>
 
@@ -82,30 +82,39 @@ static void fetch_lists(umiclust_ctx* c, const Pass& P, const PfCapture& cap, si
 
 // What umiclust_align_pairs, umiclust_consensus and umiclust_prep share: n records on the device, beside whatever load
 // the context holds, and k_prep over them.  The uploads have completed when probe_prep returns, the kernel is queued.
+// perm (n record indices, or null: the identity) names the record of each output row, as prepare_impl's sort does;
+// with `changed` the per-row "output differs from input" flags are written too (they need `masked`).
 struct ProbeSeqs {
   DevBuf<char> d_a, d_m;
   DevBuf<int64_t> d_o;
+  DevBuf<int32_t> d_perm;
   DevBuf<uint32_t> d_codes, d_amb;
-  DevBuf<uint8_t> d_lens, d_nk;
+  DevBuf<uint8_t> d_lens, d_nk, d_chg;
   DevBuf<uint16_t> d_km;
   DevSeqs ds() const { return DevSeqs{d_codes.p, d_lens.p, d_km.p, d_nk.p}; }
 };
 static void probe_prep(umiclust_ctx* c, ProbeSeqs& S, const char* seqs, const int64_t* offs, int64_t n, int dust,
-                       bool masked, bool amb) {
+                       bool masked, bool amb, const int32_t* perm = nullptr, bool changed = false) {
   std::vector<int64_t> rel;
   upload_seqs(c, seqs, offs, n, S.d_a, S.d_o, rel, c->st);
+  if (perm) {
+    c->hip(S.d_perm.ensure((size_t)n + 1), "alloc");
+    if (n > 0) c->hip(hipMemcpyAsync(S.d_perm.p, perm, (size_t)n * 4, hipMemcpyHostToDevice, c->st), "h2d");
+  }
   c->hip(hipStreamSynchronize(c->st), "sync");  // `rel` goes out of scope
   c->hip(S.d_codes.ensure((size_t)n * 2 * kCodeWords + 1), "alloc");
   c->hip(S.d_lens.ensure((size_t)n + 1), "alloc");
   c->hip(S.d_km.ensure((size_t)n * 2 * kKmerStride + 1), "alloc");
   c->hip(S.d_nk.ensure((size_t)n * 2 + 1), "alloc");
   if (masked) c->hip(S.d_m.ensure((size_t)n * kMaxLen + 1), "alloc");
+  if (changed) c->hip(S.d_chg.ensure((size_t)n + 1), "alloc");
   if (amb) {
     c->hip(S.d_amb.ensure(2), "alloc");
     c->hip(hipMemsetAsync(S.d_amb.p, 0, 8, c->st), "memset");
   }
-  c->hip(launch_prep(S.d_a.p, S.d_o.p, nullptr, (int32_t)n, dust, S.d_codes.p, S.d_lens.p, S.d_km.p, S.d_nk.p,
-                     masked ? S.d_m.p : nullptr, amb ? S.d_amb.p : nullptr, c->st),
+  c->hip(launch_prep(S.d_a.p, S.d_o.p, perm ? S.d_perm.p : nullptr, (int32_t)n, dust, S.d_codes.p, S.d_lens.p,
+                     S.d_km.p, S.d_nk.p, masked ? S.d_m.p : nullptr, amb ? S.d_amb.p : nullptr, c->st,
+                     changed ? S.d_chg.p : nullptr),
          "prep");
 }
 // an alignment result word: matches, the alignment's internal length, the score
@@ -464,6 +473,52 @@ int32_t umiclust_prep(umiclust_ctx* c, const umiclust_params* p, const char* seq
           for (int x = 0; x < nkv[(size_t)2 * i + s] && x < kstride; x++)
             kmers[(size_t)(2 * i + s) * kstride + x] = km[(size_t)(2 * i + s) * kKmerStride + x];
       }
+    }
+    return UMICLUST_OK;
+  });
+}
+
+// Everything K1 writes, as the device holds it, for n records launched the way prepare_impl launches a load's: output
+// row s is record perm[s].  Every access of the kernel is bounded by the record lengths and by perm, so both are checked
+// here before anything is launched.
+int32_t umiclust_prep_outputs(umiclust_ctx* c, const umiclust_params* p, const char* seqs, const int64_t* offsets,
+                              int64_t n, const int32_t* perm, char* masked, uint32_t* codes, uint8_t* lens,
+                              uint16_t* kmers, int32_t kstride, int32_t* nk, uint8_t* changed, uint32_t* flags) {
+  UC_GUARD(c, {
+    if (!p || n < 0 || (n > 0 && (!seqs || !offsets))) c->fail(UMICLUST_EINVAL, "null argument");
+    if (n > (1 << 30)) c->fail(UMICLUST_ERANGE, "too many records");
+    if (kmers && (kstride < kMaxKmers || !nk)) c->fail(UMICLUST_EINVAL, "kmers needs nk and kstride >= %d", kMaxKmers);
+    for (int64_t i = 0; i < n; i++) {
+      const int64_t L = offsets[i + 1] - offsets[i];
+      if (L < 0) c->fail(UMICLUST_EINVAL, "record %lld: offsets decrease", (long long)i);
+      if (L > kMaxLen) c->fail(UMICLUST_ERANGE, "record %lld longer than %d", (long long)i, kMaxLen);
+    }
+    if (perm) {
+      std::vector<uint8_t> seen((size_t)n, 0);
+      for (int64_t s = 0; s < n; s++) {
+        if (perm[s] < 0 || perm[s] >= n || seen[perm[s]]) c->fail(UMICLUST_EINVAL, "perm is no permutation of 0..n-1");
+        seen[perm[s]] = 1;
+      }
+    }
+    ProbeSeqs S;
+    probe_prep(c, S, seqs, offsets, n, p->qmask_dust, true, true, perm, true);
+    auto out = [&](void* dst, const void* src, size_t bytes) {
+      if (dst && bytes) c->hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st), "d2h");
+    };
+    std::vector<uint16_t> km(kmers ? (size_t)n * 2 * kKmerStride : 0);
+    std::vector<uint8_t> nkv((size_t)n * 2);
+    out(masked, S.d_m.p, (size_t)n * kMaxLen);
+    out(codes, S.d_codes.p, (size_t)n * 2 * kCodeWords * 4);
+    out(lens, S.d_lens.p, (size_t)n);
+    out(changed, S.d_chg.p, (size_t)n);
+    out(flags, S.d_amb.p, 8);
+    out(kmers ? km.data() : nullptr, S.d_km.p, km.size() * 2);
+    out(nk ? nkv.data() : nullptr, S.d_nk.p, nkv.size());
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    for (int64_t r = 0; nk && r < 2 * n; r++) {
+      nk[r] = nkv[(size_t)r];
+      if (nkv[(size_t)r] > kMaxKmers) c->fail(UMICLUST_EDEVICE, "row %lld: the kernel reported %d k-mers", (long long)r, nk[r]);
+      if (kmers) memcpy(kmers + (size_t)r * kstride, km.data() + (size_t)r * kKmerStride, (size_t)nkv[(size_t)r] * 2);
     }
     return UMICLUST_OK;
   });

@@ -143,6 +143,7 @@ EXPORTS = [
     "umiclust_load", "umiclust_stage", "umiclust_prepare", "umiclust_set_priority", "umiclust_cluster", "umiclust_fetch", "umiclust_load_bins", "umiclust_cluster_bin", "umiclust_cluster_pack",
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
+    "umiclust_prep_outputs",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_filter_stats", "umiclust_fastq_filter_stats_argv",
     "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
@@ -253,6 +254,9 @@ def lib() -> C.CDLL:
                                      P(C.c_int32), P(C.c_uint8), C.c_void_p, P(C.c_int32), C.c_int32, C.c_void_p,
                                      P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_int64,
                                      P(C.c_int64)]
+    L.umiclust_prep_outputs.restype = C.c_int32
+    L.umiclust_prep_outputs.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64] + \
+        [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3
     L.umiclust_prep.restype = C.c_int32
     L.umiclust_prep.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64, C.c_void_p,
                                 P(C.c_uint16), C.c_int32, P(C.c_int32)]
@@ -927,6 +931,33 @@ class Context:
         return dict(masked=[mb[o[i]:o[i + 1]].decode() for i in range(n)],
                     kmers=[[list(km[(2 * i + s) * kst:(2 * i + s) * kst + nk[2 * i + s]]) for s in range(2)]
                            for i in range(n)])
+
+    def prep_outputs(self, p: Params, seqs, perm=None) -> dict:
+        """umiclust_prep_outputs: everything K1 writes for the records (row s is record perm[s]), as the device holds
+        it -- masked (bytes per row), codes [n, 2, 14], lens, kmers (per row and strand, device order), nk [n, 2],
+        changed, ambig and n_changed (the two flag words)."""
+        b, o = _pack(seqs)
+        n = len(o) - 1
+        pm = None if perm is None else np.ascontiguousarray(perm, np.int32)
+        if pm is not None and len(pm) != n:
+            raise ValueError("perm: one entry per record")
+        kst = MAX_LEN - 7
+        masked = np.zeros((max(n, 1), MAX_LEN), np.uint8)
+        codes = np.full((max(n, 1), 2, MAX_LEN // 8), 0xffffffff, np.uint32)
+        lens = np.full(max(n, 1), 255, np.uint8)
+        km = np.zeros((max(n, 1), 2, kst), np.uint16)
+        nk = np.full((max(n, 1), 2), -1, np.int32)
+        changed = np.full(max(n, 1), 255, np.uint8)
+        flags = np.full(2, 0xffffffff, np.uint32)
+        rc = lib().umiclust_prep_outputs(self._h, C.byref(p), b.ctypes.data, _i64(o), n,
+                                         None if pm is None else pm.ctypes.data, masked.ctypes.data, codes.ctypes.data,
+                                         lens.ctypes.data, km.ctypes.data, kst, nk.ctypes.data, changed.ctypes.data,
+                                         flags.ctypes.data)
+        self._check(rc, "prep_outputs")
+        lens, nk = lens[:n], nk[:n]
+        return dict(masked=[masked[s, :lens[s]].tobytes().decode("latin-1") for s in range(n)], codes=codes[:n],
+                    lens=lens, kmers=[[[int(x) for x in km[s, st, :nk[s, st]]] for st in range(2)] for s in range(n)],
+                    nk=nk, changed=changed[:n], ambig=int(flags[0]), n_changed=int(flags[1]))
 
 
 class BamSession:
