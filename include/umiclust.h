@@ -647,6 +647,33 @@ int32_t umiclust_prep_outputs(umiclust_ctx *ctx, const umiclust_params *p, const
                               const int64_t *offsets, int64_t n, const int32_t *perm, char *masked,
                               uint32_t *codes, uint8_t *lens, uint16_t *kmers, int32_t kstride, int32_t *nk,
                               uint8_t *changed, uint32_t *flags);
+/* The region join of umiclust_overlap_regions with every array its kernels leave behind copied out (an added
+ * function, ABI version unchanged).  seqs, offsets, n, region_start, nregions, total and maxcount are that function's,
+ * and the kernels run in its order: the table passes with the member lists, then the region pairs.  The table has
+ * m slots, m = the smallest power of two that is >= 1024 and >= 2 n, which the caller computes to size its buffers.
+ * Each output may be NULL:
+ *   hash[n]      the 64-bit hash of each sequence under the accepted seed
+ *   region[n]    its region
+ *   slot[n]      its slot in the table: equal for byte-equal sequences only
+ *   rep_of[n]    the representative of its slot: the lowest index of an equal sequence
+ *   cnt[m]       sequences per slot
+ *   start[m+1]   the exclusive prefix sum of cnt (all 0 for n = 0, where no kernel runs)
+ *   members[n]   the sequence indices bucketed by slot: slot s holds members[start[s] .. start[s+1]), ascending where
+ *                it holds 2..32 of them
+ *   big[*nbig]   the slots with more than 32 members, which a workgroup each takes over, in any order
+ *   info[0..2]   m, the table passes that ran, the seed of the accepted pass
+ * hash_bits (1..64): the hashes of the first table pass keep that many low bits, so different sequences collide and
+ * the pass is repeated under the next seed with all 64 (64: the production run; 8: what the environment variable
+ * UMICLUST_OVERLAP_TEST_COLLIDE sets for every call).  n_cap, m_cap and big_cap are the caller's capacities: of the
+ * arrays over sequences, of cnt (start has one more) and of big.  UMICLUST_ERANGE: n_cap < n, m_cap < m, or more
+ * than big_cap large buckets (info is written, in the last case *nbig too).  UMICLUST_EINVAL: what umiclust_overlap_regions refuses
+ * (region boundaries that do not span [0, n] or decrease, nregions outside 1..UMICLUST_OVERLAP_MAX_REGIONS), hash_bits
+ * outside 1..64, a negative capacity. */
+int32_t umiclust_overlap_probe(umiclust_ctx *ctx, const char *seqs, const int64_t *offsets, int64_t n,
+                               const int64_t *region_start, int32_t nregions, int32_t hash_bits, int64_t n_cap,
+                               int64_t m_cap, int64_t big_cap, uint64_t *hash, int32_t *region, int64_t *slot,
+                               int64_t *rep_of, uint32_t *cnt, uint32_t *start, uint32_t *members, uint32_t *big,
+                               int64_t *nbig, int64_t *total, int32_t *maxcount, uint64_t *info);
 
 /* The k-mer prefilter alone (k_pf_count, k_pf_full, k_pf_merge), launched as a whole pass of the pipeline launches
  * it, on the sequences of the current single-bin load (umiclust_load / umiclust_prepare; sequences given longest

@@ -293,6 +293,26 @@ inline void append_set(const char* s, const int64_t* o, int64_t n, std::vector<c
   }
 }
 
+// Region overlap (f3, dropin_overlap.cpp): n sequences of nreg regions on the device and the buffers of the accepted
+// hash-table pass.  overlap_table checks the arguments (UMICLUST_EINVAL: null arguments, region boundaries that do not
+// span [0, n] or decrease), sizes the table (m = mask + 1 = the smallest power of two >= max(1024, 2 n)), uploads, and
+// runs launch_overlap_table under one seed after another until no two different sequences share a hash.  hash_bits
+// < 64 keeps that many low bits of the first pass's hashes (umiclust_overlap_probe; UMICLUST_OVERLAP_TEST_COLLIDE
+// keeps 8); `passes` and `seed` tell how many passes ran and which seed was accepted.
+struct OvRun {
+  DevBuf<char> d_seq;
+  DevBuf<int64_t> d_off, d_rs, d_slot;
+  DevBuf<uint64_t> d_hash;
+  DevBuf<int32_t> d_reg;
+  DevBuf<unsigned long long> d_keys, d_rep;
+  DevBuf<uint32_t> d_cnt, d_start, d_cursor, d_bsum, d_members, d_coll, d_big, d_nbig;
+  OvBuffers B{};
+  uint64_t mask = 0, seed = 0;
+  int passes = 0;
+};
+void overlap_table(Ctx* c, OvRun& R, const char* seqs, const int64_t* offs, int64_t n, const int64_t* rstart,
+                   int32_t nreg, bool csr, int hash_bits = 64);
+
 }  // namespace uc
 
 // Body of an entry point: selects the device; what the body throws becomes the ABI's error code and last-error text.

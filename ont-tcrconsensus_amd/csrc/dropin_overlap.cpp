@@ -5,21 +5,8 @@
 
 using namespace uc;
 
-namespace {
-// n sequences of nreg regions on the device, one table pass (re-seeded on a 64-bit hash collision)
-struct OvRun {
-  DevBuf<char> d_seq;
-  DevBuf<int64_t> d_off, d_rs, d_slot;
-  DevBuf<uint64_t> d_hash;
-  DevBuf<int32_t> d_reg;
-  DevBuf<unsigned long long> d_keys, d_rep;
-  DevBuf<uint32_t> d_cnt, d_start, d_cursor, d_bsum, d_members, d_coll, d_big, d_nbig;
-  OvBuffers B{};
-  uint64_t mask = 0;
-};
-
-void overlap_table(Ctx* c, OvRun& R, const char* seqs, const int64_t* offs, int64_t n,
-                   const int64_t* rstart, int32_t nreg, bool csr) {
+void uc::overlap_table(Ctx* c, OvRun& R, const char* seqs, const int64_t* offs, int64_t n, const int64_t* rstart,
+                       int32_t nreg, bool csr, int hash_bits) {
   if (n < 0 || nreg < 1 || (n > 0 && (!seqs || !offs)) || !rstart) c->fail(UMICLUST_EINVAL, "null argument");
   if (rstart[0] != 0 || rstart[nreg] != n) c->fail(UMICLUST_EINVAL, "region boundaries must span [0, n]");
   for (int32_t r = 0; r < nreg; r++)
@@ -43,19 +30,23 @@ void overlap_table(Ctx* c, OvRun& R, const char* seqs, const int64_t* offs, int6
   // a 64-bit collision between two different sequences is detected exactly; the next seed is tried
   const uint64_t seeds[4] = {0x243f6a8885a308d3ull, 0x13198a2e03707344ull, 0xa4093822299f31d0ull,
                              0x082efa98ec4e6c89ull};
-  const bool test_collide = env_overlap_test_collide();  // first pass: 8-bit hashes
+  // first pass: 8-bit hashes under UMICLUST_OVERLAP_TEST_COLLIDE, hash_bits of them where the probe asks for fewer
+  if (hash_bits == 64 && env_overlap_test_collide()) hash_bits = 8;
+  const uint64_t first = hash_bits < 64 ? (1ull << hash_bits) - 1 : ~0ull;
+  R.passes = 0;
   for (int k = 0; k < 4; k++) {
     uint32_t coll = 0;
-    const uint64_t hmask = (test_collide && k == 0) ? 0xffull : ~0ull;
+    const uint64_t hmask = k == 0 ? first : ~0ull;
     c->hip(launch_overlap_table(R.d_seq.p, R.d_off.p, n, R.d_rs.p, nreg, seeds[k], hmask, R.mask, R.B, csr, &coll,
                                 c->st),
            "overlap table");
     c->stats.n_overlap_passes++;
+    R.passes++;
+    R.seed = seeds[k];
     if (!coll) return;
   }
   c->fail(UMICLUST_EDEVICE, "overlap: 64-bit hash collisions under four seeds");
 }
-}  // namespace
 
 int32_t umiclust_overlap_counts(umiclust_ctx* ctx, const char* s1, const int64_t* off1, int64_t n1, const char* s2,
                                 const int64_t* off2, int64_t n2, int64_t* counts) {

@@ -1,6 +1,7 @@
 // probes.cpp -- the kernel-level entry points of the C ABI, for the test suite: one prefilter or one whole pass
 // through the pipeline's own steps (umiclust_prefilter, umiclust_pass), and the alignment, consensus and preparation
-// kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep, umiclust_prep_outputs).
+// kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep, umiclust_prep_outputs), and
+// the region overlap join's intermediate arrays (umiclust_overlap_probe).
 #include <algorithm>
 #include <cstddef>
 
@@ -519,6 +520,72 @@ int32_t umiclust_prep_outputs(umiclust_ctx* c, const umiclust_params* p, const c
       nk[r] = nkv[(size_t)r];
       if (nkv[(size_t)r] > kMaxKmers) c->fail(UMICLUST_EDEVICE, "row %lld: the kernel reported %d k-mers", (long long)r, nk[r]);
       if (kmers) memcpy(kmers + (size_t)r * kstride, km.data() + (size_t)r * kKmerStride, (size_t)nkv[(size_t)r] * 2);
+    }
+    return UMICLUST_OK;
+  });
+}
+
+// The region join's own sequence (overlap_table with the CSR, then launch_overlap_pairs, as umiclust_overlap_regions
+// runs them) with every array the kernels leave behind copied out.  No kernel runs for n = 0, as there: start is
+// then all zero by definition.
+int32_t umiclust_overlap_probe(umiclust_ctx* c, const char* seqs, const int64_t* offsets, int64_t n,
+                               const int64_t* region_start, int32_t nregions, int32_t hash_bits, int64_t n_cap,
+                               int64_t m_cap, int64_t big_cap, uint64_t* hash, int32_t* region, int64_t* slot,
+                               int64_t* rep_of, uint32_t* cnt, uint32_t* start, uint32_t* members, uint32_t* big,
+                               int64_t* nbig, int64_t* total, int32_t* maxcount, uint64_t* info) {
+  UC_GUARD(c, {
+    if (nregions < 1 || nregions > UMICLUST_OVERLAP_MAX_REGIONS || hash_bits < 1 || hash_bits > 64 || n_cap < 0 ||
+        m_cap < 0 || big_cap < 0)
+      c->fail(UMICLUST_EINVAL, "umiclust_overlap_probe: 1..%d regions, 1..64 hash bits, capacities >= 0",
+              UMICLUST_OVERLAP_MAX_REGIONS);
+    OvRun R;
+    overlap_table(c, R, seqs, offsets, n, region_start, nregions, true, hash_bits);
+    const int64_t m = (int64_t)R.mask + 1;
+    if (info) info[0] = (uint64_t)m, info[1] = (uint64_t)R.passes, info[2] = R.seed;
+    if (n_cap < n || m_cap < m)
+      c->fail(UMICLUST_ERANGE, "umiclust_overlap_probe: %lld sequences and %lld slots, room for %lld and %lld",
+              (long long)n, (long long)m, (long long)n_cap, (long long)m_cap);
+    const size_t cells = (size_t)nregions * nregions;
+    DevBuf<unsigned long long> d_total;
+    DevBuf<uint32_t> d_max;
+    alloc_each(c, cells, d_total, d_max);
+    c->hip(hipMemsetAsync(d_total.p, 0, cells * 8, c->st), "memset");
+    c->hip(hipMemsetAsync(d_max.p, 0, cells * 4, c->st), "memset");
+    c->hip(hipMemsetAsync(R.d_nbig.p, 0, 4, c->st), "memset");
+    if (n > 0) c->hip(launch_overlap_pairs(R.B, R.mask, nregions, d_total.p, d_max.p, c->st), "overlap pairs");
+    auto out = [&](void* dst, const void* src, size_t bytes) {
+      if (dst) c->d2h(dst, src, bytes);
+    };
+    std::vector<unsigned long long> rep(rep_of ? (size_t)m : 0);
+    std::vector<int64_t> sl(rep_of ? (size_t)n : 0);
+    std::vector<uint32_t> mx(maxcount ? cells : 0);
+    uint32_t nb = 0;
+    out(hash, R.d_hash.p, (size_t)n * 8);
+    out(region, R.d_reg.p, (size_t)n * 4);
+    out(slot, R.d_slot.p, (size_t)n * 8);
+    out(cnt, R.d_cnt.p, (size_t)m * 4);
+    if (n > 0) out(start, R.d_start.p, ((size_t)m + 1) * 4);
+    else if (start) std::fill(start, start + m + 1, 0u);
+    out(members, R.d_members.p, (size_t)n * 4);  // after k_ov_pairs: the small buckets are sorted
+    out(total, d_total.p, cells * 8);
+    out(maxcount ? mx.data() : nullptr, d_max.p, cells * 4);
+    out(rep_of ? rep.data() : nullptr, R.d_rep.p, (size_t)m * 8);
+    out(rep_of ? sl.data() : nullptr, R.d_slot.p, (size_t)n * 8);
+    c->d2h(&nb, R.d_nbig.p, 4);
+    c->hip(hipStreamSynchronize(c->st), "sync");
+    for (size_t x = 0; maxcount && x < cells; x++) maxcount[x] = (int32_t)mx[x];
+    for (int64_t i = 0; rep_of && i < n; i++) {
+      if (sl[i] < 0 || sl[i] >= m) c->fail(UMICLUST_EDEVICE, "sequence %lld: slot %lld", (long long)i, (long long)sl[i]);
+      rep_of[i] = (int64_t)rep[(size_t)sl[i]];
+    }
+    if (nbig) *nbig = nb;
+    if ((int64_t)nb > (int64_t)n / (kOvSmallBucket + 1))
+      c->fail(UMICLUST_EDEVICE, "umiclust_overlap_probe: %u large buckets of %lld sequences", nb, (long long)n);
+    if (big) {
+      c->d2h(big, R.d_big.p, (size_t)std::min<int64_t>(nb, big_cap) * 4);
+      c->hip(hipStreamSynchronize(c->st), "sync");
+      if ((int64_t)nb > big_cap)
+        c->fail(UMICLUST_ERANGE, "umiclust_overlap_probe: %u large buckets, room for %lld", nb, (long long)big_cap);
     }
     return UMICLUST_OK;
   });

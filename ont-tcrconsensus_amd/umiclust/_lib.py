@@ -143,7 +143,7 @@ EXPORTS = [
     "umiclust_load", "umiclust_stage", "umiclust_prepare", "umiclust_set_priority", "umiclust_cluster", "umiclust_fetch", "umiclust_load_bins", "umiclust_cluster_bin", "umiclust_cluster_pack",
     "umiclust_fetch_bin", "umiclust_overlap_counts", "umiclust_overlap_regions", "umiclust_extract_umis",
     "umiclust_extract_umis_file", "umiclust_region_split", "umiclust_align_pairs", "umiclust_prep",
-    "umiclust_prep_outputs",
+    "umiclust_prep_outputs", "umiclust_overlap_probe",
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_filter_stats", "umiclust_fastq_filter_stats_argv",
     "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
@@ -257,6 +257,9 @@ def lib() -> C.CDLL:
     L.umiclust_prep_outputs.restype = C.c_int32
     L.umiclust_prep_outputs.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64] + \
         [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3
+    L.umiclust_overlap_probe.restype = C.c_int32
+    L.umiclust_overlap_probe.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), C.c_int64, P(C.c_int64), C.c_int32,
+                                         C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 12
     L.umiclust_prep.restype = C.c_int32
     L.umiclust_prep.argtypes = [C.c_void_p, P(Params), C.c_void_p, P(C.c_int64), C.c_int64, C.c_void_p,
                                 P(C.c_uint16), C.c_int32, P(C.c_int32)]
@@ -579,6 +582,38 @@ class Context:
                                                    _i64(tot), mx.ctypes.data_as(C.POINTER(C.c_int32))),
                     "overlap_regions")
         return tot.reshape(R, R), mx.reshape(R, R)
+
+    def overlap_probe(self, regions, hash_bits: int = 64, caps=None) -> dict:
+        """umiclust_overlap_probe: the region join of overlap_regions with the arrays its kernels leave behind -- hash,
+        region, slot, rep_of, members [n]; cnt [m], start [m + 1]; big (the slots handed to the workgroup kernel);
+        total, maxcount [R, R]; m, passes, seed.  caps = (n_cap, m_cap, big_cap) overrides the capacities passed."""
+        flat = [s for r in regions for s in r]
+        buf, off = _pack(flat)
+        n, R = len(flat), len(regions)
+        rs = np.zeros(R + 1, np.int64)
+        np.cumsum([len(r) for r in regions], out=rs[1:])
+        m = 1024
+        while m < 2 * n:
+            m *= 2
+        nb = n // 33 + 1
+        u64 = np.iinfo(np.uint64).max
+        o = dict(hash=np.full(max(n, 1), u64, np.uint64), region=np.full(max(n, 1), -1, np.int32),
+                 slot=np.full(max(n, 1), -1, np.int64), rep_of=np.full(max(n, 1), -1, np.int64),
+                 cnt=np.full(m, 0xffffffff, np.uint32), start=np.full(m + 1, 0xffffffff, np.uint32),
+                 members=np.full(max(n, 1), 0xffffffff, np.uint32), big=np.full(nb, 0xffffffff, np.uint32),
+                 nbig=np.full(1, -1, np.int64), total=np.full(R * R, -1, np.int64),
+                 maxcount=np.full(R * R, -1, np.int32), info=np.zeros(3, np.uint64))
+        n_cap, m_cap, big_cap = caps if caps is not None else (n, m, nb)
+        rc = lib().umiclust_overlap_probe(self._h, buf.ctypes.data, _i64(off), n, _i64(rs), R, hash_bits, n_cap, m_cap,
+                                          big_cap, *(o[k].ctypes.data for k in (
+                                              "hash", "region", "slot", "rep_of", "cnt", "start", "members", "big",
+                                              "nbig", "total", "maxcount", "info")))
+        self._check(rc, "overlap_probe")
+        nbig = int(o["nbig"][0])
+        return dict(hash=o["hash"][:n], region=o["region"][:n], slot=o["slot"][:n], rep_of=o["rep_of"][:n],
+                    cnt=o["cnt"], start=o["start"], members=o["members"][:n], big=o["big"][:nbig],
+                    total=o["total"].reshape(R, R), maxcount=o["maxcount"].reshape(R, R), m=int(o["info"][0]),
+                    passes=int(o["info"][1]), seed=int(o["info"][2]))
 
     def extract_umis(self, seqs, a5: int = 73, a3: int = 68, k: int = 3, fwd: str = "", rev: str = "") -> np.ndarray:
         """[n, 6] int32: (dist, start, end) of the 5' and 3' UMI per read (-1: none), window coordinates."""
