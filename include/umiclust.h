@@ -532,7 +532,7 @@ int32_t umiclust_bam_close(umiclust_ctx *ctx);
  * SO:coordinate, GO: dropped, an @HD line added where there is none, no @PG) and parses the aux f values.  The session
  * is then exactly the one umiclust_bam_open builds from the sorted BAM: every umiclust_bam_* call works on it, and
  * umiclust_bam_write with every record kept is the drop-in for `samtools sort -o`.  `samtools index` (:138) and
- * `samtools flagstat` (:152-153) are not replaced: a caller that wants them writes the BAM.
+ * `samtools flagstat` (:152-153) are umiclust_bam_write_index and umiclust_bam_flagstat on the same session (below).
  * The rules (csrc/sam_text.h, policy O9) restate htslib's sam_parse1; every refusal names the 1-based line and the
  * field, and leaves no session: UMICLUST_EFORMAT for a malformed header or line (fewer than 11 fields, an empty line,
  * a name over 254 bytes, an unknown RNAME / RNEXT -- named --, a malformed number or CIGAR, QUAL and SEQ of different
@@ -566,7 +566,60 @@ int64_t umiclust_bam_region_split_extract(umiclust_ctx *ctx, int32_t nregions, c
                                           int64_t *reads_per_cluster, int64_t *umis_per_cluster, int32_t ncluster_cap,
                                           uint8_t *region_detected, char *missing_name, int32_t missing_cap);
 
+/* ---- the .bai index and flagstat of the session, on the device (added functions, ABI version
+ * unchanged) ---- */
+/* Replaces `samtools index` (minimap2_align.py:138, :247).  umiclust_bam_write(keep, out_bam), then the index of
+ * exactly that file at out_bai (NULL: out_bam + ".bai"): both writers record the compressed offset of every block
+ * they frame, the device computes per kept record its bin, its windows and the virtual offsets of its start and end,
+ * detects the runs of one bin, sorts them and fills the linear index; the host finishes (small bins move to their
+ * parent, neighbouring chunks merge) and writes the file.  The rules are policy O10 (csrc/bam_index.h): the SAM
+ * specification's §5.1.1 and §5.2 and htslib's finish, restated; bins are written in ascending number with the
+ * pseudo-bin 37450 last, and n_no_coor always.  Returns the records written.  The kept records must be
+ * coordinate-sorted (a session from umiclust_sam_open is): UMICLUST_EFORMAT "unsorted" names the first record that is
+ * not; UMICLUST_ERANGE names a placed record with pos < 0 or an end past 2^29, which a .bai cannot address;
+ * UMICLUST_EIO the index path.  On any of them the BAM stays and no file is left at out_bai. */
+int64_t umiclust_bam_write_index(umiclust_ctx *ctx, const uint8_t *keep, const char *out_bam, const char *out_bai);
+/* `samtools index bam_file`: the file's blocks are walked and inflated on the device as umiclust_bam_open does it, the
+ * header and the record offsets parsed (no aux scan, no cs grouping), and the index written to out_bai (NULL: bam_file +
+ * ".bai").  An open session is not touched, and none is needed.  Returns the number of records; the error codes are
+ * umiclust_bam_open's and umiclust_bam_write_index's. */
+int64_t umiclust_bam_index_file(umiclust_ctx *ctx, const char *bam_file, const char *out_bai);
+/* Replaces `samtools flagstat` (:152-153) on the open session: the records with keep[r] != 0 (keep NULL: all).
+ * out[32] (may be NULL): counter 2 k + w = row k of the text below, w = 0 QC-passed, 1 QC-failed (flag & 0x200).  text:
+ * the 16 lines of samtools >= 1.13 (policy O11: total, primary, secondary, supplementary, duplicates, primary
+ * duplicates, mapped, primary mapped, paired in sequencing, read1, read2, properly paired, with itself and mate mapped,
+ * singletons, with mate mapped to a different chr, the same with mapQ>=5), NUL-terminated.  cap == 0: returns the bytes
+ * text needs; otherwise fills it and returns them (UMICLUST_ERANGE when cap is smaller).  The records need no order. */
+int32_t umiclust_bam_flagstat(umiclust_ctx *ctx, const uint8_t *keep, int64_t *out, char *text, int64_t cap);
+/* DIAGNOSTIC of the context's last index, probe or flagstat call (UMICLUST_ESTATE before any): out[0..3] = kept
+ * records, runs, chunks after the finish, linear-index windows; times[0..3] = seconds by HIP events of the upload, the
+ * kernels and the copies back, and by the host's clock of the finish with the file.  Either may be NULL.
+ * tools/bam_index_bench.py reads the figures of DESIGN.md §9h through it */
+int32_t umiclust_bam_index_info(umiclust_ctx *ctx, int64_t *out, double *times);
+
 /* ---- kernel-level entry points (parity tests) ---- */
+/* The index kernels on the open session's kept records (keep NULL: all) under a block table the caller gives, with
+ * everything they leave behind (csrc/bamindex.hip).  The table lists every block of the imagined file in order: block
+ * b starts at compressed offset coff[b] and holds the stream bytes [ustart[b], ustart[b + 1]); the last entry is the
+ * block after the data (the EOF block): ustart[nblocks - 1] = header bytes + kept record bytes.  UMICLUST_EINVAL for a
+ * table that does not start at 0, decreases, holds more than 64 KiB in a block or ends elsewhere.  Each output may be
+ * NULL:
+ *   bin, u, v, status   per kept record, in order: its bin (0 without a reference), the virtual offsets of its start
+ *                       and end, 0 or 1 = unsorted against the kept record before, 2 = outside 0 .. 2^29, 3 = a
+ *                       reference the header does not hold
+ *   runs, sorted_runs   4 int64 a run (reference, bin, start, end): in file order, and stably sorted by (reference, bin)
+ *   n_intv, mapped, unmapped   per reference of the header
+ *   linear              the linear indexes one after another, reference by reference
+ *   counters[32]        as umiclust_bam_flagstat's
+ *   info[0..5]          kept records, runs, windows, the first refused record (-1: none), its status, n_no_coor
+ * A refused record is no error here: info names it, the per-record outputs, the counts and the counters are filled,
+ * and runs, sorted_runs and linear are not.  UMICLUST_ERANGE: more runs than run_cap or more windows than linear_cap
+ * (info is written). */
+int32_t umiclust_bam_index_probe(umiclust_ctx *ctx, const uint8_t *keep, const int64_t *coff, const int64_t *ustart,
+                                 int64_t nblocks, int32_t *bin, uint64_t *u, uint64_t *v, int32_t *status,
+                                 int64_t *runs, int64_t *sorted_runs, int64_t run_cap, int64_t *n_intv,
+                                 uint64_t *linear, int64_t linear_cap, int64_t *mapped, int64_t *unmapped,
+                                 int64_t *counters, int64_t *info);
 /* The quality kernel alone: record i = quals[offsets[i] .. offsets[i+1]); ee_fx[i] = sum over its bytes b with
  * 0 <= b - fastq_ascii <= 93 of llrint(10^(-(b - fastq_ascii)/10) * 2^40) (other bytes add 0), qlo[i] / qhi[i] = its
  * smallest / largest raw byte (255 / 0 for an empty record).  Records of more than 2^22 bytes: UMICLUST_ERANGE. */

@@ -1,6 +1,7 @@
-// bam_dev.h -- what the four host files of the BAM drop-ins need of each other: dropin_bgzf.cpp (BGZF on the device),
-// dropin_sam.cpp (SAM text to raw), dropin_split.cpp (the region split) and dropin_bam.cpp (the session).
-// Declarations only.
+// bam_dev.h -- what the five host files of the BAM drop-ins need of each other: dropin_bgzf.cpp (BGZF on the device),
+// dropin_sam.cpp (SAM text to raw), dropin_split.cpp (the region split), dropin_bam.cpp (the session) and
+// dropin_index.cpp (the .bai index and flagstat).  Declarations only.  (The radix sort that dropin_sam.cpp and
+// dropin_index.cpp share is launch_sam_sort of umiclust_internal.h, which this header brings in through ctx.h.)
 #pragma once
 #include <string>
 #include <string_view>
@@ -26,8 +27,12 @@ struct InputBytes {
 uint8_t* alloc_touched(RawBuf& raw, size_t bytes);
 // What both BAM readers start with: the file inflated on the device into d_raw and copied back into `raw`.  info: BGZF
 // blocks, blocks inflated on the device, compressed bytes uploaded; *t_upload (may be null): seconds of the upload.
+// table (may be null): the file's block table as bam_index.h reads it.
+struct BlockTable {
+  std::vector<int64_t> coff, ustart;
+};
 bool read_bam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_t>& d_raw, int64_t info[3],
-                        double* t_upload);
+                        double* t_upload, BlockTable* table = nullptr);
 // umiclust_bam_write on the device: the records written, -1 + err, or -2 for the caller to take the host writer
 int64_t write_bgzf_device(Ctx* c, BamSession& S, const uint8_t* keep, const char* path, std::string& err);
 

@@ -321,8 +321,10 @@ void bgzf_gather_crc(const BgzfStream& S, size_t b0, size_t b1, uint8_t* dst, ui
 }
 
 int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
-                   const uint8_t* keep, int threads, std::string& err) {
+                   const uint8_t* keep, int threads, std::string& err, std::vector<int64_t>* coff) {
   const BgzfStream S = bgzf_stream(raw, header_end, roff, keep);
+  int64_t at = 0;
+  if (coff) coff->clear();
   const size_t total = S.total;
   const int64_t nkept = S.nkept;
   const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
@@ -352,8 +354,13 @@ int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, cons
     work();
     for (auto& x : th) x.join();
     ok = !failed;
-    for (size_t b = b0; b < b1 && ok; b++) ok = write_fd(fd, out[b - b0].data(), out[b - b0].size());
+    for (size_t b = b0; b < b1 && ok; b++) {
+      ok = write_fd(fd, out[b - b0].data(), out[b - b0].size());
+      if (coff) coff->push_back(at);
+      at += (int64_t)out[b - b0].size();
+    }
   }
+  if (coff) coff->push_back(at);
   ok = ok && write_fd(fd, kBgzfEof, sizeof kBgzfEof);
   ok = (close(fd) == 0) && ok;
   if (!ok) {

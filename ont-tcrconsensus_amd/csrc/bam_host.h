@@ -79,9 +79,10 @@ std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3
 // The file at `path` inflates to raw[0, header_end) followed by the records r with keep[r] != 0 (record r =
 // raw[roff[r], roff[r] + 4 + block_size)), in input order: blocks of at most 0xff00 payload bytes, raw deflate, the BC
 // extra field with BSIZE, CRC32 and ISIZE, then the 28-byte EOF block.  Blocks are compressed on `threads` threads
-// and written in order.  Returns the number of records written, -1 + err on an I/O failure.
+// and written in order.  Returns the number of records written, -1 + err on an I/O failure.  coff (may be null): the
+// compressed offset of every block written, the EOF block's last.
 int64_t write_bgzf(const char* path, const uint8_t* raw, size_t header_end, const std::vector<int64_t>& roff,
-                   const uint8_t* keep, int threads, std::string& err);
+                   const uint8_t* keep, int threads, std::string& err, std::vector<int64_t>* coff = nullptr);
 
 // The pieces of it that the device writer (dropin_bgzf.cpp) shares.
 constexpr size_t kBgzfPayload = 0xff00;

@@ -218,6 +218,9 @@ struct BamSession {
   bool wrote = false;
   int64_t write_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double write_times[4] = {0, 0, 0, 0};
+  // the compressed offset of every block that write framed, the EOF block's last: what
+  // umiclust_bam_write_index reads the virtual offsets from
+  std::vector<int64_t> write_coff;
   // a session opened from SAM text (umiclust_sam_open): lines, records, text bytes uploaded, aux f
   // values the host parsed; seconds of upload, lines + measure, sort, encode, copy back
   bool from_sam = false;
@@ -236,6 +239,13 @@ struct Ctx {
   FqState fq;
   BamSession bs;
   BgzfWriteState bw;
+  // the last index or flagstat call: kept records, runs, chunks after the finish, windows; seconds of
+  // upload, kernels, copy back (HIP events) and of the host's finish
+  struct IndexInfo {
+    bool have = false;
+    int64_t out[4] = {0, 0, 0, 0};
+    double times[4] = {0, 0, 0, 0};
+  } ix;
   // (the members go after the derived context's destructor, which selects the device)
 
   void fail(int code, const char* fmt, ...) {

@@ -298,7 +298,7 @@ int64_t umiclust_bam_write(umiclust_ctx* ctx, const uint8_t* keep, const char* o
     if (!keep) keep = &none;  // (no records: nothing reads it)
     int64_t k = c->tun.bgzf_device ? write_bgzf_device(c, S, keep, out_bam, err) : -2;
     if (k == -2) {  // the host writer: by the switch, or without the memory for a batch
-      k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err);
+      k = bam::write_bgzf(out_bam, S.raw.data(), S.hdr.end, S.roff, keep, io_threads(), err, &S.write_coff);
       std::fill(S.write_info, S.write_info + 8, 0);
       std::fill(S.write_times, S.write_times + 4, 0.0);
       struct stat sb;

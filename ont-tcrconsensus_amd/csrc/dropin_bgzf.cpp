@@ -26,6 +26,7 @@ namespace {
 struct BgzfPlan {
   std::vector<BgzfBlock> blk;
   std::vector<int64_t> file_idx;
+  BlockTable table;  // every block, the empty ones too
   int64_t n_blocks = 0, total = 0;
 };
 bool bgzf_plan(const uint8_t* d, size_t N, BgzfPlan& P) {
@@ -35,12 +36,14 @@ bool bgzf_plan(const uint8_t* d, size_t N, BgzfPlan& P) {
   P.n_blocks = (int64_t)boff.size();
   for (size_t b = 0; b < boff.size(); b++) {
     const size_t xlen = (size_t)d[boff[b] + 10] | ((size_t)d[boff[b] + 11] << 8);
+    P.table.coff.push_back((int64_t)boff[b]), P.table.ustart.push_back(P.total);
     if (isz[b]) {
       P.blk.push_back({(int64_t)(boff[b] + 12 + xlen), P.total, (uint32_t)(bsz[b] - 12 - xlen - 8), isz[b]});
       P.file_idx.push_back((int64_t)b);
     }
     P.total += isz[b];
   }
+  if (isz.empty() || isz.back()) P.table.coff.push_back((int64_t)N), P.table.ustart.push_back(P.total);  // no EOF block
   return true;
 }
 // d[0 .. N) uploaded (with 8 zero bytes of padding, rounded up to whole words), P's blocks inflated into d_raw
@@ -165,6 +168,7 @@ int64_t uc::write_bgzf_device(Ctx* c, BamSession& S, const uint8_t* keep, const 
   std::fill(I, I + 8, 0);
   std::fill(S.write_times, S.write_times + 4, 0.0);
   I[0] = (int64_t)nb;
+  S.write_coff.assign(nb + 1, 0);
   size_t bytes = 0;
   bool ok = true;
   std::vector<uint8_t> redo;
@@ -184,11 +188,13 @@ int64_t uc::write_bgzf_device(Ctx* c, BamSession& S, const uint8_t* keep, const 
     }
     I[1] += (int64_t)n - bad, I[5] += bad;
     if (!bad) {
+      for (size_t b = 0; b < n; b++) S.write_coff[b0 + b] = (int64_t)bytes + D.foff[b];
       ok = bam::write_fd(fd, out.p, total);
       bytes += total;
       continue;
     }
     for (size_t b = 0; b < n && ok; b++) {  // block by block: a refused block by zlib, in its place
+      S.write_coff[b0 + b] = (int64_t)bytes;
       if (!D.meta[4 * b + 2]) {
         const size_t len = (size_t)(D.foff[b + 1] - D.foff[b]);
         ok = bam::write_fd(fd, out.p + D.foff[b], len);
@@ -201,6 +207,7 @@ int64_t uc::write_bgzf_device(Ctx* c, BamSession& S, const uint8_t* keep, const 
   }
   g.join();
   S.write_times[3] = g.seconds;
+  S.write_coff[nb] = (int64_t)bytes;
   ok = ok && bam::write_fd(fd, bam::kBgzfEof, sizeof bam::kBgzfEof);
   guard.fd = -1;
   ok = (close(fd) == 0) && ok;
@@ -263,7 +270,7 @@ bool uc::InputBytes::read(const char* path, bool regular_only) {
 // copied back to the host, where the header parser, record_offsets, the session and the writer read it.  False for
 // what io::inflate_bgzf returned false for, and for a path that is no regular file.
 bool uc::read_bam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_t>& d_raw, int64_t info[3],
-                            double* t_upload) {
+                            double* t_upload, BlockTable* table) {
   InputBytes in;
   BgzfPlan P;
   if (!in.read(path, true) || !bgzf_plan(in.p, in.n, P)) return false;
@@ -274,6 +281,7 @@ bool uc::read_bam_on_device(Ctx* c, const char* path, RawBuf& raw, DevBuf<uint8_
   bgzf_inflate_device(c, in.p, in.n, P, d_raw, status, host_dst, t);
   info[0] = P.n_blocks, info[1] = (int64_t)P.blk.size(), info[2] = (int64_t)in.n;
   if (t_upload) *t_upload = t[0];
+  if (table) *table = std::move(P.table);
   for (int32_t s : status)
     if (s) return false;
   return true;

@@ -395,4 +395,45 @@ hipError_t launch_sam_encode(const uint8_t* body, const int64_t* start, const ui
 // raw[at[i] .. + 4) = bits[i], little-endian
 hipError_t launch_sam_put_f(uint8_t* raw, const int64_t* at, const uint32_t* bits, int64_t n, hipStream_t st);
 
+// ---- the .bai index and flagstat of the session's kept records (bamindex.hip on bam_index.h) ----
+// Every pointer is device memory.  keep may be null (every record); the block table (bam_index.h) may be empty
+// (nblocks = 0: no virtual offsets, as flagstat alone needs it).
+struct BaiIn {
+  const uint8_t* raw;
+  const int64_t* roff;
+  const uint8_t* keep;
+  int64_t n, header_end;
+  const int64_t *coff, *ustart;
+  int64_t nblocks;
+  int32_t nref;
+};
+struct BaiCols {  // per kept record, in order: entry j = the j-th kept record
+  uint32_t* rec;  // its index among all records
+  int32_t *tid, *beg, *bin, *w0, *w1, *status;
+  uint64_t *u, *v;  // the virtual offsets of its start and its end
+};
+struct BaiAcc {  // zeroed by the caller, first_bad set to ~0
+  uint64_t* first_bad;   // min over the refused records of rec << 2 | status
+  uint64_t* counters;    // the 32 of flagstat
+  uint64_t *mapped, *unmapped, *n_intv;  // per reference
+  uint64_t* n_no_coor;
+};
+namespace bai {
+struct Run;  // bam_index.h: one run of kept records in one bin (reference, bin, start, end)
+}  // namespace bai
+// scratch: 4 arrays of n + 1 int64 (kept flag and size, their scans); nk[0] = kept records.  Fills the columns (status:
+// the record's own) and the accumulators.
+hipError_t launch_bai_keys(const BaiIn& I, int64_t* scratch, int64_t* nk, const BaiCols& o, const BaiAcc& A,
+                           hipStream_t st);
+// The order test against the kept record before (status, first_bad), the run heads and their scan (head, hx: n + 1
+// int64 each; nruns[0] = runs), and the runs in file order with their sort keys (tid << 16 | bin).
+hipError_t launch_bai_runs(const BaiCols& o, int64_t n, const int64_t* nk, int64_t* head, int64_t* hx, int64_t* nruns,
+                           uint64_t* first_bad, bai::Run* runs, uint64_t* key, hipStream_t st);
+// sorted[s] = runs[idx[s]]
+hipError_t launch_bai_gather(const bai::Run* runs, const uint32_t* idx, int64_t nruns, bai::Run* sorted, hipStream_t st);
+// win[base[tid] + w] = the smallest u of a record over window w (win starts as all-ones, nwin entries), then every
+// untouched window takes the next touched one's value, reference by reference
+hipError_t launch_bai_linear(const BaiCols& o, int64_t n, const int64_t* nk, const int64_t* base, const uint64_t* n_intv,
+                             int32_t nref, uint64_t* win, int64_t nwin, hipStream_t st);
+
 }  // namespace uc

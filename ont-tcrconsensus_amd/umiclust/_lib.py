@@ -152,7 +152,8 @@ EXPORTS = [
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
     "umiclust_bgzf_inflate", "umiclust_bam_inflate_info", "umiclust_sam_open", "umiclust_sam_info",
     "umiclust_bam_region_split", "umiclust_bam_region_split_extract", "umiclust_bgzf_deflate",
-    "umiclust_bam_write_info",
+    "umiclust_bam_write_info", "umiclust_bam_write_index", "umiclust_bam_index_file", "umiclust_bam_flagstat",
+    "umiclust_bam_index_probe", "umiclust_bam_index_info",
 ]
 OVERLAP_MAX_REGIONS = 4096
 # umiclust_pass_qs / umiclust_pass_walk (include/umiclust.h) and the largest record k_pack writes, in words
@@ -340,6 +341,17 @@ def lib() -> C.CDLL:
     L.umiclust_sam_open.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.umiclust_sam_info.restype = C.c_int32
     L.umiclust_sam_info.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
+    L.umiclust_bam_write_index.restype = C.c_int64
+    L.umiclust_bam_write_index.argtypes = [C.c_void_p, P(C.c_uint8), C.c_char_p, C.c_char_p]
+    L.umiclust_bam_index_file.restype = C.c_int64
+    L.umiclust_bam_index_file.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    L.umiclust_bam_flagstat.restype = C.c_int32
+    L.umiclust_bam_flagstat.argtypes = [C.c_void_p, P(C.c_uint8), P(C.c_int64), C.c_void_p, C.c_int64]
+    L.umiclust_bam_index_probe.restype = C.c_int32
+    L.umiclust_bam_index_probe.argtypes = [C.c_void_p, P(C.c_uint8), P(C.c_int64), P(C.c_int64), C.c_int64] + \
+        [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+    L.umiclust_bam_index_info.restype = C.c_int32
+    L.umiclust_bam_index_info.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double)]
     # the path-based calls without their bam_file argument
     L.umiclust_bam_region_split.restype = C.c_int64
     L.umiclust_bam_region_split.argtypes = [a for k, a in enumerate(L.umiclust_region_split.argtypes) if k != 1]
@@ -771,6 +783,22 @@ class Context:
         self._check(lib().umiclust_sam_open(self._h, os.fspath(sam_file).encode(), hash_bits), "sam_open")
         return BamSession(self)
 
+    def bam_index_file(self, bam_file, bai=None) -> int:
+        """umiclust_bam_index_file: `samtools index bam_file` on the device, the index at `bai` (None:
+        bam_file + ".bai").  Returns the number of records; an open session stays as it is."""
+        return int(self._check(lib().umiclust_bam_index_file(
+            self._h, os.fspath(bam_file).encode(), os.fspath(bai).encode() if bai is not None else None),
+            "bam_index_file"))
+
+    def bam_index_info(self) -> dict:
+        """umiclust_bam_index_info: the counts and seconds of this context's last index, probe or flagstat call"""
+        out, t = np.zeros(4, np.int64), np.zeros(4, np.float64)
+        self._check(lib().umiclust_bam_index_info(self._h, _i64(out), t.ctypes.data_as(C.POINTER(C.c_double))),
+                    "bam_index_info")
+        d = dict(zip(("kept", "runs", "chunks", "windows"), (int(x) for x in out)))
+        d.update(zip(("upload_s", "kernel_s", "copy_back_s", "finish_s"), (float(x) for x in t)))
+        return d
+
     def bgzf_inflate(self, data, want_status: bool = False):
         """umiclust_bgzf_inflate: the BGZF byte string `data` inflated on the device, as a uint8 array.
         want_status: returns (bytes, status, error) instead -- one int32 per block (0 = ok, else the decoder's error
@@ -1085,12 +1113,72 @@ class BamSession:
     def cs_strings(self, idx) -> list:
         return self._strings(1, idx)
 
-    def write(self, keep, path) -> int:
+    def _keep(self, keep):
+        """(the array that owns the bytes, the pointer the ABI takes): None passes as NULL"""
+        if keep is None:
+            return None, None
         keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
         if len(keep) != self.n:
             raise ValueError("keep needs one entry per record")
-        return int(self._ctx._check(lib().umiclust_bam_write(
-            self._ctx._h, keep.ctypes.data_as(C.POINTER(C.c_uint8)), os.fspath(path).encode()), "bam_write"))
+        return keep, keep.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def write(self, keep, path, index=None) -> int:
+        """umiclust_bam_write; with index=True (path + ".bai") or index=<a path>, umiclust_bam_write_index: the file
+        and its .bai"""
+        if keep is None:
+            raise ValueError("keep needs one entry per record")  # (a write names what it keeps)
+        keep, kp = self._keep(keep)
+        if index is None or index is False:
+            return int(self._ctx._check(lib().umiclust_bam_write(self._ctx._h, kp, os.fspath(path).encode()),
+                                        "bam_write"))
+        bai = None if index is True else os.fspath(index).encode()
+        return int(self._ctx._check(lib().umiclust_bam_write_index(self._ctx._h, kp, os.fspath(path).encode(), bai),
+                                    "bam_write_index"))
+
+    FLAGSTAT_ROWS = ("total", "primary", "secondary", "supplementary", "duplicates", "primary_duplicates", "mapped",
+                     "primary_mapped", "paired", "read1", "read2", "properly_paired", "both_mapped", "singletons",
+                     "mate_other_chr", "mate_other_chr_mapq5")
+
+    def flagstat(self, keep=None) -> tuple[dict, str]:
+        """umiclust_bam_flagstat (policy O11): ({row: (QC-passed, QC-failed)}, the text `samtools
+        flagstat` prints) over the records with keep[r] != 0 (None: all)"""
+        keep, kp = self._keep(keep)
+        L, h = lib(), self._ctx._h
+        out = np.zeros(32, np.int64)
+        need = self._ctx._check(L.umiclust_bam_flagstat(h, kp, _i64(out), None, 0), "bam_flagstat")
+        buf = C.create_string_buffer(need)
+        self._ctx._check(L.umiclust_bam_flagstat(h, kp, _i64(out), buf, need), "bam_flagstat")
+        return ({k: (int(out[2 * x]), int(out[2 * x + 1])) for x, k in enumerate(self.FLAGSTAT_ROWS)},
+                buf.value.decode("ascii"))
+
+    def index_probe(self, keep, coff, ustart) -> dict:
+        """umiclust_bam_index_probe: the index kernels on the kept records (None: all) under the block table (coff,
+        ustart), with every array they leave.  A refused record is reported in first_bad / first_status."""
+        keep, kp = self._keep(keep)
+        coff, ustart = np.ascontiguousarray(coff, np.int64), np.ascontiguousarray(ustart, np.int64)
+        if len(coff) != len(ustart):
+            raise ValueError("coff and ustart need one entry per block")
+        nk = self.n if keep is None else int(np.count_nonzero(keep))
+        # a reference's windows: at most 2^29 >> 14 each, and every window of a reference but its last few holds a record
+        wcap = 32768 * min(self.n_refs, nk) + 1
+        a = dict(bin=np.zeros(nk, np.int32), u=np.zeros(nk, np.uint64), v=np.zeros(nk, np.uint64),
+                 status=np.zeros(nk, np.int32), runs=np.zeros((nk, 4), np.int64), sorted_runs=np.zeros((nk, 4), np.int64),
+                 n_intv=np.zeros(self.n_refs, np.int64), linear=np.zeros(wcap, np.uint64),
+                 mapped=np.zeros(self.n_refs, np.int64), unmapped=np.zeros(self.n_refs, np.int64),
+                 counters=np.zeros(32, np.int64), info=np.zeros(6, np.int64))
+        p = {k: x.ctypes.data for k, x in a.items()}
+        self._ctx._check(lib().umiclust_bam_index_probe(
+            self._ctx._h, kp, _i64(coff), _i64(ustart), len(coff), p["bin"], p["u"], p["v"], p["status"], p["runs"],
+            p["sorted_runs"], nk, p["n_intv"], p["linear"], wcap, p["mapped"], p["unmapped"], p["counters"], p["info"]),
+            "bam_index_probe")
+        nkept, nruns, nwin, first_bad, first_status, n_no_coor = (int(x) for x in a.pop("info"))
+        a.update(runs=a["runs"][:nruns], sorted_runs=a["sorted_runs"][:nruns], linear=a["linear"][:nwin], n_kept=nkept,
+                 first_bad=first_bad, first_status=first_status, n_no_coor=n_no_coor)
+        return a
+
+    def index_info(self) -> dict:
+        """umiclust_bam_index_info: the counts and seconds of the context's last index, probe or flagstat call"""
+        return self._ctx.bam_index_info()
 
     def split(self, keep, names, lengths, buckets, bucket_paths, overlap: float, s5: int, s3: int):
         """umiclust_bam_split: the records (keep None: all, else those with keep[r] != 0) appended as FASTA to

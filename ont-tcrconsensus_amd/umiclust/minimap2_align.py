@@ -119,23 +119,49 @@ def write_cs_tag_report(fh, bam_file_or_session, keep=None, top: int = 40, sub: 
     fh.write(cs_tag_report(bam_file_or_session, keep=keep, top=top, sub=sub))
 
 
-def samtools_sort(sam_file: Union[str, os.PathLike[str]], bam_file: Union[str, os.PathLike[str]]) -> int:
+def _write(src, keep, path, index: bool) -> int:
+    """src.write, asking for the .bai only where it is wanted: a source without one keeps working"""
+    return src.write(keep, path, index=True) if index else src.write(keep, path)
+
+
+def samtools_sort(sam_file: Union[str, os.PathLike[str]], bam_file: Union[str, os.PathLike[str]],
+                  index: bool = False) -> int:
     """`samtools sort -o bam_file sam_file` (:133-137) on the device (umiclust_sam_open): the text --
     a file, a FIFO or /dev/fd/N -- parsed, encoded and coordinate-sorted, every record written.  Returns their number.
-    No index is written: `samtools index` runs on the file as before."""
+    index=True also writes bam_file + ".bai" from the same session (`samtools index`, :138)."""
     with _v.context().sam_open(os.fspath(sam_file)) as src:
-        return src.write(np.ones(src.n, np.uint8), bam_file)
+        return _write(src, np.ones(src.n, np.uint8), bam_file, index)
+
+
+def samtools_index(bam_file: Union[str, os.PathLike[str]]) -> int:
+    """`samtools index bam_file` (:138, :247) on the device (umiclust_bam_index_file): bam_file +
+    ".bai".  Returns the number of records."""
+    return _v.context().bam_index_file(os.fspath(bam_file))
+
+
+def samtools_flagstat(bam_file_or_session, out_path: Union[str, os.PathLike[str]]) -> dict:
+    """`samtools flagstat bam_file > out_path` (:152-153) on the device (umiclust_bam_flagstat), from a
+    file or from an open session.  Returns the counters, {row: (QC-passed, QC-failed)}."""
+    with _Opened(bam_file_or_session) as src:
+        counters, text = src.flagstat()
+    with open(out_path, "w") as fh:
+        fh.write(text)
+    return counters
 
 
 def minimap2_ont_align_session(fastx: Union[str, os.PathLike[str]], reference: Union[str, os.PathLike[str]],
                                logs_dir: Union[str, os.PathLike[str]], minimap2_threads: int,
-                               minimap2_params: str = None, bam_file: Union[str, os.PathLike[str]] = None):
+                               minimap2_params: str = None, bam_file: Union[str, os.PathLike[str]] = None,
+                               index: bool = False, flagstat: bool = False):
     """minimap2_ont_align (:76-155) without the BAM in the middle: minimap2 runs with the reference's argv and its
     stderr in the same <fastx>_minimap2.err log; its SAM output is read from the pipe by umiclust_sam_open, which
     parses, encodes and coordinate-sorts it on the device; the three cs-tag blocks of :140-150 are appended to the log
     from that session; and the open session is returned, for region_split.filter_split_and_extract_umis_from and its
-    like.  The sorted BAM is written only when bam_file is given.  `samtools index` (:138) and `samtools flagstat`
-    (:152-153) are not replaced: a caller that wants them passes bam_file and runs them on it."""
+    like.  The sorted BAM is written only when bam_file is given; index=True (which needs bam_file) writes its .bai
+    with it (`samtools index`, :138).  flagstat=True writes <logs_dir>/<name>_flagstat.out (:152-153) from the session,
+    <name> being the BAM's as :86 forms it -- bam_file's, or the FASTX's where none is written.  DESIGN.md §9h."""
+    if index and bam_file is None:
+        raise ValueError("index=True needs bam_file: a .bai indexes a file")
     log_file = os.path.join(logs_dir, os.path.basename(fastx).split(".")[0] + "_minimap2")
     with open(log_file + ".err", "w") as ferr:
         minimap2_process = subprocess.Popen(
@@ -167,7 +193,10 @@ def minimap2_ont_align_session(fastx: Union[str, os.PathLike[str]], reference: U
         try:
             write_cs_tag_report(ferr, src)
             if bam_file is not None:
-                src.write(np.ones(src.n, np.uint8), bam_file)
+                _write(src, np.ones(src.n, np.uint8), bam_file, index)
+            if flagstat:
+                stem = os.path.basename(bam_file if bam_file is not None else fastx).split(".")[0]
+                samtools_flagstat(src, os.path.join(logs_dir, stem + "_flagstat.out"))
         except Exception:
             src.close()
             raise
@@ -205,17 +234,22 @@ def _write_lines(fh, lines) -> None:
 
 
 def filter_consensus_alignments_from(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                     minimal_region_overlap=0.9975, max_softclip_5_end=73, max_softclip_3_end=68):
+                                     minimal_region_overlap=0.9975, max_softclip_5_end=73, max_softclip_3_end=68,
+                                     index="samtools"):
     """filter_consensus_alignments (:158-359) over the columns of `src` (a _lib.BamSession, or any object with its
     attributes): the decisions, the seven CSVs, the log and -- through src.write -- the filtered BAM.  Values and
-    texts are pinned by tests/golden/bam_filter, which the reference's own function produced."""
+    texts are pinned by tests/golden/bam_filter, which the reference's own function produced.  index: "samtools" runs
+    `samtools index` on the filtered BAM as the reference does (:247); "device" has the session write the .bai with
+    the BAM instead, and no subprocess runs."""
     return _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)[0]
+                                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, index)[0]
 
 
 def _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                 minimal_region_overlap, max_softclip_5_end, max_softclip_3_end):
+                                 minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, index="samtools"):
     """filter_consensus_alignments_from, returning (filtered BAM path, keep): keep[r] != 0 for the records written"""
+    if index not in ("samtools", "device"):
+        raise ValueError("index is 'samtools' or 'device'")
     stem = os.path.basename(consensus_bam_file).split(".")[0]
     filtered = os.path.splitext(consensus_bam_file)[0] + "_filtered.bam"
     lengths = generate_region_length_dict_from_ref_fa(reference=reference)
@@ -257,13 +291,14 @@ def _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, b
         raised = e
     # the reference's output file is closed with what was written before the exception, and nothing else follows
     try:
-        src.write(keep, filtered)
+        _write(src, keep, filtered, index == "device" and raised is None)  # :247 on the device: the .bai with the BAM
     except Exception:
         if raised is None:
             raise
     if raised is not None:
         raise raised
-    subprocess.run(["samtools", "index", filtered])  # :247, kept as it is
+    if index == "samtools":
+        subprocess.run(["samtools", "index", filtered])  # :247, kept as it is
 
     # the seven CSVs (:253-279), as DataFrame.to_csv(index=False) writes them
     for suffix, columns, rows in (
@@ -319,11 +354,12 @@ def _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, b
 def filter_consensus_alignments(consensus_bam_file: Union[str, os.PathLike[str]],
                                 reference: Union[str, os.PathLike[str]], logs_dir: Union[str, os.PathLike[str]],
                                 blast_id_threshold: float, minimal_region_overlap: float = 0.9975,
-                                max_softclip_5_end: int = 73, max_softclip_3_end: int = 68):
-    """:158-359 -- same signature, defaults, files and return value."""
+                                max_softclip_5_end: int = 73, max_softclip_3_end: int = 68, index: str = "samtools"):
+    """:158-359 -- same signature, defaults, files and return value; index="device" writes the .bai of :247 from the
+    session instead of running samtools."""
     with _Opened(consensus_bam_file) as src:
         return filter_consensus_alignments_from(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                                minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+                                                minimal_region_overlap, max_softclip_5_end, max_softclip_3_end, index)
 
 
 def filter_consensus_alignments_and_split(consensus_bam_file: Union[str, os.PathLike[str]],
@@ -331,7 +367,7 @@ def filter_consensus_alignments_and_split(consensus_bam_file: Union[str, os.Path
                                           logs_dir: Union[str, os.PathLike[str]], blast_id_threshold: float,
                                           region_fasta_out_dir: Union[str, os.PathLike[str]],
                                           minimal_region_overlap: float = 0.9975, max_softclip_5_end: int = 73,
-                                          max_softclip_3_end: int = 68):
+                                          max_softclip_3_end: int = 68, index: str = "samtools"):
     """tcr_consensus.py's filter_consensus_alignments (:366-374) and filter_and_split_reads_by_region (:376-384) on one
     session: the filter runs as above (it still writes and indexes the filtered BAM), then the session's records are
     split under the filter's keep mask instead of the filtered BAM being read back.  The split takes the filter's
@@ -339,7 +375,8 @@ def filter_consensus_alignments_and_split(consensus_bam_file: Union[str, os.Path
     call does.  Returns (filtered BAM path, list of region_<name>.fasta paths)."""
     with _Opened(consensus_bam_file) as src:
         filtered, keep = _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end,
+                                                      index)
         fastas = filter_and_split_reads_by_region_from(src, keep, filtered, reference, logs_dir, region_fasta_out_dir,
                                                        minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
     return filtered, fastas
@@ -352,7 +389,8 @@ def filter_consensus_alignments_split_and_extract(consensus_bam_file: Union[str,
                                                   minimal_region_overlap: float = 0.9975, max_softclip_5_end: int = 73,
                                                   max_softclip_3_end: int = 68, adapter_length_5_end: int = None,
                                                   adapter_length_3_end: int = None, max_pattern_dist: int = 3,
-                                                  umi_fwd: str = UMI_FWD_DEFAULT, umi_rev: str = UMI_REV_DEFAULT):
+                                                  umi_fwd: str = UMI_FWD_DEFAULT, umi_rev: str = UMI_REV_DEFAULT,
+                                                  index: str = "samtools"):
     """filter_consensus_alignments_and_split with the UMI extraction of tcr_consensus.py:386-403 fused into the split
     (row f4+f1): the filter runs as above, then the session's records are split under its keep mask and
     searched for their UMIs in one pass, so that region_<name>_detected_umis.fasta is written and no region FASTA is.
@@ -360,7 +398,8 @@ def filter_consensus_alignments_split_and_extract(consensus_bam_file: Union[str,
     of the detected-UMI FASTA paths that hold a record)."""
     with _Opened(consensus_bam_file) as src:
         filtered, keep = _filter_consensus_alignments(src, consensus_bam_file, reference, logs_dir, blast_id_threshold,
-                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end)
+                                                      minimal_region_overlap, max_softclip_5_end, max_softclip_3_end,
+                                                      index)
         umi_fastas = filter_split_and_extract_umis_by_region_from(
             src, keep, filtered, reference, logs_dir, umi_fasta_out_dir, minimal_region_overlap, max_softclip_5_end,
             max_softclip_3_end, adapter_length_5_end, adapter_length_3_end, max_pattern_dist, umi_fwd, umi_rev)
