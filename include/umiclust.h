@@ -739,12 +739,43 @@ int32_t umiclust_overlap_probe(umiclust_ctx *ctx, const char *seqs, const int64_
  *   peer_id[qs * 128 ...] (seqno - w0), peer_count[qs * 128 ...], npeer[qs]   the in-window peers (255 = overflow)
  * and info[0..4]: (query-strand, part) units the lean kernel handed to the full kernel, centroid tiles the pass
  * read, counter segments, 1 if the one-wave layout of k_pf_count was launched, both.  Any output may be NULL.
- * Not covered (each keeps its end-to-end tests): split passes, packs, policy O4 rounds, more than one counter
- * segment.  nq > 8192, centroids in the window, a block spanning more than 32 lengths, policy_threads or several
+ * More than 458,752 centroids (one counter segment) take the pipeline's multi-segment branch, up to its limit of 16
+ * segments: the lean kernel does not run there -- k_pf_full counts every (query-strand, part) unit segment by segment
+ * and merges a running top-41 -- so info[0] = 0 (nothing was handed over) and info[3] = 0, and info[2] > 1 tells.
+ * Not covered (each keeps its end-to-end tests): policy O4 rounds; split passes and packs are the two siblings'
+ * below.  nq > 8192, centroids in the window, a block spanning more than 32 lengths, policy_threads or several
  * bins: UMICLUST_EINVAL; no load: UMICLUST_ESTATE.  Leaves the context loaded and not clustered. */
 int32_t umiclust_prefilter(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int32_t q0, int32_t nq,
                            int32_t nprev, int32_t append_step, uint32_t *top_seqno, uint8_t *top_count,
                            uint8_t *ntop, uint16_t *peer_id, uint8_t *peer_count, uint8_t *npeer, int64_t *info);
+/* umiclust_prefilter on a pack of a umiclust_load_bins load (an added function, ABI version unchanged): the bins
+ * [first_bin, first_bin + nbins) in one greedy order, as umiclust_cluster_pack clusters them -- per-bin scrambled
+ * k-mers, the earlier bins' centroids and peers cut out of the counter sweeps, the full kernel keyed by the centroid
+ * length table.  cent, the window and the block lie in the pack's sorted seqno range, a block may cross a bin
+ * boundary; the pass is a whole pass.  Outputs and info[0..4] as umiclust_prefilter's (seqnos absolute in the load).
+ * UMICLUST_EINVAL besides umiclust_prefilter's: a pack outside the load, seqnos outside the pack, more than one
+ * counter segment, and a cent that holds a seqno of some bin without that bin's first sequence (a bin's first
+ * sequence is always its first centroid; the bin's ordinal range opens with it). */
+int32_t umiclust_prefilter_pack(umiclust_ctx *ctx, int32_t first_bin, int32_t nbins, const int32_t *cent,
+                                int32_t ncent, int32_t q0, int32_t nq, int32_t nprev, int32_t append_step,
+                                uint32_t *top_seqno, uint8_t *top_count, uint8_t *ntop, uint16_t *peer_id,
+                                uint8_t *peer_count, uint8_t *npeer, int64_t *info);
+/* One split pass in the steady state of the single-bin pipeline (an added function, ABI version unchanged).  The
+ * blocks are j-2 = [w0, w0 + nq), j-1 and j = [w0 + 2 nq, w0 + 3 nq); cent (all before w0) is appended append_step at
+ * a time on the side stream; then, with no host synchronisation in between: the three peer tiles, the counting half
+ * of block j (k_pf_count over the index and the three-block window, block j-2 flagged), the append of newcent[nnew]
+ * (increasing seqnos inside block j-2: the centroids its resolution found), and the second half of block j (k_pf_full
+ * over the overflowed units, k_pf_merge keeping the flagged hits that became centroids) with the window j-1 .. j.
+ * The lists are those of block j against cent and newcent together with the window [w0 + nq, w0 + 3 nq): peer ids
+ * are relative to w0 + nq.  info[0..4] as umiclust_prefilter's, info[0] counting the counting half's units (flagged
+ * hits included) and info[1] the tiles the second half read; info[5] the tiles the counting half read; info[6] the
+ * centroids in the sealed and base tiles after the append (ncent + nnew exactly when that append folded the delta).
+ * UMICLUST_EINVAL besides umiclust_prefilter's: newcent outside block j-2 or not increasing, ncent + nnew past one
+ * counter segment (the pipeline does not split there). */
+int32_t umiclust_prefilter_split(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, const int32_t *newcent,
+                                 int32_t nnew, int32_t w0, int32_t nq, int32_t append_step, uint32_t *top_seqno,
+                                 uint8_t *top_count, uint8_t *ntop, uint16_t *peer_id, uint8_t *peer_count,
+                                 uint8_t *npeer, int64_t *info);
 
 /* One whole device pass (the prefilter, then k_walk, the per-length alignment rounds, k_peer_rel / k_peer_pairs and
  * k_pack), launched as the pipeline launches it, with everything the host's resolve step reads of it.  cent, ncent,

@@ -114,10 +114,11 @@ struct Pass {
   int32_t a_q0 = -1, a_base = 0, a_slot = 0, t_slot = 0;
 };
 
-// What a whole pass's prefilter ran, for umiclust_prefilter (the kernel-level parity entry)
+// What a pass's prefilter ran, for umiclust_prefilter and its siblings (the kernel-level parity entries)
 struct PfCapture {
   uint32_t* h_nunits = nullptr;  // pinned: *nunits between the lean kernel and the full kernel over its units
   int32_t ntiles = 0, nseg = 0, one_wave = 0;  // centroid tiles read, counter segments, k_pf_count<0, 1> launched
+  int32_t ntiles_count = 0;      // split passes: centroid tiles the counting half read (ntiles: the second half)
 };
 
 // The centroid index of the bin being clustered (index.cpp): sealed tiles (kTile centroids each, built once) + an
@@ -384,7 +385,7 @@ struct ClusterRun {
   Tile& stile(int32_t j) { return c->blk_tile[j % (kPeerTiles + 1)]; }
   void build_peer(int32_t j, bool side);
   void second_half(int32_t j, int32_t first, bool after_count, PfCapture* cap = nullptr);
-  void count_half(int32_t j, int32_t first, int flag);
+  void count_half(int32_t j, int32_t first, int flag, PfCapture* cap = nullptr);
   void prime(int32_t r);
   void run_split();
   void run_pipeline();
@@ -450,7 +451,7 @@ void ensure_pass_buffers(umiclust_ctx* c, Pass& P, int32_t B);
 void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* const* prevs, int nprev, Tile& own,
                   int32_t region, bool lazy_peers = false, bool after_count = false, PfCapture* cap = nullptr);
 void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* const* wins, int nwin, int flag,
-                   int32_t slot);
+                   int32_t slot, PfCapture* cap = nullptr);
 bool resolve_pass(umiclust_ctx* c, Pass& P, const StateView& state, std::vector<int32_t>& new_cents, double& t_pf,
                   double& t_al, double& t_host, int32_t* resolved);
 

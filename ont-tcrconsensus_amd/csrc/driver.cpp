@@ -423,11 +423,11 @@ void ClusterRun::second_half(int32_t j, int32_t first, bool after_count, PfCaptu
   enqueue_pass(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, prevs, np, stile(j), j % kPeerTiles, lazy,
                after_count, cap);
 }
-void ClusterRun::count_half(int32_t j, int32_t first, int flag) {
+void ClusterRun::count_half(int32_t j, int32_t first, int flag, PfCapture* cap) {
   const Tile* wins[kPeerTiles];
   int nw = 0;
   for (int32_t i = first; i <= j; i++) wins[nw++] = &stile(i);
-  enqueue_count(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, wins, nw, flag, j % 4);
+  enqueue_count(c, c->pass[j % 2], plan.blocks[j].first, plan.blocks[j].second, wins, nw, flag, j % 4, cap);
 }
 // the index holds the blocks before r and nothing is queued: classic passes r (window r) and r+1 (window
 // r, r+1), then A(r+2) with block r flagged

@@ -643,7 +643,9 @@ __device__ __forceinline__ TileView cent_view(const PrefilterArgs& a, int i) {
   return a.ntiles <= kArgTiles ? a.tv[i] : load_view(a.tiles + i);
 }
 
-// packs: the bytes of a counter word from byte nb on (nb <= 0: all four, nb >= 4: none)
+// packs: the bytes of a counter word from byte nb on (nb <= 0: all four, nb >= 4: none).  The peer sweeps apply it
+// to the hit mask, not to the counts: with thr = 0 a count cut to zero is still a hit, and a query without unmasked
+// 8-mers listed up to three entries of the earlier bin per part as peers (tests/test_gpu_prefilter.py pack_win*).
 __device__ __forceinline__ uint32_t keep_from(int nb) {
   return nb <= 0 ? 0xffffffffu : nb >= 4 ? 0u : ~((1u << (8 * nb)) - 1u);
 }
@@ -1050,9 +1052,10 @@ __device__ __forceinline__ void pf_full_unit(const PrefilterArgs& a, uint32_t un
         const int32_t pmin = pack_pmin(seq0, pv.base, part);  // packs: earlier bins' queries are never peers
         for (int x0 = (pmin >> 2) + wv * 64; x0 < nwords; x0 += kPfThreads) {
           const int x = x0 + lane;
-          const uint32_t w = x < nwords ? pw[x] & keep_from(pmin - 4 * x) : 0u;
+          const uint32_t w = x < nwords ? pw[x] : 0u;
           const int valid = x < nwords ? min(4, nsubP - 4 * x) : 0;  // bytes of peers before q
-          uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u);
+          uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u) &
+                      keep_from(pmin - 4 * x);
           if (__ballot(mk != 0u) == 0ull) continue;
           uint32_t slot = wave_alloc((uint32_t)__builtin_popcount(mk), &S.npc);
           while (mk) {
@@ -1340,9 +1343,10 @@ __global__ __launch_bounds__(64 * W, 8) void k_pf_count(PrefilterArgs a, uint32_
     const int32_t pmin = pack_pmin(seq0, pv.base, part);  // packs: earlier bins' queries are never peers
     for (int x0 = (pmin >> 2) + wv * 64; x0 < nwords; x0 += kThr) {
       const int x = x0 + lane;
-      const uint32_t w = x < nwords ? pw[x] & keep_from(pmin - 4 * x) : 0u;
+      const uint32_t w = x < nwords ? pw[x] : 0u;
       const int valid = x < nwords ? min(4, nsubP - 4 * x) : 0;  // bytes of peers before q
-      uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u);
+      uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u) &
+                      keep_from(pmin - 4 * x);
       if (__ballot(mk != 0u) == 0ull) continue;
       uint32_t slot = wave_alloc((uint32_t)__builtin_popcount(mk), &H.npc);
       while (mk) {
@@ -1366,9 +1370,10 @@ __global__ __launch_bounds__(64 * W, 8) void k_pf_count(PrefilterArgs a, uint32_
     const int32_t pmin = pack_pmin(seq0, pv.base, part);
     for (int x0 = (pmin >> 2) + wv * 64; x0 < nwords; x0 += kThr) {
       const int x = x0 + lane;
-      const uint32_t w = x < nwords ? pw[x] & keep_from(pmin - 4 * x) : 0u;
+      const uint32_t w = x < nwords ? pw[x] : 0u;
       const int valid = x < nwords ? min(4, nsubP - 4 * x) : 0;
-      uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u);
+      uint32_t mk = (w + add) & 0x80808080u & (valid >= 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u) &
+                      keep_from(pmin - 4 * x);
       if (__ballot(mk != 0u) == 0ull) continue;
       uint32_t slot = wave_alloc((uint32_t)__builtin_popcount(mk), &H.ncand);
       while (mk) {
@@ -1400,6 +1405,26 @@ __global__ __launch_bounds__(64 * W, 8) void k_pf_count(PrefilterArgs a, uint32_
     atomicAdd(&a.prof[19], __builtin_amdgcn_s_memrealtime() - rt0);
   }
 #undef PFC_MARK
+}
+
+// A split pass's second half, before the full kernel.  The counting half listed block j-2's hits as flagged candidates
+// by their window part ((seqno - block start) % kParts); the full kernel counts again against the index as it stands
+// now, where those that became centroids sit in the part of their ordinal.  A query-strand with some parts overflowed
+// and others not would mix the two partitions: a new centroid whose window part stayed lean and whose ordinal part
+// was recounted appeared twice in the merge, one whose window part was recounted and whose ordinal part stayed lean
+// not at all (tests/test_gpu_prefilter.py split_cap65).  So the other parts of such a query-strand become units too,
+// and all its lists are the recount's.  One thread per query-strand; the units array holds nqs * kParts entries.
+__global__ __launch_bounds__(256) void k_pf_expand_units(PrefilterArgs a, int32_t nqs) {
+  const int32_t qs = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+  if (qs >= nqs) return;
+  const int64_t p0 = (int64_t)qs * kParts;
+  int over = 0;
+#pragma unroll
+  for (int p = 0; p < kParts; p++) over += a.pncand[p0 + p] == 255;  // the lean kernel's overflow mark
+  if (over == 0 || over == kParts) return;
+#pragma unroll
+  for (int p = 0; p < kParts; p++)
+    if (a.pncand[p0 + p] != 255) a.units[atomicAdd(a.nunits, 1u)] = (uint32_t)(p0 + p);
 }
 
 // One wave per query-strand.  Candidates: the parts' lists (distinct ordinals) get their u64 keys
@@ -1609,7 +1634,8 @@ hipError_t launch_prefilter(const PrefilterArgs& a, hipStream_t st, int mode) {
       hipLaunchKernelGGL((k_pf_count<0, kPfWaves>), dim3(nqs * kParts), dim3(kPfThreads), lds, st, a, tab_off);
     if (mode == 1 || mode == 3) return hipGetLastError();
   }
-  if (mode == 2 || a.nseg <= 1) {
+  if (mode == 4) hipLaunchKernelGGL(k_pf_expand_units, dim3((nqs + 255) / 256), dim3(256), 0, st, a, nqs);
+  if (mode == 2 || mode == 4 || a.nseg <= 1) {
     // the full kernel over the units the lean kernel could not finish (exits at once when there are none); its
     // workgroups loop over the units (256: one per CU; 1024 / 2048 measured within noise, round 4 full_wg/)
     hipLaunchKernelGGL(k_pf_full, dim3(256), dim3(kPfThreads), smem_full, st, a, 1);

@@ -215,8 +215,14 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
   if (second_half) c->hip(hipStreamWaitEvent(st, c->a_ev[P.a_slot][1], 0), "wait");
   c->hip(hipEventRecord(P.ev[0], st), "event");
   P.c_timed = false;
+  if (cap) {  // (one_wave: the lean kernel's layout, set where that kernel is launched)
+    cap->ntiles = nv;
+    cap->nseg = a.nseg;
+  }
   if (second_half) {
-    c->hip(launch_prefilter(a, st, 2), "prefilter");
+    // (the units are the counting half's: the merge resets their count)
+    if (cap) c->hip(hipMemcpyAsync(cap->h_nunits, P.d_anunits.p, 4, hipMemcpyDeviceToHost, st), "d2h units");
+    c->hip(launch_prefilter(a, st, 4), "prefilter");
   } else if (a.nseg <= 1) {
     // whole pass: the lean counting (timed alone), then the full kernel over its overflowed units + merge
     c->hip(hipEventRecord(P.ev_c[0].get(c), st), "event");
@@ -226,8 +232,6 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
     if (c->tun.pf_probe) launch_pf_probe(c, a, st);
     if (cap) {
       c->hip(hipMemcpyAsync(cap->h_nunits, P.d_anunits.p, 4, hipMemcpyDeviceToHost, st), "d2h units");
-      cap->ntiles = nv;
-      cap->nseg = a.nseg;
       cap->one_wave = prefilter_one_wave(a) ? 1 : 0;
     }
     c->hip(launch_prefilter(a, st, 2), "prefilter");
@@ -328,7 +332,7 @@ void enqueue_pass(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* 
 // enqueue_pass(..., after_count = true) once that block is resolved and appended.  Bins past one counter
 // segment are not split (a_live stays false and the second half runs the whole prefilter).
 void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile* const* wins, int nwin, int flag,
-                   int32_t slot) {
+                   int32_t slot, PfCapture* cap) {
   P.a_live = false;
   if (c->ix.nseg() > 1) return;
   // on its own stream, gated by the main stream's work so far (index append, peer tiles, this buffer set's
@@ -352,6 +356,10 @@ void enqueue_count(umiclust_ctx* c, Pass& P, int32_t q0, int32_t nq, const Tile*
   a.flag_tile = flag >= 0 ? (kPeerTiles - nwin) + flag : -1;
   a.peer_base = a.cand_base = wins[0]->base;
   a.nlist_cap = nlist_cap(c, q0, nq, nv);
+  if (cap) {
+    cap->ntiles_count = nv;
+    cap->one_wave = prefilter_one_wave(a) ? 1 : 0;
+  }
   c->hip(hipEventRecord(c->a_ev[slot][0].get(c), st), "event");
   c->hip(launch_prefilter(a, st, 1), "prefilter (count)");
   c->hip(hipEventRecord(c->a_ev[slot][1].get(c), st), "event");

@@ -1,5 +1,6 @@
 // probes.cpp -- the kernel-level entry points of the C ABI, for the test suite: one prefilter or one whole pass
-// through the pipeline's own steps (umiclust_prefilter, umiclust_pass), and the alignment, consensus and preparation
+// through the pipeline's own steps (umiclust_prefilter, umiclust_prefilter_pack, umiclust_prefilter_split,
+// umiclust_pass), and the alignment, consensus and preparation
 // kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep, umiclust_prep_outputs), and
 // the region overlap join's intermediate arrays (umiclust_overlap_probe).
 #include <algorithm>
@@ -9,28 +10,42 @@
 
 using namespace uc;
 
-// What umiclust_prefilter and umiclust_pass share.  check_block_args: the refusals (`who` names the entry point).
-// stage_block: the pipeline's own steps up to the pass -- the bin's clean slate, arena and pass buffers (ClusterRun),
-// Index::append in steps of append_step, and the window's peer tiles (ClusterRun::build_peer) with the window's
-// blocks as the plan, oldest first, the block under test last (index nprev), as ClusterRun::prime enqueues a first pass.
+// What umiclust_prefilter, its siblings and umiclust_pass share.  check_block_args: the refusals (`who` names the entry
+// point); npk = 0 asks for a single-bin load, npk >= 1 names the pack [bin, bin + npk) of a umiclust_load_bins load,
+// whose sorted seqno range then bounds the centroids and the window; max_cent is the largest index covered.
+// stage_block: the pipeline's own steps up to the pass -- the bin's (or pack's) clean slate, arena and pass buffers
+// (ClusterRun), Index::append in steps of append_step, and the window's peer tiles (ClusterRun::build_peer) with the
+// window's blocks as the plan, oldest first, the block under test last (index nprev), as ClusterRun::prime enqueues a
+// first pass.  With `split` the appends and the tile builds go to the side stream behind ix_done, as
+// ClusterRun::run_split queues them in its steady state.
 static void check_block_args(umiclust_ctx* c, const char* who, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq,
-                      int32_t nprev, int32_t append_step) {
+                      int32_t nprev, int32_t append_step, int32_t max_cent, int32_t bin = 0, int32_t npk = 0) {
   if (!c->loaded) c->fail(UMICLUST_ESTATE, "%s before umiclust_load", who);
-  if (c->bin_s.size() != 2) c->fail(UMICLUST_EINVAL, "%s: the load holds several bins", who);
+  if (npk == 0 && c->bin_s.size() != 2) c->fail(UMICLUST_EINVAL, "%s: the load holds several bins", who);
+  if (npk != 0 && (bin < 0 || npk < 1 || (int64_t)bin + npk >= (int64_t)c->bin_s.size()))
+    c->fail(UMICLUST_EINVAL, "%s: bins [%d, %d) out of range", who, bin, bin + npk);
   if (c->o4_T) c->fail(UMICLUST_EINVAL, "%s: batched rounds (policy O4) are not covered", who);
+  const int32_t s0 = npk ? c->bin_s[bin] : 0, s1 = npk ? c->bin_s[bin + npk] : c->n;
   if ((!cent && ncent > 0) || ncent < 0 || nq < 1 || nq > kMaxBlock || nprev < 0 || nprev > kPeerTiles - 1 ||
-      append_step < 1 || q0 < 0 || (int64_t)q0 + nq > c->n || (int64_t)q0 - (int64_t)nprev * nq < 0)
+      append_step < 1 || q0 < s0 || (int64_t)q0 + nq > s1 || (int64_t)q0 - (int64_t)nprev * nq < s0)
     c->fail(UMICLUST_EINVAL, "%s: block, window or append step out of range", who);
-  if (ncent > kSegCentroids) c->fail(UMICLUST_EINVAL, "%s: more than one counter segment", who);
+  if (ncent > max_cent)
+    c->fail(UMICLUST_EINVAL, "%s: more than %d counter segment(s)", who, (max_cent + kSegCentroids - 1) / kSegCentroids);
   const int32_t w0 = q0 - nprev * nq;
   for (int32_t i = 0; i < ncent; i++)
-    if (cent[i] < (i ? cent[i - 1] + 1 : 0) || cent[i] >= w0)
+    if (cent[i] < (i ? cent[i - 1] + 1 : s0) || cent[i] >= w0)
       c->fail(UMICLUST_EINVAL, "%s: centroid seqnos must increase and precede the window", who);
+  // packs: a bin's first sequence is its first centroid (Index::append opens the bin's ordinal range with it)
+  for (int32_t i = 0; npk > 1 && i < ncent; i++) {
+    const int32_t b = c->hqbin[cent[i]];
+    if ((i == 0 || c->hqbin[cent[i - 1]] != b) && cent[i] != c->bin_s[b])
+      c->fail(UMICLUST_EINVAL, "%s: centroids of bin %d without the bin's first sequence", who, b);
+  }
   if (block_maxlen(c, q0, nq) - block_minlen(c, q0, nq) + 1 > kSegLens)
     c->fail(UMICLUST_EINVAL, "%s: block spans more than %d query lengths", who, kSegLens);
 }
 static void stage_block(umiclust_ctx* c, ClusterRun& r, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq,
-                 int32_t nprev, int32_t append_step) {
+                 int32_t nprev, int32_t append_step, bool split = false) {
   const int32_t w0 = q0 - nprev * nq;
   c->rec_direct = g_live_ctx.load() > 1;
   c->clustered = false;
@@ -40,7 +55,7 @@ static void stage_block(umiclust_ctx* c, ClusterRun& r, const int32_t* cent, int
   c->ix.layout(r.n, r.T4);
   if (nq > c->pass_B)
     for (Pass& P : c->pass) ensure_pass_buffers(c, P, nq);
-  c->ix_st = nullptr;
+  c->ix_st = split ? (hipStream_t)c->st_b : nullptr;
   c->last_r_ev = nullptr;
   for (Pass& P : c->pass) P.live = P.a_live = false;
   std::vector<int32_t> step;
@@ -50,7 +65,7 @@ static void stage_block(umiclust_ctx* c, ClusterRun& r, const int32_t* cent, int
   }
   r.plan.blocks.clear();
   for (int32_t j = 0; j <= nprev; j++) r.plan.blocks.push_back({w0 + j * nq, nq});
-  for (int32_t j = 0; j <= nprev; j++) r.build_peer(j, false);
+  for (int32_t j = 0; j <= nprev; j++) r.build_peer(j, split);
   c->hip(c->h_pf_nunits.ensure(1), "pin");
   c->h_pf_nunits.p[0] = 0;
 }
@@ -80,6 +95,11 @@ static void fetch_lists(umiclust_ctx* c, const Pass& P, const PfCapture& cap, si
     info[4] = c->both;
   }
 }
+// the appends and tile builds go back to the main stream, whatever ends a split probe
+struct SideStreamOff {
+  umiclust_ctx* c;
+  ~SideStreamOff() { c->ix_st = nullptr; }
+};
 
 // What umiclust_align_pairs, umiclust_consensus and umiclust_prep share: n records on the device, beside whatever load
 // the context holds, and k_prep over them.  The uploads have completed when probe_prep returns, the kernel is queued.
@@ -125,6 +145,21 @@ static void unpack_result(uint32_t r, int64_t k, int32_t* matches, int32_t* inte
   if (score) score[k] = (int32_t)(int16_t)(r >> 16);
 }
 
+// one whole pass (ClusterRun::second_half -> enqueue_pass) of the staged block and its lists: umiclust_prefilter and
+// umiclust_prefilter_pack
+static void whole_pass_lists(umiclust_ctx* c, ClusterRun& r, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq,
+                             int32_t nprev, int32_t append_step, uint32_t* top_seqno, uint8_t* top_count, uint8_t* ntop,
+                             uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer, int64_t* info) {
+  stage_block(c, r, cent, ncent, q0, nq, nprev, append_step);
+  PfCapture cap;
+  cap.h_nunits = c->h_pf_nunits.p;
+  r.second_half(nprev, 0, false, &cap);
+  Pass& P = c->pass[nprev % 2];
+  sync_streams(c);
+  P.live = false;
+  fetch_lists(c, P, cap, (size_t)nq * c->both, top_seqno, top_count, ntop, peer_id, peer_count, npeer, info);
+}
+
 static_assert(sizeof(umiclust_pass_qs) == sizeof(HostQs) && offsetof(umiclust_pass_qs, rel) == offsetof(HostQs, rel) &&
                   offsetof(umiclust_pass_qs, nrel) == offsetof(HostQs, nrel) &&
                   offsetof(umiclust_pass_qs, npeer) == offsetof(HostQs, npeer),
@@ -143,16 +178,69 @@ int32_t umiclust_prefilter(umiclust_ctx* c, const int32_t* cent, int32_t ncent, 
                            int32_t append_step, uint32_t* top_seqno, uint8_t* top_count, uint8_t* ntop,
                            uint16_t* peer_id, uint8_t* peer_count, uint8_t* npeer, int64_t* info) {
   UC_GUARD(c, {
-    check_block_args(c, "umiclust_prefilter", cent, ncent, q0, nq, nprev, append_step);
+    check_block_args(c, "umiclust_prefilter", cent, ncent, q0, nq, nprev, append_step, kMaxSegs * kSegCentroids);
     ClusterRun r(c, 0, 1, false);
-    stage_block(c, r, cent, ncent, q0, nq, nprev, append_step);
+    whole_pass_lists(c, r, cent, ncent, q0, nq, nprev, append_step, top_seqno, top_count, ntop, peer_id, peer_count,
+                     npeer, info);
+    return UMICLUST_OK;
+  });
+}
+
+// The same on a pack of a multi-bin load: ClusterRun over the bins [first_bin, first_bin + nbins), so the queries see
+// the scrambled k-mers, the per-bin cuts of the counter sweeps and the centroid length table as a clustering of the
+// pack does.
+int32_t umiclust_prefilter_pack(umiclust_ctx* c, int32_t first_bin, int32_t nbins, const int32_t* cent, int32_t ncent,
+                                int32_t q0, int32_t nq, int32_t nprev, int32_t append_step, uint32_t* top_seqno,
+                                uint8_t* top_count, uint8_t* ntop, uint16_t* peer_id, uint8_t* peer_count,
+                                uint8_t* npeer, int64_t* info) {
+  UC_GUARD(c, {
+    if (c->loaded && nbins < 1)
+      c->fail(UMICLUST_EINVAL, "umiclust_prefilter_pack: bins [%d, %d) out of range", first_bin, first_bin + nbins);
+    check_block_args(c, "umiclust_prefilter_pack", cent, ncent, q0, nq, nprev, append_step, kSegCentroids, first_bin,
+                     nbins);
+    ClusterRun r(c, first_bin, nbins, true);
+    whole_pass_lists(c, r, cent, ncent, q0, nq, nprev, append_step, top_seqno, top_count, ntop, peer_id, peer_count,
+                     npeer, info);
+    return UMICLUST_OK;
+  });
+}
+
+// A split pass in ClusterRun::run_split's steady state: the blocks j-2 = [w0, w0 + nq), j-1 and j = [w0 + 2 nq,
+// w0 + 3 nq); the counting half of block j with block j-2 flagged, the append of block j-2's new centroids, then
+// the second half of block j with the window j-1 .. j.  One synchronisation, at the end: the order of the halves,
+// the append and the fold it may bring rests on the events the pipeline itself records.
+int32_t umiclust_prefilter_split(umiclust_ctx* c, const int32_t* cent, int32_t ncent, const int32_t* newcent,
+                                 int32_t nnew, int32_t w0, int32_t nq, int32_t append_step, uint32_t* top_seqno,
+                                 uint8_t* top_count, uint8_t* ntop, uint16_t* peer_id, uint8_t* peer_count,
+                                 uint8_t* npeer, int64_t* info) {
+  UC_GUARD(c, {
+    const char* who = "umiclust_prefilter_split";
+    if (c->loaded && (w0 < 0 || w0 > c->n || nq < 1 || nq > kMaxBlock))
+      c->fail(UMICLUST_EINVAL, "%s: block, window or append step out of range", who);
+    const int32_t q0 = c->loaded ? w0 + 2 * nq : 0;
+    check_block_args(c, who, cent, ncent, q0, nq, 2, append_step, kSegCentroids);
+    if ((!newcent && nnew > 0) || nnew < 0) c->fail(UMICLUST_EINVAL, "%s: new centroids", who);
+    for (int32_t i = 0; i < nnew; i++)
+      if (newcent[i] < (i ? newcent[i - 1] + 1 : w0) || newcent[i] >= w0 + nq)
+        c->fail(UMICLUST_EINVAL, "%s: new centroid seqnos must increase inside the window's oldest block", who);
+    // (the counting half of an index past one counter segment is skipped: enqueue_count)
+    if ((int64_t)ncent + nnew > kSegCentroids) c->fail(UMICLUST_EINVAL, "%s: more than one counter segment", who);
+    ClusterRun r(c, 0, 1, false);
+    SideStreamOff off{c};
+    stage_block(c, r, cent, ncent, q0, nq, 2, append_step, true);
     PfCapture cap;
     cap.h_nunits = c->h_pf_nunits.p;
-    r.second_half(nprev, 0, false, &cap);
-    Pass& P = c->pass[nprev % 2];
+    r.count_half(2, 0, 0, &cap);
+    c->ix.append(std::vector<int32_t>(newcent, newcent + nnew));
+    r.second_half(2, 1, true, &cap);
+    Pass& P = c->pass[0];
     sync_streams(c);
     P.live = false;
     fetch_lists(c, P, cap, (size_t)nq * c->both, top_seqno, top_count, ntop, peer_id, peer_count, npeer, info);
+    if (info) {
+      info[5] = cap.ntiles_count;
+      info[6] = c->ix.base_end;
+    }
     return UMICLUST_OK;
   });
 }
@@ -168,7 +256,7 @@ int32_t umiclust_pass(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32
                       int64_t rec_cap, int64_t* rec_total, uint32_t* res, uint64_t* aligned, umiclust_pass_walk* walk,
                       uint32_t* counters, int64_t* info) {
   UC_GUARD(c, {
-    check_block_args(c, "umiclust_pass", cent, ncent, q0, nq, nprev, append_step);
+    check_block_args(c, "umiclust_pass", cent, ncent, q0, nq, nprev, append_step, kSegCentroids);
     if (flags & ~(UMICLUST_PASS_LAZY | UMICLUST_PASS_PREV)) c->fail(UMICLUST_EINVAL, "umiclust_pass: unknown flag");
     if ((flags & UMICLUST_PASS_PREV) && nprev < 1)
       c->fail(UMICLUST_EINVAL, "umiclust_pass: the previous block's pass needs nprev >= 1");

@@ -143,7 +143,9 @@ struct PrefilterArgs {
 // two kernels: the per-part counting/selection (grid nqs*kParts) and the per-query-strand merge
 // mode 0: the whole prefilter (lean counting + the full kernel over its overflowed units, or the full
 // kernel alone for multi-segment bins, then the merge); mode 1: only the lean counting (a split pass's
-// first half); mode 2: the full kernel over the units mode 1 left + the merge (its second half)
+// first half); mode 2: the full kernel over the units mode 1 left + the merge (a whole pass's second launch);
+// mode 4: the same as a split pass's second half, where a query-strand with only some parts overflowed hands the
+// full kernel its other parts too (k_pf_expand_units)
 hipError_t launch_prefilter(const PrefilterArgs& a, hipStream_t st, int mode = 0);
 // whether launch_prefilter's lean counting runs one-wave units (k_pf_count<0, 1>) for these arguments
 bool prefilter_one_wave(const PrefilterArgs& a);

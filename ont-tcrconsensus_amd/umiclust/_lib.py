@@ -147,6 +147,7 @@ EXPORTS = [
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_filter_stats", "umiclust_fastq_filter_stats_argv",
     "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
+    "umiclust_prefilter_pack", "umiclust_prefilter_split",
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
@@ -291,6 +292,11 @@ def lib() -> C.CDLL:
     L.umiclust_prefilter.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
                                      P(C.c_uint8), P(C.c_int64)]
+    lists = [P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8), P(C.c_uint8), P(C.c_int64)]
+    L.umiclust_prefilter_pack.restype = C.c_int32
+    L.umiclust_prefilter_pack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P(C.c_int32)] + [C.c_int32] * 5 + lists
+    L.umiclust_prefilter_split.restype = C.c_int32
+    L.umiclust_prefilter_split.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, P(C.c_int32)] + [C.c_int32] * 4 + lists
     L.umiclust_pass.restype = C.c_int32
     L.umiclust_pass.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_uint32, P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
@@ -917,10 +923,8 @@ class Context:
         return dict(consensus=[raw[coff[k]:coff[k + 1]].decode() for k in range(K)], ops=shaped(out_ops),
                     score=shaped(sc[:nm]), matches=shaped(mt[:nm]), internal_len=shaped(il[:nm]))
 
-    def prefilter(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30) -> dict:
-        """umiclust_prefilter on the current load: the top and peer lists of the block [q0, q0 + nq) against the
-        centroids `cent` (increasing sorted seqnos before the window), per query-strand (rows), and info[0..3]."""
-        ce = np.ascontiguousarray(cent, np.int32)
+    def _prefilter_lists(self, what: str, nq: int, ninfo: int, call) -> dict:
+        """the output buffers of the prefilter probes; call(*buffers) -> return code"""
         nqs = max(nq, 1) * 2
         top_seqno = np.zeros((nqs, 41), np.uint32)
         top_count = np.zeros((nqs, 41), np.uint8)
@@ -931,13 +935,34 @@ class Context:
         info = np.zeros(8, np.int64)
         P = C.POINTER
         u8 = lambda a: a.ctypes.data_as(P(C.c_uint8))  # noqa: E731
-        rc = lib().umiclust_prefilter(self._h, ce.ctypes.data_as(P(C.c_int32)), len(ce), q0, nq, nprev, append_step,
-                                      top_seqno.ctypes.data_as(P(C.c_uint32)), u8(top_count), u8(ntop),
-                                      peer_id.ctypes.data_as(P(C.c_uint16)), u8(peer_count), u8(npeer), _i64(info))
-        self._check(rc, "prefilter")
+        self._check(call(top_seqno.ctypes.data_as(P(C.c_uint32)), u8(top_count), u8(ntop),
+                         peer_id.ctypes.data_as(P(C.c_uint16)), u8(peer_count), u8(npeer), _i64(info)), what)
         n = nq * int(info[4])
         return dict(top_seqno=top_seqno[:n], top_count=top_count[:n], ntop=ntop[:n], peer_id=peer_id[:n],
-                    peer_count=peer_count[:n], npeer=npeer[:n], info=info[:4], both=int(info[4]))
+                    peer_count=peer_count[:n], npeer=npeer[:n], info=info[:ninfo], both=int(info[4]))
+
+    def prefilter(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30) -> dict:
+        """umiclust_prefilter on the current load: the top and peer lists of the block [q0, q0 + nq) against the
+        centroids `cent` (increasing sorted seqnos before the window), per query-strand (rows), and info[0..3]."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        return self._prefilter_lists("prefilter", nq, 4, lambda *out: lib().umiclust_prefilter(
+            self._h, ce.ctypes.data_as(C.POINTER(C.c_int32)), len(ce), q0, nq, nprev, append_step, *out))
+
+    def prefilter_pack(self, first: int, nbins: int, cent, q0: int, nq: int, nprev: int = 0,
+                       append_step: int = 1 << 30) -> dict:
+        """umiclust_prefilter_pack: prefilter() on the pack [first, first + nbins) of a load_bins load."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        return self._prefilter_lists("prefilter_pack", nq, 4, lambda *out: lib().umiclust_prefilter_pack(
+            self._h, first, nbins, ce.ctypes.data_as(C.POINTER(C.c_int32)), len(ce), q0, nq, nprev, append_step, *out))
+
+    def prefilter_split(self, cent, newcent, w0: int, nq: int, append_step: int = 1 << 30) -> dict:
+        """umiclust_prefilter_split: block [w0 + 2 nq, w0 + 3 nq) as a split pass -- the counting half with block
+        [w0, w0 + nq) flagged, the append of `newcent` (seqnos of that block), the second half; info[0..6]."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        nc = np.ascontiguousarray(newcent, np.int32)
+        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        return self._prefilter_lists("prefilter_split", nq, 7, lambda *out: lib().umiclust_prefilter_split(
+            self._h, p32(ce), len(ce), p32(nc), len(nc), w0, nq, append_step, *out))
 
     def run_pass(self, cent, q0: int, nq: int, nprev: int = 0, append_step: int = 1 << 30, lazy: bool = False,
                  prev: bool = False, rec_cap: int | None = None) -> dict:
