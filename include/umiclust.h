@@ -833,6 +833,29 @@ int32_t umiclust_pass(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int
                       int64_t rec_cap, int64_t *rec_total, uint32_t *res, uint64_t *aligned, umiclust_pass_walk *walk,
                       uint32_t *counters, int64_t *info);
 
+/* The same pass, queued and then resolved on the host by the pipeline's own resolve step, round B on the device
+ * included: which queries of the block become centroids and which centroid each member joins.  The block arguments,
+ * flags bits 0 and 1, the load it needs, what it refuses and its error codes are umiclust_pass's.
+ * win_state[q0 - w0]: the states of the window's queries before the block, 1 = centroid, 2 = member (anything else:
+ *   UMICLUST_EINVAL); cent and the window's centroids together are the centroids the block is clustered against.
+ * flags bit 2 (UMICLUST_RESOLVE_PARTIAL): when a peer list of the block overflowed, the queries before the first
+ *   overflowing one are resolved, as the pipeline does before it re-runs the rest; without it such a block resolves
+ *   nothing.
+ * Outputs, each optional (NULL):
+ *   state[nq], target[nq], strand[nq]   per query 0 = not resolved, 1 = centroid, 2 = member; the centroid seqno a
+ *                        member joins (-1 otherwise) and the strand of that hit
+ *   new_cents[nq]        the block's new centroids, increasing; info[2] of them
+ *   info[0..12]          queries resolved; 1 if that is the whole block; new centroids; the resolve step's alignments,
+ *                        cells, merged walks, deferred queries and round-B pairs; round B's trips to the device, its
+ *                        launches and its pairs as the device side counted them; strands per query; the trips that
+ *                        went through device buffers (more than 4096 pairs)
+ * Leaves the context loaded and not clustered.  (An added function: the struct layouts and the ABI version are
+ * unchanged.) */
+#define UMICLUST_RESOLVE_PARTIAL 4u
+int32_t umiclust_resolve(umiclust_ctx *ctx, const int32_t *cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
+                         int32_t append_step, uint32_t flags, const uint8_t *win_state, uint8_t *state,
+                         int32_t *target, uint8_t *strand, int32_t *new_cents, int64_t *info);
+
 /* The BGZF inflate kernel alone (an added function, ABI version unchanged).
  * file = a whole BGZF byte string in host memory.  cap == 0: returns the inflated size (sum of ISIZE) without a
  * launch.  Otherwise inflates on the device into out and returns the size.  block_status (may be NULL): one int32 per

@@ -43,8 +43,9 @@ struct DebugSums {
     double wait = 0, hq_copy = 0, rec_copy = 0, classify = 0, inorder = 0, enqueue = 0, total = 0, appends = 0,
            round_b = 0, resolve_block = 0;
   } t;
-  struct {  // round B: device time between its first and last launch's events (s), round trips, launches, pairs
-    double dev_s = 0, trips = 0, launches = 0, pairs = 0;
+  struct {  // round B: device time between its first and last launch's events (s), round trips, launches, pairs,
+            // trips of more than kRbDirect pairs
+    double dev_s = 0, trips = 0, launches = 0, pairs = 0, staged = 0;
   } rb;
   int64_t mispredicted = 0, saved = 0, blocked = 0;  // relevant peers predicted members that were not / were / undetermined
   // queries without records / records with only earlier-block relevant peers / with an in-block relevant peer / host ns

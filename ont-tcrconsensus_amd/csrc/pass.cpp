@@ -468,6 +468,7 @@ void round_b(umiclust_ctx* c, const std::vector<uint32_t>& bpq, const std::vecto
   c->dbg.rb.trips += 1;
   c->dbg.rb.launches += nl;
   c->dbg.rb.pairs += nb;
+  c->dbg.rb.staged += direct ? 0 : 1;
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // probes.cpp -- the kernel-level entry points of the C ABI, for the test suite: one prefilter or one whole pass
 // through the pipeline's own steps (umiclust_prefilter, umiclust_prefilter_pack, umiclust_prefilter_split,
-// umiclust_pass), and the alignment, consensus and preparation
+// umiclust_pass, umiclust_resolve), and the alignment, consensus and preparation
 // kernels on caller-given records (umiclust_align_pairs, umiclust_consensus, umiclust_prep, umiclust_prep_outputs), and
 // the region overlap join's intermediate arrays (umiclust_overlap_probe).
 #include <algorithm>
@@ -305,6 +305,78 @@ int32_t umiclust_pass(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32
     if (counters) memcpy(counters, P.h_counters.p, 16 * 4);
     if (rec && total > rec_cap) c->fail(UMICLUST_ERANGE, "umiclust_pass: %lld record words, room for %lld",
                                          (long long)total, (long long)rec_cap);
+    return UMICLUST_OK;
+  });
+}
+
+// The same pass, queued and then resolved by the pipeline's own resolve_pass (pass.cpp): resolve_block on the pass's
+// outcomes and records with the window's states as given, round B on the device, on the copy stream (the resolve step
+// against tests/resolve_ref.py).  The bin's states before the window are members (never read), the block's
+// undetermined; with UMICLUST_RESOLVE_PARTIAL resolve_pass may resolve the prefix before the first overflowing query,
+// as ClusterRun::run_whole asks it to.
+int32_t umiclust_resolve(umiclust_ctx* c, const int32_t* cent, int32_t ncent, int32_t q0, int32_t nq, int32_t nprev,
+                         int32_t append_step, uint32_t flags, const uint8_t* win_state, uint8_t* state,
+                         int32_t* target, uint8_t* strand, int32_t* new_cents, int64_t* info) {
+  UC_GUARD(c, {
+    check_block_args(c, "umiclust_resolve", cent, ncent, q0, nq, nprev, append_step, kSegCentroids);
+    if (flags & ~(UMICLUST_PASS_LAZY | UMICLUST_PASS_PREV | UMICLUST_RESOLVE_PARTIAL))
+      c->fail(UMICLUST_EINVAL, "umiclust_resolve: unknown flag");
+    if ((flags & UMICLUST_PASS_PREV) && nprev < 1)
+      c->fail(UMICLUST_EINVAL, "umiclust_resolve: the previous block's pass needs nprev >= 1");
+    const int32_t w0 = q0 - nprev * nq;
+    if (!win_state && q0 > w0) c->fail(UMICLUST_EINVAL, "umiclust_resolve: the window's states");
+    for (int32_t x = w0; x < q0; x++)
+      if (win_state[x - w0] != ST_CENT && win_state[x - w0] != ST_MEMBER)
+        c->fail(UMICLUST_EINVAL, "umiclust_resolve: window query %d is neither a centroid (1) nor a member (2)", x);
+    ClusterRun r(c, 0, 1, false);
+    const uint32_t* ctr_p[kPeerTiles];  // (as umiclust_pass: the buffer sets' zeroed counters stay known)
+    bool ctr_z[kPeerTiles];
+    for (int i = 0; i < kPeerTiles; i++) {
+      ctr_p[i] = c->pass[i].d_counters.p;
+      ctr_z[i] = c->pass[i].ctr_zeroed;
+    }
+    stage_block(c, r, cent, ncent, q0, nq, nprev, append_step);
+    sync_streams(c);
+    for (int i = 0; i < kPeerTiles; i++)
+      if (ctr_p[i] && c->pass[i].d_counters.p == ctr_p[i]) c->pass[i].ctr_zeroed = ctr_z[i];
+    r.lazy = (flags & UMICLUST_PASS_LAZY) != 0;
+    Pass& P = c->pass[nprev % 2];
+    for (Pass& Q : c->pass)
+      if (&Q != &P) Q.nq = 0;
+    std::fill(r.state_buf.begin(), r.state_buf.begin() + w0, (uint8_t)ST_MEMBER);
+    std::copy(win_state, win_state + (q0 - w0), r.state_buf.begin() + w0);
+    if (flags & UMICLUST_PASS_PREV) r.second_half(nprev - 1, 0, false);
+    r.second_half(nprev, 0, false);
+    const auto rb0 = c->dbg.rb;
+    int32_t done = 0;
+    const bool all = resolve_pass(c, P, r.state, r.new_cents, r.t_pf, r.t_al, r.t_host,
+                                  (flags & UMICLUST_RESOLVE_PARTIAL) ? &done : nullptr);
+    if (!(flags & UMICLUST_RESOLVE_PARTIAL)) done = all ? nq : 0;
+    sync_streams(c);
+    c->hip(hipStreamSynchronize(c->st_copy), "sync");
+    for (Pass& Q : c->pass) Q.live = false;
+    for (int32_t i = 0; i < nq; i++) {
+      if (state) state[i] = r.state[q0 + i];
+      if (target) target[i] = c->target[(size_t)(q0 + i)];
+      if (strand) strand[i] = c->strand[(size_t)(q0 + i)];
+    }
+    const int64_t nc = done > 0 ? (int64_t)r.new_cents.size() : 0;
+    if (new_cents) std::copy(r.new_cents.begin(), r.new_cents.begin() + nc, new_cents);
+    if (info) {
+      info[0] = done;
+      info[1] = all ? 1 : 0;
+      info[2] = nc;
+      info[3] = c->stats.n_alignments;
+      info[4] = c->stats.cells;
+      info[5] = c->stats.n_merged_walks;
+      info[6] = c->stats.n_deferred;
+      info[7] = c->stats.pairs_round_b;
+      info[8] = (int64_t)(c->dbg.rb.trips - rb0.trips);
+      info[9] = (int64_t)(c->dbg.rb.launches - rb0.launches);
+      info[10] = (int64_t)(c->dbg.rb.pairs - rb0.pairs);
+      info[11] = c->both;
+      info[12] = (int64_t)(c->dbg.rb.staged - rb0.staged);
+    }
     return UMICLUST_OK;
   });
 }

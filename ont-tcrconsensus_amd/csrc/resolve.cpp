@@ -11,7 +11,7 @@
 // makes the host run the exact merged walk over T_old u (peers that are centroids) -- every such peer now matters,
 // so an undetermined one blocks too.  A merged walk that needs an alignment the pass did not compute (a T_old entry
 // past the device walk, or a peer that was not aligned) is deferred to round B, and so are queries blocked by
-// deferred ones.  Classification runs on the worker pool (every strand whose outcome needs no in-order state is
+// deferred ones; round B asks for a peer only once it is known to be a centroid.  Classification runs on the worker pool (every strand whose outcome needs no in-order state is
 // resolved there); the in-order phase and round B run on the calling thread.
 #include "resolve.h"
 
@@ -624,51 +624,81 @@ int resolve_block(const ResolveEnv& env, int32_t q0, int32_t nq, int32_t w0, con
   }
   rst.t_inorder_s += now_s() - tp1;
   rst.n_deferred += (int64_t)deferred.size();
-  // --- round B (side stream, so the queued pass keeps the device busy): align every T_old entry and
-  // every peer a deferred query could still need, then resolve the deferred queries in order
+  // --- round B (side stream, so the queued pass keeps the device busy): align every T_old entry past the device
+  // walk and every centroid peer the pass did not align, then resolve the deferred queries.  Only centroids enter a
+  // merged walk, so a peer is asked for once it is known to be one: a peer that is itself deferred is undetermined
+  // now, and if it ends up a member nothing is aligned against it.  A deferred query is resolved once its peers are
+  // all determined and its centroid peers aligned (its outcome depends on nothing else, so the order among the
+  // deferred does not matter); one that waits for a deferred peer that turned out a centroid takes another trip.
+  // Usually there is one: the first trip serves every deferred query whose deferred peers end up members.
   if (!deferred.empty()) {
-    std::vector<uint32_t> bpq, bpt, bidx;
-    for (int32_t ql : deferred)
-      for (int s = 0; s < both; s++) {
-        const int32_t qs = ql * both + s;
-        const HostQs& h = hq[qs];
-        if (h.rec == 0xffffffffu) continue;
-        const Rec R = rec_of(h);
-        const uint32_t qv = ((uint32_t)(q0 + ql) << 1) | (uint32_t)s;
-        for (int x = h.e; x < R.nt; x++) {
-          bpq.push_back(qv);
-          bpt.push_back(R.seq[x]);
-          bidx.push_back((uint32_t)(qs * kSlots + x));
-        }
-        for (int y = 0; y < R.np; y++)
-          // a peer that is a member never enters the merged walk (only centroids are candidates)
-          if (!((R.peer[y] >> 25) & 1u) && state[(uint32_t)w0 + (R.peer[y] & 0xffffu)] != ST_MEMBER) {
-            bpq.push_back(qv);
-            bpt.push_back((uint32_t)w0 + (R.peer[y] & 0xffffu));
-            bidx.push_back((uint32_t)(qs * kSlots + kWalk + y));
-          }
-      }
-    const int32_t nb = (int32_t)bpq.size();
-    rst.pairs_round_b += nb;
-    for (int32_t x = 0; x < nb; x++) rst.cells_round_b += (int64_t)env.hlen[bpq[x] >> 1] * env.hlen[bpt[x]];
-    std::vector<uint32_t> bres(nb);
-    if (nb > 0) {
-      const double tb0 = now_s();
-      round_b(bpq, bpt, bres);
-      rst.t_round_b_s += now_s() - tb0;
-    }
     extra_row.assign((size_t)nqs, -1);
     for (size_t r = 0; r < deferred.size(); r++)
       for (int s = 0; s < both; s++) extra_row[(size_t)deferred[r] * both + s] = (int32_t)(r * both + s);
     extra_res.assign(deferred.size() * both * kSlots, 0);
     extra_have.assign(deferred.size() * both * kSlots, 0);
-    for (int32_t x = 0; x < nb; x++) {
-      const int32_t qs = (int32_t)(bidx[x] / kSlots), e = (int32_t)(bidx[x] % kSlots);
-      extra_res[(size_t)extra_row[qs] * kSlots + e] = bres[x];
-      extra_have[(size_t)extra_row[qs] * kSlots + e] = 1;
+    std::vector<uint8_t> asked(deferred.size() * both * kSlots, 0);
+    std::vector<int32_t> open = deferred, rest;
+    std::vector<uint32_t> bpq, bpt, bidx, bres;
+    for (bool first = true; !open.empty(); first = false) {
+      bpq.clear();
+      bpt.clear();
+      bidx.clear();
+      for (int32_t ql : open)
+        for (int s = 0; s < both; s++) {
+          const int32_t qs = ql * both + s;
+          const HostQs& h = hq[qs];
+          if (h.rec == 0xffffffffu) continue;
+          const Rec R = rec_of(h);
+          const uint32_t qv = ((uint32_t)(q0 + ql) << 1) | (uint32_t)s;
+          uint8_t* a = asked.data() + (size_t)extra_row[qs] * kSlots;
+          for (int x = h.e; first && x < R.nt; x++) {
+            bpq.push_back(qv);
+            bpt.push_back(R.seq[x]);
+            bidx.push_back((uint32_t)(qs * kSlots + x));
+          }
+          for (int y = 0; y < R.np; y++)
+            if (!((R.peer[y] >> 25) & 1u) && !a[kWalk + y] && state[(uint32_t)w0 + (R.peer[y] & 0xffffu)] == ST_CENT) {
+              a[kWalk + y] = 1;
+              bpq.push_back(qv);
+              bpt.push_back((uint32_t)w0 + (R.peer[y] & 0xffffu));
+              bidx.push_back((uint32_t)(qs * kSlots + kWalk + y));
+            }
+        }
+      const int32_t nb = (int32_t)bpq.size();
+      rst.pairs_round_b += nb;
+      for (int32_t x = 0; x < nb; x++) rst.cells_round_b += (int64_t)env.hlen[bpq[x] >> 1] * env.hlen[bpt[x]];
+      bres.assign((size_t)nb, 0);
+      if (nb > 0) {
+        const double tb0 = now_s();
+        round_b(bpq, bpt, bres);
+        rst.t_round_b_s += now_s() - tb0;
+      }
+      for (int32_t x = 0; x < nb; x++) {
+        const int32_t qs = (int32_t)(bidx[x] / kSlots), e = (int32_t)(bidx[x] % kSlots);
+        extra_res[(size_t)extra_row[qs] * kSlots + e] = bres[x];
+        extra_have[(size_t)extra_row[qs] * kSlots + e] = 1;
+      }
+      rest.clear();
+      for (int32_t ql : open) {
+        bool ready = true;  // every peer determined, every centroid peer aligned
+        for (int s = 0; s < both && ready; s++) {
+          const int32_t qs = ql * both + s;
+          const HostQs& h = hq[qs];
+          if (h.rec == 0xffffffffu) continue;
+          const Rec R = rec_of(h);
+          const uint8_t* a = asked.data() + (size_t)extra_row[qs] * kSlots;
+          for (int y = 0; y < R.np && ready; y++) {
+            const uint8_t st = state[(uint32_t)w0 + (R.peer[y] & 0xffffu)];
+            ready = st == ST_MEMBER || (st == ST_CENT && (((R.peer[y] >> 25) & 1u) || a[kWalk + y]));
+          }
+        }
+        if (!ready) rest.push_back(ql);
+        else if (!resolve(ql, true, strand_outcome)) return kResolveStuck;
+      }
+      if (nb == 0 && rest.size() == open.size()) return kResolveStuck;  // nothing asked, nothing resolved
+      open.swap(rest);
     }
-    for (int32_t ql : deferred)
-      if (!resolve(ql, true, strand_outcome)) return kResolveStuck;
     std::sort(new_cents.begin(), new_cents.end());
   }
   rst.n_merged_walks += scr0.merged;

@@ -147,7 +147,7 @@ EXPORTS = [
     "umiclust_timeline", "umiclust_wait_host", "umiclust_fastq_filter_params_from_argv", "umiclust_fastq_filter",
     "umiclust_fastq_filter_argv", "umiclust_fastq_filter_stats", "umiclust_fastq_filter_stats_argv",
     "umiclust_fastq_ee", "umiclust_fastq_record_stats", "umiclust_prefilter", "umiclust_consensus", "umiclust_pass",
-    "umiclust_prefilter_pack", "umiclust_prefilter_split",
+    "umiclust_prefilter_pack", "umiclust_prefilter_split", "umiclust_resolve",
     "umiclust_bam_open", "umiclust_bam_counts", "umiclust_bam_times", "umiclust_bam_columns", "umiclust_bam_refs",
     "umiclust_bam_strings", "umiclust_bam_cs_groups", "umiclust_bam_write", "umiclust_bam_split",
     "umiclust_bam_name_suffix", "umiclust_bam_close", "umiclust_region_split_extract", "umiclust_bam_split_extract",
@@ -297,6 +297,10 @@ def lib() -> C.CDLL:
     L.umiclust_prefilter_pack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P(C.c_int32)] + [C.c_int32] * 5 + lists
     L.umiclust_prefilter_split.restype = C.c_int32
     L.umiclust_prefilter_split.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, P(C.c_int32)] + [C.c_int32] * 4 + lists
+    L.umiclust_resolve.restype = C.c_int32
+    L.umiclust_resolve.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_uint32, P(C.c_uint8), P(C.c_uint8), P(C.c_int32), P(C.c_uint8), P(C.c_int32),
+                                   P(C.c_int64)]
     L.umiclust_pass.restype = C.c_int32
     L.umiclust_pass.argtypes = [C.c_void_p, P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_uint32, P(C.c_uint32), P(C.c_uint8), P(C.c_uint8), P(C.c_uint16), P(C.c_uint8),
@@ -1003,6 +1007,37 @@ class Context:
                     rec=rec[:min(int(total[0]), cap)], rec_total=int(total[0]), res=res[:n * 32].reshape(n, 32),
                     peer_res=res[n * 32:n * 160].reshape(n, 128), aligned=aligned[:n], walk=walk[:n],
                     counters=counters)
+
+    def run_resolve(self, cent, q0: int, nq: int, nprev: int = 0, win_state=(), append_step: int = 1 << 30,
+                    lazy: bool = False, prev: bool = False, partial: bool = False) -> dict:
+        """umiclust_resolve on the current load: the pass of the block [q0, q0 + nq) queued as run_pass queues it, then
+        resolved by the pipeline's own resolve step with the window's states `win_state` (1 centroid, 2 member per
+        query of [q0 - nprev * nq, q0)), round B on the device.  state / target / strand per query, new_cents,
+        resolved (queries), all (bool), the resolve step's n_alignments, cells, n_merged_walks, n_deferred,
+        pairs_round_b, and round B's trips, launches, pairs and staged trips (rb_*) on the device side."""
+        ce = np.ascontiguousarray(cent, np.int32)
+        ws = np.ascontiguousarray(win_state, np.uint8)
+        if len(ws) != nprev * nq:
+            raise ValueError("win_state must hold nprev * nq states")
+        n = max(nq, 1)
+        state = np.zeros(n, np.uint8)
+        target = np.full(n, -1, np.int32)
+        strand = np.zeros(n, np.uint8)
+        newc = np.zeros(n, np.int32)
+        info = np.zeros(16, np.int64)
+        P = C.POINTER
+        u8 = lambda a: a.ctypes.data_as(P(C.c_uint8))  # noqa: E731
+        i32 = lambda a: a.ctypes.data_as(P(C.c_int32))  # noqa: E731
+        rc = lib().umiclust_resolve(self._h, i32(ce), len(ce), q0, nq, nprev, append_step,
+                                    (1 if lazy else 0) | (2 if prev else 0) | (4 if partial else 0), u8(ws), u8(state),
+                                    i32(target), u8(strand), i32(newc), _i64(info))
+        self._check(rc, "resolve")
+        keys = ("resolved", "all", "n_new", "n_alignments", "cells", "n_merged_walks", "n_deferred", "pairs_round_b",
+                "rb_trips", "rb_launches", "rb_pairs", "both", "rb_staged")
+        out = {k: int(v) for k, v in zip(keys, info)}
+        out.update(state=state[:nq], target=target[:nq], strand=strand[:nq], new_cents=newc[:out["n_new"]],
+                   all=bool(out["all"]))
+        return out
 
     def prep(self, p: Params, seqs) -> dict:
         b, o = _pack(seqs)
