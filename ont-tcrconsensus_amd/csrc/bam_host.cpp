@@ -13,25 +13,20 @@
 namespace uc {
 namespace bam {
 
-namespace {
-uint32_t ld_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-}  // namespace
-
 bool parse_header(const uint8_t* raw, size_t n, Header& h, std::string& err) {
   h = Header();
   if (n < 12 || memcmp(raw, "BAM\1", 4) != 0) {
     err = "not BAM";
     return false;
   }
-  const int32_t lt = (int32_t)ld_u32(raw + 4);
+  const int32_t lt = (int32_t)le32(raw + 4);
   if (lt < 0 || (size_t)lt > n - 12) {
     err = "truncated BAM header";
     return false;
   }
   h.text_len = (size_t)lt;
   size_t o = 8 + (size_t)lt;
-  const int32_t nref = (int32_t)ld_u32(raw + o);
+  const int32_t nref = (int32_t)le32(raw + o);
   o += 4;
   if (nref < 0 || (size_t)nref > (n - o) / 8) {
     err = "truncated BAM header";
@@ -44,13 +39,13 @@ bool parse_header(const uint8_t* raw, size_t n, Header& h, std::string& err) {
       err = "truncated BAM header";
       return false;
     }
-    const int32_t ln = (int32_t)ld_u32(raw + o);
+    const int32_t ln = (int32_t)le32(raw + o);
     if (ln < 0 || (size_t)ln > n - o - 8) {
       err = "truncated BAM header";
       return false;
     }
     h.ref_name[r] = std::string((const char*)raw + o + 4, (size_t)std::max(0, ln - 1));
-    h.ref_len[r] = (int64_t)(int32_t)ld_u32(raw + o + 4 + (size_t)ln);
+    h.ref_len[r] = (int64_t)(int32_t)le32(raw + o + 4 + (size_t)ln);
     o += 4 + (size_t)ln + 4;
   }
   h.end = o;
@@ -61,7 +56,7 @@ bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int6
   roff.clear();
   size_t o = start;
   while (o + 4 <= n) {
-    const int32_t bs = (int32_t)ld_u32(raw + o);
+    const int32_t bs = (int32_t)le32(raw + o);
     if (bs < 32 || (size_t)bs > n - o - 4) {
       err = "truncated BAM record " + std::to_string(roff.size());
       return false;
@@ -78,11 +73,9 @@ bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int6
 
 bool check_record_fields(const uint8_t* raw, const std::vector<int64_t>& roff, std::string& err) {
   for (size_t r = 0; r < roff.size(); r++) {
-    const uint8_t* f = raw + roff[r] + 4;
-    const int64_t bs = (int64_t)ld_u32(raw + roff[r]);
-    const int64_t lrn = f[8], ncig = ld_u16(f + 12), lseq = (int32_t)ld_u32(f + 16);
-    // offsets from the block_size field: 36 fixed bytes, name, CIGAR, 4-bit sequence, qualities
-    if (lrn < 1 || lseq < 0 || 36 + lrn + 4 * ncig + (lseq + 1) / 2 + lseq > 4 + bs) {
+    const uint8_t* rec = raw + roff[r];
+    const int64_t bs = block_size(rec), lrn = l_read_name(rec), ncig = n_cigar_op(rec), lseq = l_seq(rec);
+    if (!fits(lrn, ncig, lseq, bs)) {
       err = "BAM record " + std::to_string(r) + ": l_read_name " + std::to_string(lrn) + ", n_cigar_op " +
             std::to_string(ncig) + ", l_seq " + std::to_string(lseq) + " do not fit block_size " + std::to_string(bs);
       return false;
@@ -93,26 +86,25 @@ bool check_record_fields(const uint8_t* raw, const std::vector<int64_t>& roff, s
 
 void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask, ScanRow& out) {
   out = ScanRow();
-  const uint8_t* f = raw + roff + 4;
-  const int64_t end = roff + 4 + (int64_t)ld_u32(raw + roff);
-  const uint32_t lrn = f[8], ncig = ld_u16(f + 12), flag = ld_u16(f + 14);
-  const int32_t lseq = (int32_t)ld_u32(f + 16);
-  out.ref = (int32_t)ld_u32(f);
+  const uint8_t* rec = raw + roff;
+  const int64_t end = roff + 4 + (int64_t)block_size(rec);
+  const uint32_t lrn = l_read_name(rec), ncig = n_cigar_op(rec), flag = bam::flag(rec);
+  const int32_t lseq = l_seq(rec);
+  out.ref = ref_id(rec);
   out.l_seq = lseq;
-  out.cls = (flag & 0x4u) ? kScanUnmapped : (flag & 0x900u) ? kScanSecondary : kScanPrimary;
-  const int64_t cig = roff + 36 + (int64_t)lrn, cigend = cig + 4 * (int64_t)ncig;
-  const int64_t aux = cigend + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
+  out.cls = (flag & kFlagUnmapped) ? kScanUnmapped : (flag & kFlagNotPrimary) ? kScanSecondary : kScanPrimary;
+  const int64_t aux = roff + aux_offset(lrn, ncig, lseq);
   if (lseq < 0 || aux > end) {
     out.bad = 1;
     return;
   }
   int64_t rl = 0, cols = 0;
   for (uint32_t x = 0; x < ncig; x++) {
-    const uint32_t v = ld_u32(raw + cig + 4 * (int64_t)x), op = v & 15u;
-    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += v >> 4;
-    if (op <= 2) cols += v >> 4;
+    const uint32_t v = le32(cigar(rec, lrn) + 4 * (int64_t)x), op = v & 15u;
+    if (op_on_reference(op)) rl += v >> 4;
+    if (op_in_columns(op)) cols += v >> 4;
   }
-  out.reference_length = rl ? rl : 1;  // htslib's bam_endpos: a zero reference span counts as 1
+  out.reference_length = reference_span(rl);
   out.cols = cols;
   if (out.cls != kScanPrimary) return;  // the reference never reads the tags of the other records
   bool have_nm = false, have_cs = false;
@@ -125,22 +117,14 @@ void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask
     const uint8_t t0 = raw[cur], t1 = raw[cur + 1], ty = raw[cur + 2];
     const bool is_nm = t0 == 'N' && t1 == 'M' && !have_nm, is_cs = t0 == 'c' && t1 == 's' && !have_cs;
     const int64_t v = cur + 3;
-    int sz = 0;
-    switch (ty) {
-      case 'A': case 'c': case 'C': sz = 1; break;
-      case 's': case 'S': sz = 2; break;
-      case 'i': case 'I': case 'f': sz = 4; break;
-      default: break;
-    }
+    const int sz = aux_fixed_size(ty);
     if (sz) {
       if (v + sz > end || is_cs || (is_nm && (ty == 'A' || ty == 'f'))) {
         out.bad = 1;
         return;
       }
       if (is_nm) {
-        const uint8_t* q = raw + v;
-        out.nm = ty == 'c' ? (int64_t)(int8_t)q[0] : ty == 'C' ? (int64_t)q[0] : ty == 's' ? (int64_t)(int16_t)ld_u16(q)
-                 : ty == 'S' ? (int64_t)ld_u16(q) : ty == 'i' ? (int64_t)(int32_t)ld_u32(q) : (int64_t)ld_u32(q);
+        out.nm = aux_int_value(ty, raw + v);
         out.nm_present = 1;
         have_nm = true;
       }
@@ -150,9 +134,8 @@ void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask
         out.bad = 1;
         return;
       }
-      const uint8_t sub = raw[v];
-      const int64_t cnt = (int64_t)ld_u32(raw + v + 1);
-      const int ss = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+      const int64_t cnt = (int64_t)le32(raw + v + 1);
+      const int ss = aux_array_elem_size(raw[v]);
       if (!ss || v + 5 + ss * cnt > end) {
         out.bad = 1;
         return;
@@ -189,27 +172,19 @@ void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask
 
 // ---------------------------------------------------------------- detected-UMI record (row f4+f1)
 std::string forward_text(const uint8_t* rec) {
-  const uint8_t* f = rec + 4;
-  const uint32_t lrn = f[8], ncig = ld_u16(f + 12), flag = ld_u16(f + 14);
-  const int32_t lseq = (int32_t)ld_u32(f + 16);
+  const int32_t lseq = l_seq(rec);
   if (lseq <= 0) return "None";
-  const uint8_t* sq = f + 32 + lrn + 4 * (size_t)ncig;
-  const bool rev = (flag & 0x10u) != 0;
+  const uint8_t* sq = seq(rec, l_read_name(rec), n_cigar_op(rec));
+  const bool rev = (flag(rec) & kFlagReverse) != 0;
   std::string out((size_t)lseq, '\0');
-  for (int32_t x = 0; x < lseq; x++) {
-    const int32_t y = rev ? lseq - 1 - x : x;
-    char ch = "=ACMGRSVTWYHKDBN"[(sq[y >> 1] >> (((y & 1) ^ 1) * 4)) & 15u];
-    if (rev) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-    out[(size_t)x] = ch;
-  }
+  for (int32_t x = 0; x < lseq; x++) out[(size_t)x] = forward_base(sq, lseq, rev, x);
   return out;
 }
 
 std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3) {
-  const uint8_t* f = rec + 4;
   const std::string read = forward_text(rec);
-  std::string hdr((const char*)f + 32, (size_t)f[8] - 1);
-  hdr += (ld_u16(f + 14) & 0x10u) ? ";strand=-" : ";strand=+";
+  std::string hdr((const char*)name(rec), (size_t)l_read_name(rec) - 1);
+  hdr += (flag(rec) & kFlagReverse) ? ";strand=-" : ";strand=+";
   const std::string rid = hdr.substr(0, hdr.find(';'));
   const size_t s0 = hdr.find("strand=") + 7, s1 = hdr.find("strand=", s0);
   const std::string strand = hdr.substr(s0, s1 == std::string::npos ? s1 : s1 - s0);
@@ -222,10 +197,7 @@ std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3
     out += u5 + u3;
   } else {
     for (const std::string* u : {&u3, &u5})
-      for (size_t x = u->size(); x-- > 0;) {
-        const char ch = (*u)[x];
-        out.push_back(ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'T' ? 'A' : ch == 'G' ? 'C' : ch);
-      }
+      for (size_t x = u->size(); x-- > 0;) out.push_back(complement((*u)[x]));
   }
   out.push_back('\n');
   return out;
@@ -283,7 +255,7 @@ BgzfStream bgzf_stream(const uint8_t* raw, size_t header_end, const std::vector<
   S.seg.emplace_back(0, header_end);
   for (size_t r = 0; r < roff.size(); r++)
     if (keep[r]) {
-      const size_t o = (size_t)roff[r], n = 4 + (size_t)ld_u32(raw + o);
+      const size_t o = (size_t)roff[r], n = 4 + (size_t)block_size(raw + o);
       if (S.seg.back().first + S.seg.back().second == o) S.seg.back().second += n;
       else S.seg.emplace_back(o, n);
       S.nkept++;

@@ -1,6 +1,6 @@
 // bam_host.h -- the HIP-free host side of the BAM readers and of the BAM writer (rows f4 and f6):
-// header parsing and record offsets (shared by umiclust_region_split and the umiclust_bam_* session), the host
-// restatement of k_bam_scan (csrc/bamscan.hip) and the BGZF writer.  Compiled by g++ (no HIP), so the CPU suite
+// header parsing and record offsets (shared by umiclust_region_split and the umiclust_bam_* session), the serial walk
+// of k_bam_scan (csrc/bamscan.hip) over the rules of bam_record.h, and the BGZF writer.  Compiled by g++ (no HIP), so the CPU suite
 // builds it with ASan + UBSan (tools/bam_check_main.cpp, tests/test_bam_filter_cpu.py).
 #pragma once
 #include <stdint.h>
@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "bam_record.h"
 
 namespace uc {
 namespace bam {
@@ -24,17 +26,12 @@ bool parse_header(const uint8_t* raw, size_t n, Header& h, std::string& err);
 // block_size is smaller than the 32 fixed bytes
 bool record_offsets(const uint8_t* raw, size_t n, size_t start, std::vector<int64_t>& roff, std::string& err);
 
-// the variable-length fields of every record stay inside the record: l_read_name >= 1, l_seq >= 0 and
-// 36 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size.  The f4 kernels (regionsplit.hip)
+// the variable-length fields of every record stay inside the record (bam::fits).  The f4 kernels (regionsplit.hip)
 // index the name, the CIGAR and the sequence by these fields alone, so umiclust_region_split checks them before any
 // launch.  false + err naming the first record that fails
 bool check_record_fields(const uint8_t* raw, const std::vector<int64_t>& roff, std::string& err);
 
-// block_size of the record whose block_size field is at p
-inline uint32_t rd_block(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
-// ---- the per-record columns of k_bam_scan ----
-constexpr uint64_t kCsEmpty = ~0ull;   // the group table's empty key: never a cs_hash
+// ---- the per-record columns of k_bam_scan (the cs hash: bam_record.h) ----
 enum : int8_t { kScanUnmapped = 0, kScanSecondary = 1, kScanPrimary = 2 };
 struct ScanRow {
   int8_t cls = 0, bad = 0;
@@ -43,36 +40,17 @@ struct ScanRow {
   int64_t reference_length = 0, cols = 0, nm = 0, cs_off = 0;
   uint64_t cs_hash = 0;
 };
-// The hash of a cs string, order-independent over its bytes so that a wave can sum 64 positions a step:
-// mix(sum over x of mix(seed + (x + 1) * K1 + (byte + 1) * K2) ^ len * K3) & hmask, kCsEmpty mapped to kCsEmpty - 1.
-inline uint64_t mix64(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-constexpr uint64_t kCsK1 = 0x9e3779b97f4a7c15ull, kCsK2 = 0xd6e8feb86659fd93ull, kCsK3 = 0xa0761d6478bd642full;
-inline uint64_t cs_term(uint64_t seed, uint64_t x, uint8_t b) { return mix64(seed + (x + 1) * kCsK1 + ((uint64_t)b + 1) * kCsK2); }
-inline uint64_t cs_finish(uint64_t sum, uint64_t len, uint64_t hmask) {
-  const uint64_t h = mix64(sum ^ (len * kCsK3)) & hmask;
-  return h == kCsEmpty ? h - 1 : h;
-}
-// seed of hashing pass k (pass 0 first; a detected collision moves on to k + 1)
-inline uint64_t cs_seed(int k) { return 0x243f6a8885a308d3ull + (uint64_t)k * 0x13198a2e03707345ull; }
-
 // one record, exactly as the kernel computes it (roff = offset of its block_size field)
 void scan_record(const uint8_t* raw, int64_t roff, uint64_t seed, uint64_t hmask, ScanRow& out);
 
 // ---- the detected-UMI record of one BAM record (row f4+f1) ----
-// The read as k_bam_emit (regionsplit.hip) writes it: the forward sequence (reverse strand: reversed, A/C/G/T
-// complemented), "None" for a record without one.  rec = the record's block_size field; its fields have been checked.
+// The read as k_bam_emit (regionsplit.hip) writes it: the forward sequence (bam::forward_base), "None" for a record
+// without one.  rec = the record's block_size field; its fields have been checked.
 std::string forward_text(const uint8_t* rec);
 // What extract_umis.py prints for the FASTA entry ">{name};strand={+|-}" + forward_text, given the six values of
 // umiclust_extract_umis (both UMIs found) and the 3' window length a3: read name = header up to its first ';', strand
 // = header.split("strand=")[1], combined UMI = u5 + u3 on "+", their reverse complements swapped on anything else.
-// The host restatement of k_bam_emit_umi, and the formatter of the records whose name holds "strand=".
+// The serial counterpart of k_bam_emit_umi, and the formatter of the records whose name holds "strand=".
 std::string format_umi_record(const uint8_t* rec, const int32_t* res, int32_t a3);
 
 // ---- BGZF writer ----

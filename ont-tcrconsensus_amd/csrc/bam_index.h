@@ -1,11 +1,12 @@
 // bam_index.h -- the .bai index and flagstat of a BAM stream, HIP-free (policies O10 and O11: restated
 // from the SAM specification §5 and samtools' flagstat, not pinned to a samtools binary).
 //
-// The per-record rules are here once, for the host and for the device: what a record spans on its reference, its bin,
-// the virtual offset of a stream position under a block table, the order and range tests, and which of the 32 flagstat
-// counters it adds to.  bamindex.hip runs them one thread a record; bai::build_host below is the plain serial
-// restatement of those kernels (tools/bai_check_main.cpp, tests/test_bai_cpu.py).  What follows the kernels -- the
-// finish over the runs, the file's bytes, the flagstat text -- is host code only and shared by both.
+// The per-record rules are here once, for the host and for the device, on the layout of bam_record.h: what a record
+// spans on its reference, its bin, the virtual offset of a stream position under a block table, the order and range
+// tests, and which of the 32 flagstat counters it adds to.  bamindex.hip runs them one thread a record;
+// bai::build_host below is the plain serial restatement of those kernels (tools/bai_check_main.cpp,
+// tests/test_bai_cpu.py).  What follows the kernels -- the finish over the runs, the file's bytes, the flagstat text --
+// is host code only and shared by both.
 //
 // The block table of a compressed file: block b starts at compressed offset coff[b] and holds the stream bytes
 // [ustart[b], ustart[b + 1]); every block of the file is listed, empty ones too, and the last entry is the block that
@@ -19,13 +20,7 @@
 #include <string>
 #include <vector>
 
-#ifndef UC_HD
-#if defined(__HIPCC__)
-#define UC_HD __host__ __device__
-#else
-#define UC_HD
-#endif
-#endif
+#include "bam_record.h"  // the record's layout, and UC_HD
 
 namespace uc {
 namespace bai {
@@ -34,15 +29,11 @@ enum : int32_t { kOk = 0, kUnsorted = 1, kRange = 2, kBadRef = 3 };
 constexpr int64_t kMaxEnd = (int64_t)1 << 29;  // what min_shift 14 and depth 5 address
 constexpr int32_t kMetaBin = 37450;
 constexpr int kCounters = 32;
-// counter 2 * k + w: row k of the flagstat text, w = 1 for a QC-failed record (flag & 0x200)
+// counter 2 * k + w: row k of the flagstat text, w = 1 for a QC-failed record
 enum : int {
   kTotal = 0, kPrimary, kSecondary, kSupplementary, kDup, kPrimaryDup, kMapped, kPrimaryMapped, kPaired, kRead1,
   kRead2, kProper, kBothMapped, kSingleton, kDiffChr, kDiffChrQ5
 };
-
-UC_HD inline uint32_t ld32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
 
 // What the rules read of one record; rec = its block_size field.  The CIGAR is read inside the record only: a record
 // whose fields overrun it (the session's open has named those among the primary ones) is cut there, never read past.
@@ -53,36 +44,25 @@ struct Rec {
 };
 UC_HD inline Rec read_record(const uint8_t* rec) {
   Rec r;
-  const int64_t bs = (int64_t)ld32(rec);
-  r.tid = (int32_t)ld32(rec + 4);
-  r.beg = (int32_t)ld32(rec + 8);
-  const int64_t lrn = rec[12];
-  r.mapq = rec[13];
-  int64_t ncig = (int64_t)rec[16] | ((int64_t)rec[17] << 8);
-  r.flag = (uint32_t)rec[18] | ((uint32_t)rec[19] << 8);
-  r.next_tid = (int32_t)ld32(rec + 24);
+  const int64_t bs = (int64_t)bam::block_size(rec);
+  r.tid = bam::ref_id(rec);
+  r.beg = bam::pos(rec);
+  const int64_t lrn = bam::l_read_name(rec);
+  r.mapq = bam::mapq(rec);
+  int64_t ncig = bam::n_cigar_op(rec);
+  r.flag = bam::flag(rec);
+  r.next_tid = bam::next_ref_id(rec);
   ncig = ncig < (bs - 32 - lrn) / 4 ? ncig : (bs - 32 - lrn) / 4;
   int64_t rlen = 0;
-  if (!(r.flag & 4) && ncig > 0) {
-    const uint8_t* c = rec + 36 + lrn;
+  if (!(r.flag & bam::kFlagUnmapped) && ncig > 0) {
+    const uint8_t* c = bam::cigar(rec, (uint32_t)lrn);
     for (int64_t k = 0; k < ncig; k++) {
-      const uint32_t v = ld32(c + 4 * k), op = v & 15;
-      if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += v >> 4;  // M D N = X
+      const uint32_t v = bam::le32(c + 4 * k);
+      if (bam::op_on_reference(v & 15)) rlen += v >> 4;
     }
   }
-  r.end = r.beg + (rlen ? rlen : 1);
+  r.end = r.beg + bam::reference_span(rlen);
   return r;
-}
-
-/* calculate bin given an alignment covering [beg,end) (zero-based, half-closed-half-open) */
-UC_HD inline int reg2bin(int beg, int end) {
-  --end;
-  if (beg >> 14 == end >> 14) return ((1 << 15) - 1) / 7 + (beg >> 14);
-  if (beg >> 17 == end >> 17) return ((1 << 12) - 1) / 7 + (beg >> 17);
-  if (beg >> 20 == end >> 20) return ((1 << 9) - 1) / 7 + (beg >> 20);
-  if (beg >> 23 == end >> 23) return ((1 << 6) - 1) / 7 + (beg >> 23);
-  if (beg >> 26 == end >> 26) return ((1 << 3) - 1) / 7 + (beg >> 26);
-  return 0;
 }
 
 // the record's own status: BAI cannot address it, or the header has no such reference
@@ -109,21 +89,21 @@ UC_HD inline uint64_t voffset(int64_t p, const int64_t* coff, const int64_t* ust
   return (uint64_t)coff[lo + 1] << 16;
 }
 
-// bit k of the result: the record adds to row k of flagstat (its column is flag & 0x200)
+// bit k of the result: the record adds to row k of flagstat (its column is the QC-fail bit)
 UC_HD inline uint32_t flagstat_rows(const Rec& r) {
   const uint32_t f = r.flag;
   uint32_t m = 1u << kTotal;
-  if (f & 0x100) m |= 1u << kSecondary;
-  else if (f & 0x800) m |= 1u << kSupplementary;
+  if (f & bam::kFlagSecondary) m |= 1u << kSecondary;
+  else if (f & bam::kFlagSupplementary) m |= 1u << kSupplementary;
   else {
     m |= 1u << kPrimary;
     if (f & 0x1) {
       m |= 1u << kPaired;
-      if ((f & 0x2) && !(f & 0x4)) m |= 1u << kProper;
+      if ((f & 0x2) && !(f & bam::kFlagUnmapped)) m |= 1u << kProper;
       if (f & 0x40) m |= 1u << kRead1;
       if (f & 0x80) m |= 1u << kRead2;
-      if ((f & 0x8) && !(f & 0x4)) m |= 1u << kSingleton;
-      if (!(f & 0x4) && !(f & 0x8)) {
+      if ((f & 0x8) && !(f & bam::kFlagUnmapped)) m |= 1u << kSingleton;
+      if (!(f & bam::kFlagUnmapped) && !(f & 0x8)) {
         m |= 1u << kBothMapped;
         if (r.next_tid != r.tid) {
           m |= 1u << kDiffChr;
@@ -131,10 +111,10 @@ UC_HD inline uint32_t flagstat_rows(const Rec& r) {
         }
       }
     }
-    if (!(f & 0x4)) m |= 1u << kPrimaryMapped;
+    if (!(f & bam::kFlagUnmapped)) m |= 1u << kPrimaryMapped;
     if (f & 0x400) m |= 1u << kPrimaryDup;
   }
-  if (!(f & 0x4)) m |= 1u << kMapped;
+  if (!(f & bam::kFlagUnmapped)) m |= 1u << kMapped;
   if (f & 0x400) m |= 1u << kDup;
   return m;
 }
@@ -175,23 +155,23 @@ inline void build_host(const uint8_t* raw, int64_t header_end, const std::vector
     if (keep && !keep[r]) continue;
     const uint8_t* p = raw + roff[r];
     const Rec R = read_record(p);
-    const int64_t size = 4 + (int64_t)ld32(p);
+    const int64_t size = 4 + (int64_t)bam::block_size(p);
     int32_t st = range_status(R, nref);
     if (!st && have_prev && out_of_order(ptid, pbeg, R.tid, R.beg)) st = kUnsorted;
     if (st && K.first_bad < 0) K.first_bad = (int64_t)r, K.first_status = st;
     const bool placed = R.tid >= 0 && R.tid < nref;
     const bool ok = placed && st != kRange;
     K.tid.push_back(R.tid), K.status.push_back(st);
-    K.bin.push_back(ok ? reg2bin((int)R.beg, (int)R.end) : 0);
+    K.bin.push_back(ok ? bam::reg2bin(R.beg, R.end) : 0);
     K.w0.push_back(ok ? (int32_t)(R.beg >> 14) : 0), K.w1.push_back(ok ? (int32_t)((R.end - 1) >> 14) : 0);
     K.u.push_back(nblocks ? voffset(pos, coff, ustart, nblocks) : 0);
     K.v.push_back(nblocks ? voffset(pos + size, coff, ustart, nblocks) : 0);
     const uint32_t rows = flagstat_rows(R);
     for (int k = 0; k < 16; k++)
-      if (rows >> k & 1) K.counters[2 * k + ((R.flag & 0x200) ? 1 : 0)]++;
+      if (rows >> k & 1) K.counters[2 * k + ((R.flag & bam::kFlagQcFail) ? 1 : 0)]++;
     if (R.tid < 0) K.n_no_coor++;
     if (placed) {
-      ((R.flag & 4) ? K.unmapped : K.mapped)[(size_t)R.tid]++;
+      ((R.flag & bam::kFlagUnmapped) ? K.unmapped : K.mapped)[(size_t)R.tid]++;
       if (ok) K.n_intv[(size_t)R.tid] = std::max<int64_t>(K.n_intv[(size_t)R.tid], K.w1.back() + 1);
     }
     pos += size, ptid = R.tid, pbeg = R.beg, have_prev = true;

@@ -3,9 +3,9 @@
 //
 // The two-step path writes every kept read to region_cluster<k>.fasta (k_bam_emit, regionsplit.hip) and reads it back
 // for the UMI search (extract.hip).  Here the search runs on the record where it lies: k_bam_umi_search decodes the two
-// adapter windows of a kept record from its 4-bit sequence on the fly -- forward position x is stored position
-// (rev ? l_seq - 1 - x : x), complemented if rev, or the text "None" of a sequence-less record -- and runs the two
-// Myers passes of myers.h on each, one thread per (record, window), the two threads of a record in adjacent lanes.
+// adapter windows of a kept record from its 4-bit sequence on the fly -- bam::forward_base of bam_record.h, or the
+// text "None" of a sequence-less record -- and runs the two Myers passes of myers.h on each, one thread per (record,
+// window), the two threads of a record in adjacent lanes.
 // The window bytes come straight from global memory, a byte per two symbols: a packed window of the default 73 / 68
 // symbols is at most 37 bytes at an offset only the record knows, so an LDS stage (k_extract_win's) would be filled by
 // the very byte loads it is meant to replace.  The thread of the 5' window also walks the query name once (first ';',
@@ -17,6 +17,7 @@
 
 #include <stdint.h>
 
+#include "bam_record.h"
 #include "myers.h"
 #include "umiclust_internal.h"
 
@@ -24,22 +25,7 @@ namespace uc {
 
 namespace {
 
-__device__ __forceinline__ uint32_t bx_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ uint32_t bx_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-
-// "=ACMGRSVTWYHKDBN"[code], the table in two registers
-__device__ __forceinline__ char bx_sym(uint32_t code) {
-  const uint64_t lo = 0x565352474d43413dull, hi = 0x4e42444b48595754ull;
-  return (char)(((code & 8u) ? hi : lo) >> ((code & 7u) * 8));
-}
-// A <-> T, C <-> G, every other byte unchanged: k_bam_emit's complement and extract_umis.py's reverse_complement
-__device__ __forceinline__ char bx_comp(char ch) {
-  return ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-}
-
-// the read as k_bam_emit writes it: L bytes, byte x by at(x)
+// the read as k_bam_emit writes it: L bytes, byte x by at(x) (bam::forward_base, or the text "None")
 struct ReadText {
   const uint8_t* sq;
   int32_t lseq;
@@ -47,18 +33,15 @@ struct ReadText {
   bool rev;
   __device__ __forceinline__ char at(int x) const {
     if (lseq <= 0) return x == 0 ? 'N' : x == 1 ? 'o' : x == 2 ? 'n' : 'e';
-    const int y = rev ? lseq - 1 - x : x;
-    const char ch = bx_sym((sq[y >> 1] >> (((y & 1) ^ 1) * 4)) & 15u);
-    return rev ? bx_comp(ch) : ch;
+    return bam::forward_base(sq, lseq, rev, x);
   }
 };
-__device__ __forceinline__ ReadText read_text(const uint8_t* p) {
-  const uint32_t lrn = p[8], ncig = bx_u16(p + 12), flag = bx_u16(p + 14);
+__device__ __forceinline__ ReadText read_text(const uint8_t* rec) {
   ReadText t;
-  t.lseq = (int32_t)bx_u32(p + 16);
-  t.sq = p + 32 + lrn + 4 * ncig;
+  t.lseq = bam::l_seq(rec);
+  t.sq = bam::seq(rec, bam::l_read_name(rec), bam::n_cigar_op(rec));
   t.L = t.lseq > 0 ? t.lseq : 4;
-  t.rev = (flag & 0x10u) != 0;
+  t.rev = (bam::flag(rec) & bam::kFlagReverse) != 0;
   return t;
 }
 
@@ -80,8 +63,8 @@ __global__ __launch_bounds__(256) void k_bam_umi_search(const uint8_t* __restric
   int32_t o[3] = {-1, -1, -1};
   int64_t total = 0;
   if (kept) {
-    const uint8_t* p = raw + roff[r] + 4;
-    const ReadText T = read_text(p);
+    const uint8_t* rec = raw + roff[r];
+    const ReadText T = read_text(rec);
     // Python slicing: seq[:a5] and seq[-a3:] (a3 == 0 is the whole read)
     int w0, wl;
     if (w == 0) {
@@ -95,8 +78,8 @@ __global__ __launch_bounds__(256) void k_bam_umi_search(const uint8_t* __restric
     int32_t* q = res + t * 3;
     q[0] = o[0], q[1] = o[1], q[2] = o[2];
     if (w == 0) {
-      const uint8_t* name = p + 32;
-      const int nl = (int)p[8] - 1;
+      const uint8_t* name = bam::name(rec);
+      const int nl = (int)bam::l_read_name(rec) - 1;
       const uint64_t pat = 0x3d646e61727473ull;  // "strand=", byte x = its symbol x
       int rid = nl, match = 0;
       bool space = false, strand = false;
@@ -129,10 +112,10 @@ __global__ __launch_bounds__(256) void k_bam_emit_umi(const uint8_t* __restrict_
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= n || len[r] <= 0) return;
-  const uint8_t* p = raw + roff[r] + 4;
-  const ReadText T = read_text(p);
-  const uint8_t* name = p + 32;
-  const int nl = (int)p[8] - 1;
+  const uint8_t* rec = raw + roff[r];
+  const ReadText T = read_text(rec);
+  const uint8_t* name = bam::name(rec);
+  const int nl = (int)bam::l_read_name(rec) - 1;
   int rid = nl;  // get_read_name: the name up to its first ';'
   for (int x0 = 0; x0 < nl && rid == nl; x0 += 64) {
     const unsigned long long m = __ballot(x0 + lane < nl && name[x0 + lane] == ';');
@@ -178,8 +161,8 @@ __global__ __launch_bounds__(256) void k_bam_emit_umi(const uint8_t* __restrict_
     for (int x = lane; x < l5; x += 64) cmb[x] = T.at(b5 + x);
     for (int x = lane; x < l3; x += 64) cmb[l5 + x] = T.at(b3 + x);
   } else {
-    for (int x = lane; x < l3; x += 64) cmb[x] = bx_comp(T.at(b3 + l3 - 1 - x));
-    for (int x = lane; x < l5; x += 64) cmb[l3 + x] = bx_comp(T.at(b5 + l5 - 1 - x));
+    for (int x = lane; x < l3; x += 64) cmb[x] = bam::complement(T.at(b3 + l3 - 1 - x));
+    for (int x = lane; x < l5; x += 64) cmb[l3 + x] = bam::complement(T.at(b5 + l5 - 1 - x));
   }
 }
 

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_bai_mark(BaiIn I, int64_t* __restrict__
   if (r >= I.n) return;
   const bool kept = !I.keep || I.keep[r];
   kf[r] = kept ? 1 : 0;
-  sz[r] = kept ? 4 + (int64_t)bai::ld32(I.raw + I.roff[r]) : 0;
+  sz[r] = kept ? 4 + (int64_t)bam::block_size(I.raw + I.roff[r]) : 0;
 }
 
 // kidx[r] = the kept records before r, spos[r] = where record r starts in the written stream
@@ -50,14 +50,14 @@ __global__ __launch_bounds__(256) void k_bai_keys(BaiIn I, const int64_t* __rest
     placed = R.tid >= 0 && R.tid < I.nref;
     ok = placed && st != bai::kRange;
     w1 = ok ? (int32_t)((R.end - 1) >> 14) : 0;
-    const int64_t j = kidx[r], at = spos[r], size = 4 + (int64_t)bai::ld32(p);
+    const int64_t j = kidx[r], at = spos[r], size = 4 + (int64_t)bam::block_size(p);
     o.rec[j] = (uint32_t)r, o.tid[j] = R.tid, o.beg[j] = (int32_t)R.beg, o.status[j] = st;
-    o.bin[j] = ok ? bai::reg2bin((int)R.beg, (int)R.end) : 0;
+    o.bin[j] = ok ? bam::reg2bin(R.beg, R.end) : 0;
     o.w0[j] = ok ? (int32_t)(R.beg >> 14) : 0, o.w1[j] = w1;
     o.u[j] = I.nblocks ? bai::voffset(at, I.coff, I.ustart, I.nblocks) : 0;
     o.v[j] = I.nblocks ? bai::voffset(at + size, I.coff, I.ustart, I.nblocks) : 0;
   }
-  const bool qcfail = (R.flag & 0x200) != 0;
+  const bool qcfail = (R.flag & bam::kFlagQcFail) != 0;
   for (int k = 0; k < 16; k++) {
     const bool hit = (rows >> k) & 1u;
     const int all = __popcll(__ballot(hit)), fail = __popcll(__ballot(hit && qcfail));
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_bai_keys(BaiIn I, const int64_t* __rest
     const int32_t t = __shfl(R.tid, lead);
     const bool mine = placed && R.tid == t;
     const u64 group = __ballot(mine);
-    const int nmapped = __popcll(__ballot(mine && !(R.flag & 4))), nunmapped = __popcll(group) - nmapped;
+    const int nmapped = __popcll(__ballot(mine && !(R.flag & bam::kFlagUnmapped))), nunmapped = __popcll(group) - nmapped;
     int intv = mine && ok ? w1 + 1 : 0;
     for (int d = 32; d; d >>= 1) intv = max(intv, __shfl_xor(intv, d));
     if (lane == lead) {

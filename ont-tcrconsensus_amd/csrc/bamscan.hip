@@ -11,7 +11,7 @@
 // hash in an open-addressing table (overlap.hip's scheme: CAS claim, atomicMin of the record index into the slot's
 // representative, atomicAdd on its count) and k_cs_verify compares every record's bytes with its representative's; a
 // mismatch raises the collision flag and the host re-runs with the next seed, so the groups are exact.  Byte-streaming
-// integer work: HBM-bound, no MFMA.  bam_host.cpp scan_record is the host restatement of k_bam_scan.
+// integer work: HBM-bound, no MFMA.  bam_host.cpp scan_record is the serial walk over the same rules (bam_record.h).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -22,20 +22,6 @@
 namespace uc {
 
 namespace {
-
-__device__ __forceinline__ uint32_t bs_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ uint32_t bs_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-
-__device__ __forceinline__ uint64_t bs_mix(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
 
 __device__ __forceinline__ int64_t wave_sum(int64_t v) {
   for (int d = 32; d > 0; d >>= 1) v += (int64_t)__shfl_xor((long long)v, d, 64);
@@ -54,14 +40,15 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
   const int lane = threadIdx.x & 63;
   if (r >= n) return;
   const int64_t ro = roff[r];
-  const uint8_t* f = raw + ro + 4;
-  int64_t end = ro + 4 + (int64_t)bs_u32(raw + ro);
+  const uint8_t* rec = raw + ro;
+  int64_t end = ro + 4 + (int64_t)bam::block_size(rec);
   if (end > raw_len) end = raw_len;
-  const uint32_t lrn = f[8], ncig = bs_u16(f + 12), flag = bs_u16(f + 14);
-  const int32_t lseq = (int32_t)bs_u32(f + 16);
-  const int8_t cls = (flag & 0x4u) ? bam::kScanUnmapped : (flag & 0x900u) ? bam::kScanSecondary : bam::kScanPrimary;
-  const int64_t cig = ro + 36 + (int64_t)lrn, cigend = cig + 4 * (int64_t)ncig;
-  const int64_t aux = cigend + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
+  const uint32_t lrn = bam::l_read_name(rec), ncig = bam::n_cigar_op(rec), flag = bam::flag(rec);
+  const int32_t lseq = bam::l_seq(rec);
+  const int8_t cls = (flag & bam::kFlagUnmapped) ? bam::kScanUnmapped
+                     : (flag & bam::kFlagNotPrimary) ? bam::kScanSecondary : bam::kScanPrimary;
+  const uint8_t* cig = bam::cigar(rec, lrn);
+  const int64_t aux = ro + bam::aux_offset(lrn, ncig, lseq);
   int8_t bad = 0;
   int64_t rl = 0, cols = 0, nm = 0, cs_off = 0;
   int32_t cs_len = -1;
@@ -71,13 +58,12 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
     bad = 1;
   } else {
     for (uint32_t x = (uint32_t)lane; x < ncig; x += 64) {
-      const uint32_t v = bs_u32(raw + cig + 4 * (int64_t)x), op = v & 15u;
-      if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += v >> 4;
-      if (op <= 2) cols += v >> 4;
+      const uint32_t v = bam::le32(cig + 4 * (int64_t)x), op = v & 15u;
+      if (bam::op_on_reference(op)) rl += v >> 4;
+      if (bam::op_in_columns(op)) cols += v >> 4;
     }
-    rl = wave_sum(rl);
+    rl = bam::reference_span(wave_sum(rl));
     cols = wave_sum(cols);
-    if (rl == 0) rl = 1;  // htslib's bam_endpos: a zero reference span counts as 1
     if (cls == bam::kScanPrimary) {
       bool have_nm = false, have_cs = false;
       int64_t cur = aux;  // wave-uniform: every lane reads the same tag and type bytes
@@ -89,17 +75,14 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
         const uint8_t t0 = raw[cur], t1 = raw[cur + 1], ty = raw[cur + 2];
         const bool is_nm = t0 == 'N' && t1 == 'M' && !have_nm, is_cs = t0 == 'c' && t1 == 's' && !have_cs;
         const int64_t v = cur + 3;
-        const int sz = (ty == 'A' || ty == 'c' || ty == 'C') ? 1 : (ty == 's' || ty == 'S') ? 2
-                       : (ty == 'i' || ty == 'I' || ty == 'f') ? 4 : 0;
+        const int sz = bam::aux_fixed_size(ty);
         if (sz) {
           if (v + sz > end || is_cs || (is_nm && (ty == 'A' || ty == 'f'))) {
             bad = 1;
             break;
           }
           if (is_nm) {
-            const uint8_t* q = raw + v;
-            nm = ty == 'c' ? (int64_t)(int8_t)q[0] : ty == 'C' ? (int64_t)q[0] : ty == 's' ? (int64_t)(int16_t)bs_u16(q)
-                 : ty == 'S' ? (int64_t)bs_u16(q) : ty == 'i' ? (int64_t)(int32_t)bs_u32(q) : (int64_t)bs_u32(q);
+            nm = bam::aux_int_value(ty, raw + v);
             nm_present = 1;
             have_nm = true;
           }
@@ -109,10 +92,8 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
             bad = 1;
             break;
           }
-          const uint8_t sub = raw[v];
-          const int64_t cnt = (int64_t)bs_u32(raw + v + 1);
-          const int ss = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
-                         : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+          const int64_t cnt = (int64_t)bam::le32(raw + v + 1);
+          const int ss = bam::aux_array_elem_size(raw[v]);
           if (!ss || v + 5 + ss * cnt > end) {
             bad = 1;
             break;
@@ -131,8 +112,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
             const uint8_t b = in ? raw[idx] : (uint8_t)1;
             const unsigned long long m = __ballot(in && b == 0);
             const int first = m ? __ffsll(m) - 1 : 64;
-            if (is_cs && in && lane < first)
-              sum += bs_mix(seed + ((uint64_t)(idx - v) + 1) * bam::kCsK1 + ((uint64_t)b + 1) * bam::kCsK2);
+            if (is_cs && in && lane < first) sum += bam::cs_term(seed, (uint64_t)(idx - v), b);
             if (m) {
               nul = z + first;
               break;
@@ -147,8 +127,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
             sum = (uint64_t)wave_sum((int64_t)sum);
             cs_off = v;
             cs_len = (int32_t)(nul - v);
-            const uint64_t h = bs_mix(sum ^ ((uint64_t)(nul - v) * bam::kCsK3)) & hmask;
-            cs_hash = h == bam::kCsEmpty ? h - 1 : h;
+            cs_hash = bam::cs_finish(sum, (uint64_t)(nul - v), hmask);
             have_cs = true;
           }
           cur = nul + 1;
@@ -160,7 +139,7 @@ __global__ __launch_bounds__(kScanWaves * 64) void k_bam_scan(const uint8_t* __r
   }
   if (lane == 0) {
     o.cls[r] = cls;
-    o.ref[r] = (int32_t)bs_u32(f);
+    o.ref[r] = bam::ref_id(rec);
     o.l_seq[r] = lseq;
     o.reflen[r] = rl;
     o.cols[r] = cols;

@@ -37,7 +37,7 @@ __global__ void k_split_cols(const BamScanCols o, const uint8_t* __restrict__ ra
   } else if (scan == bam::kScanSecondary) {
     c = kBamSecondary;
   } else {
-    const uint32_t lrn = raw[roff[r] + 12];  // l_read_name, with the NUL; the host refuses a kept record with 0
+    const uint32_t lrn = bam::l_read_name(raw + roff[r]);  // the host refuses a kept record with 0
     region_class(ref, nref, ref_len, ref_bucket, o.reflen[r], lseq, lrn, minov, s5 + s3, c, k, len);
   }
   cls[r] = c;
@@ -52,11 +52,10 @@ __global__ void k_name_suffix(const uint8_t* __restrict__ raw, const int64_t* __
                               int64_t* __restrict__ value, uint8_t* __restrict__ status) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  const uint8_t* p = raw + roff[r];
-  const uint32_t bs = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-  const uint32_t room = bs - 32;  // record_offsets: block_size >= 32
-  int len = (int)(p[12] < room ? p[12] : room);
-  const uint8_t* name = p + 36;
+  const uint8_t* rec = raw + roff[r];
+  const uint32_t room = bam::block_size(rec) - 32, lrn = bam::l_read_name(rec);  // record_offsets: block_size >= 32
+  int len = (int)(lrn < room ? lrn : room);
+  const uint8_t* name = bam::name(rec);
   if (len && name[len - 1] == 0) len--;
   int64_t v = 0, mul = 1;
   int nd = 0;

@@ -13,9 +13,9 @@ using namespace uc;
 using namespace uc::io;
 
 std::string_view uc::record_name(const RawBuf& raw, const std::vector<int64_t>& roff, int64_t r) {
-  const uint8_t* f = raw.data() + roff[r] + 4;
-  const size_t lrn = std::min<size_t>(f[8], (size_t)bam::rd_block(raw.data() + roff[r]) - 32);
-  return {(const char*)f + 32, lrn ? strnlen((const char*)f + 32, lrn) : 0};
+  const uint8_t* rec = raw.data() + roff[r];
+  const size_t lrn = std::min<size_t>(bam::l_read_name(rec), (size_t)bam::block_size(rec) - 32);
+  return {(const char*)bam::name(rec), lrn ? strnlen((const char*)bam::name(rec), lrn) : 0};
 }
 BamSession* uc::bam_session(Ctx* c) {
   if (!c->bs.open) c->fail(UMICLUST_ESTATE, "no BAM session is open (umiclust_bam_open)");

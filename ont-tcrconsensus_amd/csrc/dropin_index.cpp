@@ -185,7 +185,7 @@ int64_t umiclust_bam_write_index(umiclust_ctx* ctx, const uint8_t* keep, const c
       const size_t nb = S.write_coff.size();
       size_t total = S.hdr.end;
       for (size_t r = 0; r < S.roff.size(); r++)
-        if (keep[r]) total += 4 + (size_t)bam::rd_block(S.raw.data() + S.roff[r]);
+        if (keep[r]) total += 4 + (size_t)bam::block_size(S.raw.data() + S.roff[r]);
       if (nb != (total + bam::kBgzfPayload - 1) / bam::kBgzfPayload + 1)
         c->fail(UMICLUST_ESTATE, "the writer recorded %zu blocks for a stream of %zu bytes", nb, total);
       std::vector<int64_t> ustart(nb);
@@ -283,7 +283,7 @@ int32_t umiclust_bam_index_probe(umiclust_ctx* ctx, const uint8_t* keep, const i
     if (nblocks < 1 || !coff || !ustart || run_cap < 0 || linear_cap < 0) c->fail(UMICLUST_EINVAL, "bad argument");
     int64_t total = (int64_t)S.hdr.end;
     for (size_t r = 0; r < S.roff.size(); r++)
-      if (!keep || keep[r]) total += 4 + (int64_t)bam::rd_block(S.raw.data() + S.roff[r]);
+      if (!keep || keep[r]) total += 4 + (int64_t)bam::block_size(S.raw.data() + S.roff[r]);
     bool good = ustart[0] == 0 && ustart[nblocks - 1] == total && coff[0] >= 0 && coff[nblocks - 1] < ((int64_t)1 << 47);
     for (int64_t b = 1; b < nblocks && good; b++) good = ustart[b] >= ustart[b - 1] && coff[b] > coff[b - 1] && ustart[b] - ustart[b - 1] <= 0x10000;
     if (!good)

@@ -17,8 +17,6 @@ using namespace uc;
 using namespace uc::io;
 
 namespace {
-int32_t rd_i32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
-
 // The text of the kept records among [0, stop), grouped by bucket and in BAM order within a bucket: the slots are laid
 // out here from olen (a kept record may have none), the bytes written by `launch(d_pos, d_out)` (k_bam_emit or
 // k_bam_emit_umi) and then by `patch(pos, out)` on the host, and every bucket's text goes to path_of(bucket), opened
@@ -259,9 +257,9 @@ int64_t split_core(Ctx* c, SplitSource& src, const SplitArgs& a, const ExtractPa
   int32_t nb = 0;  // the kept records' buckets are [0, nb)
   for (int64_t r = 0; r < stop; r++)
     if (cls[r] == kBamKept) {
-      const uint8_t* f = raw.data() + roff[r] + 4;
-      if (f[8] == 0) c->fail(UMICLUST_EFORMAT, "BAM record %lld: l_read_name 0", (long long)r);
-      detected[rreg[rd_i32(f)]] = 1;
+      const uint8_t* rec = raw.data() + roff[r];
+      if (bam::l_read_name(rec) == 0) c->fail(UMICLUST_EFORMAT, "BAM record %lld: l_read_name 0", (long long)r);
+      detected[rreg[bam::ref_id(rec)]] = 1;
       nb = std::max(nb, bkt[r] + 1);
     }
   // output grouped by bucket (the reference's KeyError ends the pipeline before extract_umis starts: no UMI file then)
@@ -286,7 +284,7 @@ int64_t split_core(Ctx* c, SplitSource& src, const SplitArgs& a, const ExtractPa
   }
   for (int x = 0; x < 4; x++) a.counts[x] = cnt[x];
   if (stop < n) {
-    const int32_t ref = rd_i32(raw.data() + roff[stop] + 4);
+    const int32_t ref = bam::ref_id(raw.data() + roff[stop]);
     const std::string nm = ref >= 0 && ref < nref ? refname[ref] : std::string("None");
     if (a.missing_name && a.missing_cap > 0) snprintf(a.missing_name, (size_t)a.missing_cap, "%s", nm.c_str());
     c->fail(UMICLUST_EFORMAT, "KeyError: '%s'", nm.c_str());

@@ -15,14 +15,10 @@
 #include <stdint.h>
 
 #include "bam_bounds.h"
+#include "bam_record.h"
 #include "umiclust_internal.h"
 
 namespace uc {
-
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
 // region_class, the decision chain on a primary record (:261-271), with long_bound, the `too long` bound as the
 // reference rounds it (:264-267): bam_bounds.h
@@ -34,27 +30,27 @@ __global__ void k_bam_classify(const uint8_t* __restrict__ raw, const int64_t* _
                                int32_t* __restrict__ cluster, int64_t* __restrict__ outlen) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  const uint8_t* p = raw + roff[r] + 4;  // past block_size
-  const int32_t ref = (int32_t)ld_u32(p);
-  const uint32_t lrn = p[8], ncig = ld_u16(p + 12), flag = ld_u16(p + 14);
-  const int32_t lseq = (int32_t)ld_u32(p + 16);
+  const uint8_t* rec = raw + roff[r];
+  const int32_t ref = bam::ref_id(rec);
+  const uint32_t lrn = bam::l_read_name(rec), ncig = bam::n_cigar_op(rec), flag = bam::flag(rec);
+  const int32_t lseq = bam::l_seq(rec);
   int8_t c;
   int32_t k = -1;
   int64_t len = 0;
-  if (flag & 0x4u) {
+  if (flag & bam::kFlagUnmapped) {
     c = kBamUnmapped;
-  } else if (flag & 0x900u) {
+  } else if (flag & bam::kFlagNotPrimary) {
     c = kBamSecondary;
   } else {
-    const uint8_t* cg = p + 32 + lrn;
+    const uint8_t* cg = bam::cigar(rec, lrn);
     int64_t rl = 0;
     for (uint32_t x = 0; x < ncig; x++) {
-      const uint32_t v = ld_u32(cg + 4 * x), op = v & 15u;
-      if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += v >> 4;
+      const uint32_t v = bam::le32(cg + 4 * x);
+      if (bam::op_on_reference(v & 15u)) rl += v >> 4;
     }
-    // pysam's reference_length = bam_endpos - pos, and htslib's bam_endpos counts a zero reference span (no CIGAR,
-    // or only I/S/H/P ops) as 1: such a record is 1 base long and drops as short (:261-263)
-    if (rl == 0) rl = 1;
+    // pysam's reference_length = bam_endpos - pos: a record without a reference span is 1 base long and drops as
+    // short (:261-263)
+    rl = bam::reference_span(rl);
     region_class(ref, nref, ref_len, ref_cluster, rl, lseq, lrn, minov, s5 + s3, c, k, len);
   }
   cls[r] = c;
@@ -68,11 +64,11 @@ __global__ void k_bam_emit(const uint8_t* __restrict__ raw, const int64_t* __res
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= n || cls[r] != kBamKept) return;
-  const uint8_t* p = raw + roff[r] + 4;
-  const uint32_t lrn = p[8], ncig = ld_u16(p + 12), flag = ld_u16(p + 14);
-  const int32_t lseq = (int32_t)ld_u32(p + 16);
-  const uint8_t* name = p + 32;
-  const uint8_t* sq = name + lrn + 4 * ncig;
+  const uint8_t* rec = raw + roff[r];
+  const uint32_t lrn = bam::l_read_name(rec), ncig = bam::n_cigar_op(rec), flag = bam::flag(rec);
+  const int32_t lseq = bam::l_seq(rec);
+  const uint8_t* name = bam::name(rec);
+  const uint8_t* sq = bam::seq(rec, lrn, ncig);
   char* o = out + pos[r];
   const int nl = (int)lrn - 1;
   for (int x = lane; x < nl; x += 64) o[1 + x] = (char)name[x];
@@ -80,25 +76,17 @@ __global__ void k_bam_emit(const uint8_t* __restrict__ raw, const int64_t* __res
     o[0] = '>';
     const char* tag = ";strand=";
     for (int x = 0; x < 8; x++) o[1 + nl + x] = tag[x];
-    o[1 + nl + 8] = (flag & 0x10u) ? '-' : '+';
+    o[1 + nl + 8] = (flag & bam::kFlagReverse) ? '-' : '+';
     o[1 + nl + 9] = '\n';
   }
   char* s = o + 1 + nl + 10;
-  const char kSym[16] = {'=', 'A', 'C', 'M', 'G', 'R', 'S', 'V', 'T', 'W', 'Y', 'H', 'K', 'D', 'B', 'N'};
   if (lseq <= 0) {
     if (lane < 4) s[lane] = "None"[lane];
     if (lane == 0) s[4] = '\n';
     return;
   }
-  const bool rev = (flag & 0x10u) != 0;
-  for (int x = lane; x < lseq; x += 64) {
-    // forward sequence: position x of the read = stored position (rev ? lseq - 1 - x : x), complemented if rev
-    const int y = rev ? lseq - 1 - x : x;
-    const uint32_t code = (sq[y >> 1] >> (((y & 1) ^ 1) * 4)) & 15u;
-    char ch = kSym[code];
-    if (rev) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
-    s[x] = ch;
-  }
+  const bool rev = (flag & bam::kFlagReverse) != 0;
+  for (int x = lane; x < lseq; x += 64) s[x] = bam::forward_base(sq, lseq, rev, x);
   if (lane == 0) s[lseq] = '\n';
 }
 

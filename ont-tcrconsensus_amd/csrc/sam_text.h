@@ -1,11 +1,11 @@
 // sam_text.h -- SAM text to BAM records, HIP-free (policy O9: restated, not pinned).
 //
 // Everything that decides what a SAM line becomes is here, once, for the host and for the device: the field split, the
-// number formats, the CIGAR and aux rules, the record layout, reg2bin and the sort key.  sam::measure<Io> sizes a line
-// and sam::encode<Io> writes its record; what an Io supplies is only how text bytes are fetched, how record bytes are
-// put and how the lanes of an Io add up what each of them saw: HostIo below is the plain serial one (sam::encode_host,
-// the host restatement of the kernels of samsort.hip, as uc::inflate_block restates k_bgzf_inflate), samsort.hip has
-// the one whose 64 lanes work together.  Every decision is the same on all lanes of an Io.
+// number formats, the CIGAR and aux rules and the sort key (the record layout and reg2bin: bam_record.h).  sam::measure<Io>
+// sizes a line and sam::encode<Io> writes its record; what an Io supplies is only how text bytes are fetched, how record
+// bytes are put and how the lanes of an Io add up what each of them saw: HostIo below is the plain serial one
+// (sam::encode_host, the host restatement of the kernels of samsort.hip, as uc::inflate_block restates k_bgzf_inflate),
+// samsort.hip has the one whose 64 lanes work together.  Every decision is the same on all lanes of an Io.
 //
 // The rules restate htslib's sam_parse1 and samtools' coordinate order (bam1_cmp_core under SO:coordinate, ties in
 // input order).  Where this file is stricter than htslib it refuses, which is louder than guessing:
@@ -27,13 +27,7 @@
 #include <unordered_set>
 #include <vector>
 
-#ifndef UC_HD
-#if defined(__HIPCC__)
-#define UC_HD __host__ __device__
-#else
-#define UC_HD
-#endif
-#endif
+#include "bam_record.h"  // the record's layout, reg2bin, mix64, and UC_HD
 
 namespace uc {
 namespace sam {
@@ -64,18 +58,10 @@ struct Names {
   int32_t nref;
 };
 // The hash of a name, order-independent over its bytes so that the lanes of an Io can add their shares.
-UC_HD inline uint64_t mix(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
 UC_HD inline uint64_t name_term(uint64_t i, uint8_t b) {
-  return mix((i + 1) * 0x9e3779b97f4a7c15ull + ((uint64_t)b + 1) * 0xd6e8feb86659fd93ull);
+  return bam::mix64((i + 1) * 0x9e3779b97f4a7c15ull + ((uint64_t)b + 1) * 0xd6e8feb86659fd93ull);
 }
-UC_HD inline uint64_t name_finish(uint64_t sum, uint64_t len) { return mix(sum ^ (len * 0xa0761d6478bd642full)); }
+UC_HD inline uint64_t name_finish(uint64_t sum, uint64_t len) { return bam::mix64(sum ^ (len * 0xa0761d6478bd642full)); }
 
 // What measure leaves for encode: f[k] = the start of mandatory field k (0..10) relative to the line, f[11] = one past
 // the tab (or the line end) that closes field 10 = the start of the aux fields; field k is [f[k], f[k + 1] - 1).
@@ -96,19 +82,10 @@ struct FSlot {
 // tid (-1 last) << 32 | (pos + 1) << 1 | reverse: samtools' bam1_cmp_core for SO:coordinate.  pos + 1 is the POS
 // field, 0 .. 2^31 - 1, and the tid of a record without one is nref: 63 bits at the most.
 UC_HD inline uint64_t sort_key(int32_t tid, int32_t pos, uint32_t flag, int32_t nref) {
-  return ((uint64_t)(uint32_t)(tid < 0 ? nref : tid) << 32) | ((uint64_t)(uint32_t)(pos + 1) << 1) | ((flag >> 4) & 1u);
+  return ((uint64_t)(uint32_t)(tid < 0 ? nref : tid) << 32) | ((uint64_t)(uint32_t)(pos + 1) << 1) |
+         ((flag & bam::kFlagReverse) ? 1u : 0u);
 }
-// htslib's hts_reg2bin(beg, end, 14, 5), on arithmetic shifts: beg = -1, end = 0 gives 4680
-UC_HD inline int32_t reg2bin(int64_t beg, int64_t end) {
-  --end;
-  if (beg >> 14 == end >> 14) return (int32_t)(4681 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (int32_t)(585 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (int32_t)(73 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (int32_t)(9 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (int32_t)(1 + (beg >> 26));
-  return 0;
-}
-// the 4-bit code of a base: "=ACMGRSVTWYHKDBN", case-insensitive, anything else 15
+// the 4-bit code of a base, the inverse of bam::seq_symbol: case-insensitive, anything else 15
 UC_HD inline uint32_t seq_code(uint8_t c) {
   switch (c >= 'a' && c <= 'z' ? c - 32 : c) {
     case '=': return 0;
@@ -144,7 +121,6 @@ UC_HD inline int32_t cigar_op(uint8_t c) {
     default: return -1;
   }
 }
-UC_HD inline bool op_on_reference(int32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
 
 // 1..10 decimal digits at [s, t); the same on every lane (each reads the same bytes)
 template <class Io>
@@ -241,7 +217,7 @@ UC_HD inline int32_t parse_fixed(Io& io, const Names& N, int64_t b, const Fields
       const uint32_t ln = op < 0 ? 0u : cigar_len_before(io, s, p);
       wrong |= ln == 0;
       nops++;
-      if (op_on_reference(op)) rl += ln;
+      if (bam::op_on_reference((uint32_t)op)) rl += ln;
     }
     if (io.any(wrong)) return bad(kEFormat, kFCigar);
     nops = io.sum(nops), rl = io.sum(rl);
@@ -281,7 +257,7 @@ UC_HD inline int32_t aux_walk(Io& io, int64_t a, int64_t e, int64_t& o, int32_t&
       if (!parse_i(io, v, t, m, neg) || m > (neg ? 0x80000000ull : 0xffffffffull)) return bad(kEFormat, kFAux);
       if (m == 0) neg = false;
       const uint8_t code = neg ? (m <= 128 ? 'c' : m <= 32768 ? 's' : 'i') : (m <= 255 ? 'C' : m <= 65535 ? 'S' : 'I');
-      const int w = code == 'c' || code == 'C' ? 1 : code == 's' || code == 'S' ? 2 : 4;
+      const int w = bam::aux_fixed_size(code);
       if (kWrite && io.lane() == 0) {
         const uint32_t bits = neg ? 0u - (uint32_t)m : (uint32_t)m;
         io.put(o + 2, code);
@@ -326,7 +302,7 @@ UC_HD inline Measured measure(Io& io, const Names& N, int64_t b, int64_t e, Fiel
   F.f[11] = (int32_t)(s - b);
   Fixed X;
   if ((M.status = parse_fixed(io, N, b, F, X)) != kOk) return M;
-  int64_t o = 36 + X.lname + 4 * (int64_t)X.ncig + (X.lseq + 1) / 2 + X.lseq;
+  int64_t o = bam::aux_offset(X.lname, X.ncig, X.lseq);
   if (s <= e && (M.status = aux_walk<false>(io, s, e, o, M.nf)) != kOk) return M;
   if (o > 0x7fffffff) return M.status = bad(kERange, kFLine), M;
   M.size = o;
@@ -344,20 +320,19 @@ UC_HD inline void encode(Io& io, const Names& N, int64_t b, int64_t e, const Fie
     const auto put32 = [&](int64_t o, uint32_t v) {
       for (int k = 0; k < 4; k++) io.put(o + k, (uint8_t)(v >> (8 * k)));
     };
-    // bin: the reference span of a mapped record with a CIGAR, else 1; a span of 0 counts as 1
-    int64_t rlen = !(X.flag & 4) && X.ncig ? X.rlen : 1;
-    if (rlen == 0) rlen = 1;
-    const uint32_t bin = (uint32_t)reg2bin(X.pos, (int64_t)X.pos + rlen) & 0xffffu;
-    put32(0, (uint32_t)(size - 4));
-    put32(4, (uint32_t)X.tid), put32(8, (uint32_t)X.pos);
-    io.put(12, (uint8_t)X.lname), io.put(13, (uint8_t)X.mapq);
-    io.put(14, (uint8_t)bin), io.put(15, (uint8_t)(bin >> 8));
-    io.put(16, (uint8_t)X.ncig), io.put(17, (uint8_t)(X.ncig >> 8));
-    io.put(18, (uint8_t)X.flag), io.put(19, (uint8_t)(X.flag >> 8));
-    put32(20, (uint32_t)X.lseq), put32(24, (uint32_t)X.ntid), put32(28, (uint32_t)X.npos), put32(32, (uint32_t)X.tlen);
-    io.put(36 + X.lname - 1, 0);
+    const auto put16 = [&](int64_t o, uint32_t v) { io.put(o, (uint8_t)v), io.put(o + 1, (uint8_t)(v >> 8)); };
+    // bin: the reference span of a mapped record with a CIGAR, else 1
+    const int64_t rlen = bam::reference_span(!(X.flag & bam::kFlagUnmapped) && X.ncig ? X.rlen : 1);
+    put32(bam::kBlockSize, (uint32_t)(size - 4));
+    put32(bam::kRefId, (uint32_t)X.tid), put32(bam::kPos, (uint32_t)X.pos);
+    io.put(bam::kLReadName, (uint8_t)X.lname), io.put(bam::kMapq, (uint8_t)X.mapq);
+    put16(bam::kBin, (uint32_t)bam::reg2bin(X.pos, (int64_t)X.pos + rlen));
+    put16(bam::kNCigarOp, (uint32_t)X.ncig), put16(bam::kFlag, (uint32_t)X.flag);
+    put32(bam::kLSeq, (uint32_t)X.lseq), put32(bam::kNextRefId, (uint32_t)X.ntid);
+    put32(bam::kNextPos, (uint32_t)X.npos), put32(bam::kTlen, (uint32_t)X.tlen);
+    io.put(bam::kName + X.lname - 1, 0);
   }
-  int64_t o = 36;
+  int64_t o = bam::kName;
   for (int64_t i = io.lane(); i < X.lname - 1; i += io.lanes()) io.put(o + i, io.at(fs(0) + i));
   o += X.lname;
   // CIGAR: op k of the text is word k; a step of lanes() bytes ranks its letters among themselves

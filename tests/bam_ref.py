@@ -195,12 +195,16 @@ class Record:
         self.raw, self.off, self.index, self._refs = raw, off, index, refs
         bs = struct.unpack_from("<i", raw, off)[0]
         self.end = off + 4 + bs
-        (self.ref, self.pos, lrn, _mq, _bin, ncig, self.flag, self.l_seq) = struct.unpack_from("<iiBBHHHi", raw, off + 4)
+        (self.ref, self.pos, lrn, mapq, bin_, ncig, self.flag, self.l_seq, next_ref, next_pos, tlen) = \
+            struct.unpack_from("<iiBBHHHiiii", raw, off + 4)
         p = off + 36
         self.query_name = raw[p:p + lrn - 1].decode()
         p += lrn
         self.cigar = [(v & 15, v >> 4) for v in struct.unpack_from("<%dI" % ncig, raw, p)]
         self.aux = p + 4 * ncig + (self.l_seq + 1) // 2 + self.l_seq
+        # the fixed fields in file order, then where the aux fields start within the record
+        self.fixed = [self.ref, self.pos, lrn, mapq, bin_, ncig, self.flag, self.l_seq, next_ref, next_pos, tlen,
+                      self.aux - off]
         self.bytes = raw[off:self.end]
 
     @property

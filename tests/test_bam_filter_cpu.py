@@ -230,6 +230,40 @@ def test_bam_check_columns_and_writer_roundtrip(bam_check, name, tmp_path):
         raw[:start] + b"".join(r.bytes for i, r in enumerate(recs) if i % 2 == 0)
 
 
+def distinct_record_bam():
+    """One hand-built record in which no two fixed fields hold the same value: refID != next_refID, pos != next_pos, an
+    odd l_seq, the shortest name (l_read_name = 1) and no CIGAR (n_cigar_op = 0), so that its aux fields would start
+    at 36 + 1 + 0 + 4 + 7 = 48 = 4 + block_size.  A reader that takes one field's offset for another's reads another
+    number."""
+    import struct
+    body = struct.pack("<iiBBHHHiiii", 3, 1000, 1, 37, 5000, 0, 0x210, 7, 2, 2000, -300) + b"\0" + \
+        bytes([0x12, 0x48, 0x12, 0x40]) + b"\xff" * 7
+    assert len(body) == 44
+    return bam_ref.build_raw([["r%d" % i, 5000] for i in range(4)], []) + struct.pack("<i", len(body)) + body
+
+
+@pytest.mark.parametrize("name", sorted(CASES) + ["distinct"])
+def test_bam_check_reads_the_fixed_fields_as_bam_ref_does(bam_check, name, tmp_path):
+    """The accessors and bam::aux_offset of csrc/bam_record.h (the `fix` lines of bam_check) against bam_ref's decoder,
+    which unpacks the fixed part in file order and names no offset: every fixture, and the record above."""
+    bam = tmp_path / "in.bam"
+    if name == "distinct":
+        raw = distinct_record_bam()
+        bam_ref.write_bgzf(bam, raw)
+    else:
+        raw = bam_ref.write_bam(bam, CASES[name]["refs"], CASES[name]["records"])
+    lines = bam_check(bam, tmp_path / "out")
+    got = {int(ln.split()[1]): [int(x) for x in ln.split()[2:]] for ln in lines if ln.startswith("fix ")}
+    recs = bam_ref.decode(raw)[2]
+    assert len(recs) >= 1 and sorted(got) == list(range(len(recs)))
+    for r, rec in enumerate(recs):
+        assert got[r] == rec.fixed, r
+    if name == "distinct":
+        assert "fields=ok" in lines
+        assert recs[0].fixed == [3, 1000, 1, 37, 5000, 0, 0x210, 7, 2, 2000, -300, 48]
+        assert len(set(recs[0].fixed)) == 12
+
+
 @pytest.mark.parametrize("field,value", [("l_read_name", 255), ("l_read_name", 5), ("l_read_name", 0),
                                          ("n_cigar_op", 65535), ("n_cigar_op", 3), ("l_seq", 1000), ("l_seq", 11),
                                          ("l_seq", -1), ("l_seq", 0x7fffffff)])

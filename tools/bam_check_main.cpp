@@ -1,12 +1,15 @@
 // bam_check_main.cpp -- drives the HIP-free side of the BAM session (ont-tcrconsensus_amd/csrc/bam_host.cpp) under
 // ASan + UBSan, without a GPU (make bam_check; tests/test_bam_filter_cpu.py).  The device is replaced by
-// bam::scan_record, the host restatement of k_bam_scan.
+// bam::scan_record, the serial walk of k_bam_scan over the same rules (csrc/bam_record.h).
 //
 //   bam_check <in.bam> <out prefix> <threads>
 //       inflates the file, parses the header, finds the record offsets, scans every record and prints
 //         refs=<n> then one `ref <name> <length>` line per reference,
 //         records=<n>, `fields=ok` or `fields=<message of bam::check_record_fields>` (what umiclust_region_split
-//         refuses before its kernels run), then per record `rec <r> cls ref l_seq reference_length cols nm nm_present cs_len bad cs=<string>`,
+//         refuses before its kernels run), then per record
+//         `fix <r> refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID next_pos tlen aux_offset`, the fixed
+//         fields as the accessors of bam_record.h read them and bam::aux_offset of the three lengths, and
+//         `rec <r> cls ref l_seq reference_length cols nm nm_present cs_len bad cs=<string>`,
 //       then round-trips the writer twice -- every record kept (<prefix>.all.bam) and every second record kept
 //       (<prefix>.alt.bam) -- re-inflates both and compares them with the header bytes + the kept records; prints
 //       `roundtrip ok`.  Exit status 0, or 2 with `err=<message>` when the file is not BGZF / BAM.
@@ -45,6 +48,11 @@ int main(int argc, char** argv) {
   printf("records=%zu\n", roff.size());
   printf("fields=%s\n", bam::check_record_fields(raw.data(), roff, err) ? "ok" : err.c_str());
   for (size_t r = 0; r < roff.size(); r++) {
+    const uint8_t* rec = raw.data() + roff[r];
+    printf("fix %zu %d %d %u %u %u %u %u %d %d %d %d %lld\n", r, bam::ref_id(rec), bam::pos(rec), bam::l_read_name(rec),
+           bam::mapq(rec), bam::bin(rec), bam::n_cigar_op(rec), bam::flag(rec), bam::l_seq(rec), bam::next_ref_id(rec),
+           bam::next_pos(rec), bam::tlen(rec),
+           (long long)bam::aux_offset(bam::l_read_name(rec), bam::n_cigar_op(rec), bam::l_seq(rec)));
     bam::ScanRow s;
     bam::scan_record(raw.data(), roff[r], bam::cs_seed(0), ~0ull, s);
     // the hash is a function of the bytes and the length alone, and never the table's empty key
@@ -68,7 +76,7 @@ int main(int argc, char** argv) {
         keep[r] = 1;
         nkeep++;
         const uint8_t* p = raw.data() + roff[r];
-        want.insert(want.end(), p, p + 4 + bam::rd_block(p));
+        want.insert(want.end(), p, p + 4 + bam::block_size(p));
       }
     const std::string path = std::string(argv[2]) + (mode == 0 ? ".all.bam" : ".alt.bam");
     const int64_t k = bam::write_bgzf(path.c_str(), raw.data(), hdr.end, roff, keep.data(), threads, err);
